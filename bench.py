@@ -14,6 +14,10 @@ before it touches the GPU -- and relays rank 0's JSON line; under `python -m tor
 launcher's.  Per step the ranks exchange what rank 0 needs (SURVEY 8e): the per-frame payload lengths (all_gather);
 `--gather-payloads` additionally gathers the packed residual streams to rank 0 (configs[3] read literally).
 Rank 0 prints ONE JSON line.
+
+`--steps K` is the number of timed steps at N = 1 (N > 1: at least K, see run_workload); the line's `ms_per_step` is the time of
+one of them.  `--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (step_outputs): the inputs are seeded
+synthetic sweeps, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -84,7 +88,13 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary measurements (configs[2] fused, the real sweep, the datalist feed) that follow the headline at N=1")
     ap.add_argument("--verify-frames", type=int, default=64, help="frames per pipeline slot checked against the oracle when no cpu_baseline leg runs")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's batch) as DIR/<name>.npy, float32 / float64, "
+                         "under 64 MB in all, for a fixed, seeded sample of the batch's frames (step_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -262,6 +272,43 @@ def dry_run_rank(a, rank, world):
 
 SETUP_ROUNDS = 8   # untimed runs of every pipeline slot before the warm-up steps (run_workload)
 LEN_EVERY = 8      # N > 1, lengths-only exchange: steps whose per-frame payload lengths travel in one all_gather
+DUMP_FRAMES = 32            # --dump-outputs: frames written (a fixed, seeded sample of the batch) ...
+DUMP_BYTES = 60 << 20       # ... fewer when their arrays would exceed this
+
+
+def step_outputs(buf, ground, general):
+    """--dump-outputs: what a caller of ops.compress_batch receives from one step, for the frames listed in frame_index (a fixed,
+    seeded sample of the batch), as host arrays in float32 / float64: ground plane, FPS centres (pixel and point), model rows,
+    pixels per label, residual count (nnz), range image, labels, the nnz quantised residuals of each frame concatenated in
+    frame_index order [and with `general` -- configs[2], the non-uniform framework -- salience levels and key point map].
+    Model rows: those of the labels that own a pixel, frame by frame in label order.  A label without pixels has a NaN row (the
+    reference's mean over nothing, pinned in tests/test_oracle_vs_ref.py) that no pixel reads; it is left out."""
+    import numpy as np
+    import torch
+    B, P, M, K = buf.B, buf.P, buf.cen_pix.shape[1], buf.model.shape[1]
+    frame_bytes = 4 * P * (4 if general else 3) + 20 * M + 28 * K + 48
+    S = max(1, min(B, DUMP_FRAMES, DUMP_BYTES // frame_bytes))
+    idx = np.sort(np.random.default_rng(0).choice(B, S, replace=False))
+    sel = torch.as_tensor(idx, device=buf.ri.device)
+
+    def pick(t):
+        return t.index_select(0, sel).cpu().numpy()
+    nnz, q16, seg = pick(buf.nnz), pick(buf.q16), pick(buf.seg)
+    owned = np.stack([np.bincount(f.reshape(-1).astype(np.int64), minlength=K)[:K] > 0 for f in seg])   # [S, K]: labels with pixels
+    out = {"frame_index": idx.astype(np.float64),
+           "ground": pick(ground).astype(np.float64),
+           "cen_pix": pick(buf.cen_pix).astype(np.float64),
+           "centers": pick(buf.centers),
+           "model": pick(buf.model)[owned],
+           "counts": pick(buf.counts).astype(np.float64),
+           "nnz": nnz.astype(np.float64),
+           "ri": pick(buf.ri),
+           "seg": seg.astype(np.float32),
+           "q": np.concatenate([q16[j, :n] for j, n in enumerate(nnz)]).astype(np.float32)}
+    if general:
+        out["salience"] = pick(buf.salience).astype(np.float32)
+        out["key_point_map"] = pick(buf.key_point_map).astype(np.float32)
+    return out
 
 
 def load_real_batch(path, ids, H, W, dev, shuffle=False):
@@ -527,6 +574,10 @@ def run_workload(a, ctx):
         return max(rank_dt), rank_dt
 
     dt, rank_dt = timed_region(steps)
+    dump = None
+    if getattr(a, "dump_outputs", None) and rank == 0:       # the pipeline slot of the last timed step, before anything else runs
+        k_last = (step_no[0] - 1) % depth
+        dump = step_outputs(bufs[k_last], gms_l[k_last], general)
     fps_ms, fps_n = timer.read()
     # N > 1: the OTHER exchange mode, timed right after the headline's with the same number of steps (SURVEY 8e names the gather
     # of the bitstreams; the default exchanges the lengths only): both are reported under `exchange_modes`
@@ -733,6 +784,12 @@ def run_workload(a, ctx):
                                  "outside); job time = slowest rank"},
             "roofline": roof,
         }
+        if dump is not None:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for name, arr in dump.items():
+                np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+            out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": sorted(dump), "bytes": int(sum(v.nbytes for v in dump.values())),
+                                   "frames_sampled": int(dump["frame_index"].size)}
         if steps != a.steps:
             out["steps_requested"] = a.steps
             out["config"]["min_timed_region_ms"] = float(os.environ.get("RPCC_BENCH_MIN_REGION_MS", "200"))
@@ -898,6 +955,7 @@ def run_secondary(a, ctx):
         for k, v in kw.items():
             setattr(b, k, v)
         b.cpu_sample, b.steps, b.warmup, b.h2d, b.fps_bruteforce = 0, max(20, min(a.steps, 50)), 5, False, False
+        b.dump_outputs = None       # (the headline's outputs only)
         b.groundless, b.scene, b.clusters = kw.get("groundless", 0), kw.get("scene", "default"), kw.get("clusters", a.clusters)
         if "lidar" not in kw:
             b.lidar = None

@@ -1,29 +1,36 @@
-"""The C restatement (oracle/rpcc_oracle.c) against the reference's own C++ compiled from its
-sources into oracle/_ref (`make -C oracle ref`), on seeded random inputs incl. edge cases, plus the
+"""The C restatement (oracle/rpcc_oracle.c) against the reference's own C++ on seeded random inputs incl. edge cases, plus the
 known-answer test of the restated glibc atan2f against this machine's libm.
 
-oracle/_ref is built in the build container (needs /root/reference) and travels to the GPU box as a
-built artefact; when it is absent these tests skip (the golden-vector tests still pin the oracle)."""
+The reference's side is stored: tests/golden/gen_golden_cpp.py ran the reference's C++ (compiled from its sources into oracle/_ref,
+`make -C oracle ref`) on the inputs the _*_inputs() helpers below build, and kept SHA-256 digests of its outputs, and of the inputs
+themselves, in tests/golden/ref_cpp_manifest.json.  The helpers are the one definition of those inputs, shared with the generator."""
 import ctypes as C
+import hashlib
+import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
 
-REFDIR = os.path.join(os.path.dirname(os.path.abspath(orc.__file__)), "_ref")
-have_ref = os.path.exists(os.path.join(REFDIR, ".built"))
-needs_ref = pytest.mark.skipif(not have_ref, reason="oracle/_ref not built (needs /root/reference)")
+HERE = os.path.dirname(os.path.abspath(__file__))
+MANIFEST = os.path.join(HERE, "golden", "ref_cpp_manifest.json")
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 @pytest.fixture(scope="module")
-def ref():
-    sys.path.insert(0, REFDIR)
-    import dataset_utils_cpp, segment_utils_cpp, quantization_utils_cpp, feature_extractor_cpp, contour_utils_cpp  # noqa
-    return dict(ds=dataset_utils_cpp, seg=segment_utils_cpp, q=quantization_utils_cpp,
-                feat=feature_extractor_cpp, cont=contour_utils_cpp)
+def man():
+    return json.load(open(MANIFEST))
+
+
+def check_inputs(rec, **arrays):
+    """The seeded inputs must be the ones the digests were made from (a NumPy generator change would show up here first)."""
+    for k, v in arrays.items():
+        assert sha(v) == rec["in"][k], "input %r is not the one the fixture was made from (numpy version?)" % k
 
 
 def _atan2_inputs(rng, n):
@@ -63,17 +70,22 @@ def _cloud(rng, n):
     return xyz
 
 
-@needs_ref
-@pytest.mark.parametrize("geom", sorted(orc.GEOMS))
-def test_project_matches_reference_cpp(ref, geom):
-    g = orc.LidarGeom(**orc.GEOMS[geom])
+def _project_inputs():
     rng = np.random.default_rng(11)
     xyz = _cloud(rng, 150_000)
     xyz[1000] = 0          # depth-0 point resets its pixel (cpp_modules.cpp:459) -- order dependent
     xyz[5] = [1e-30, 2e-30, 0]
+    return xyz
+
+
+@pytest.mark.parametrize("geom", sorted(orc.GEOMS))
+def test_project_matches_reference_cpp(man, geom):
+    rec = man["project"][geom]
+    g = orc.LidarGeom(**orc.GEOMS[geom])
+    xyz = _project_inputs()
+    check_inputs(rec, xyz=xyz)
     got = orc.project(xyz, g)
-    exp = ref["ds"].point_cloud_to_range_image_even(xyz, g.H, g.W, g.horizontal_FOV, g.vertical_max, g.vertical_min)
-    assert np.array_equal(got.view(np.uint32), exp.view(np.uint32))
+    assert sha(got) == rec["ri"]
 
 
 def _seg_and_ri(rng, h, w, nlab=102, empty_label=None):
@@ -87,56 +99,78 @@ def _seg_and_ri(rng, h, w, nlab=102, empty_label=None):
     return seg, ri
 
 
-@needs_ref
-def test_point_modeling_and_predict_match(ref):
+def _point_modeling_inputs():
     rng = np.random.default_rng(3)
     seg, ri = _seg_and_ri(rng, 64, 2000, empty_label=57)
-    pm_o = orc.point_modeling(ri, seg)
-    pm_r = ref["seg"].point_modeling(ri.reshape(64, 2000, 1), seg)
-    assert np.array_equal(pm_o.view(np.uint32), pm_r.view(np.uint32))
-    assert pm_o.view(np.uint32)[57] == 0xFFC00000          # empty label -> NaN with this bit pattern
     tm = orc.transform_map(orc.LidarGeom(**orc.GEOMS["Velodyne64E"]))
-    mp = np.concatenate((np.zeros((pm_o.shape[0], 3)), pm_o[:, None].astype(np.float64)), -1)
+    return seg, ri, tm
+
+
+def _model_param(pm):
+    """The model rows intra_predict is fed: point_modeling's output plus hand-set rows."""
+    mp = np.concatenate((np.zeros((pm.shape[0], 3)), pm[:, None].astype(np.float64)), -1)
     mp[0] = [0.0072, -0.054, -0.998, -1.76]
     mp[5] = [0.5, -0.5, 0.1, -3.0]
     mp[6] = [0.5, -0.5, 0.0, 7.0]                          # a+b+c == 0 -> constant prediction
+    return mp
+
+
+def test_point_modeling_and_predict_match(man):
+    rec = man["point_modeling"]
+    seg, ri, tm = _point_modeling_inputs()
+    check_inputs(rec, seg=seg, ri=ri)
+    pm_o = orc.point_modeling(ri, seg)
+    assert sha(pm_o) == rec["pm"]
+    assert pm_o.view(np.uint32)[57] == 0xFFC00000          # empty label -> NaN with this bit pattern
+    mp = _model_param(pm_o)
+    check_inputs(rec, mp=mp)
     pr_o = orc.intra_predict(seg, mp, tm)
-    pr_r = ref["seg"].intra_predict(seg, mp, tm)
-    assert np.array_equal(pr_o.view(np.uint32), pr_r.view(np.uint32))
+    assert sha(pr_o) == rec["pred"]
 
 
-@needs_ref
-def test_quantizers_match(ref):
+QUANT_LEVELS = (np.array([30, 10, 3, 0]), np.array([0.04, 0.06, 0.08, 0.10]))
+
+
+def _quantizer_inputs():
     rng = np.random.default_rng(4)
     seg, ri = _seg_and_ri(rng, 32, 2250)
     res = rng.normal(0, 1.0, seg.shape).astype(np.float32)
     res.reshape(-1)[:8] = [0.02, 0.06, -0.02, -0.06, 0.1, -0.1, 0.0, 1000.0]   # half-way cases
-    q_o = orc.uniform_quantize(seg, res, 0.04)
-    q_r = ref["q"].uniform_quantize(seg, res, 0.04)
-    assert np.array_equal(q_o, q_r)
     kp = (rng.random(seg.shape) < 0.01).astype(np.int32) * rng.integers(1, 4, seg.shape).astype(np.int32)
-    lk, la = np.array([30, 10, 3, 0]), np.array([0.04, 0.06, 0.08, 0.10])
+    return seg, res, kp
+
+
+def test_quantizers_match(man):
+    rec = man["quantizers"]
+    seg, res, kp = _quantizer_inputs()
+    check_inputs(rec, seg=seg, res=res, kp=kp)
+    q_o = orc.uniform_quantize(seg, res, 0.04)
+    assert sha(q_o) == rec["q"]
+    lk, la = QUANT_LEVELS
     qn_o, s_o = orc.nonuniform_quantize(seg, res, kp, lk, la, 2)
-    qn_r, s_r = ref["q"].nonuniform_quantize(seg, res, kp, lk, la, 2)
-    assert np.array_equal(qn_o, qn_r) and np.array_equal(s_o, s_r)
+    assert sha(qn_o) == rec["qn"] and sha(s_o) == rec["sal"]
 
 
-@needs_ref
-def test_features_match_on_written_cells(ref):
-    """The reference leaves feat/key_point_map uninitialised where it writes nothing
-    (cpp_modules.cpp:38-43); compare on the cells the oracle writes and require the reference's
-    written key points to be a superset-free match there."""
+def _feature_inputs():
     rng = np.random.default_rng(5)
     seg, ri = _seg_and_ri(rng, 64, 2000)
     ri = (20 + 5 * np.sin(np.arange(2000) / 40.0)[None, :] + rng.normal(0, 0.05, (64, 2000))).astype(np.float32)
     ri[:, ::97] += 3.0                                                   # gaps -> occlusion gate
     ri[seg == 1] = 0
+    return seg, ri
+
+
+def test_features_match_on_written_cells(man):
+    """The reference leaves feat/key_point_map uninitialised where it writes nothing
+    (cpp_modules.cpp:38-43); compare on the cells the oracle writes and require the reference's
+    written key points to be a superset-free match there."""
+    rec = man["features"]
+    seg, ri = _feature_inputs()
+    check_inputs(rec, seg=seg, ri=ri)
     f_o, k_o = orc.extract_features_with_segment(ri, seg)
-    # make the reference's malloc'd outputs land on zeroed pages: large fresh allocations are mmap'd
-    f_r, k_r = ref["feat"].extract_features_with_segment(ri, seg, 3, 8, 4, 8, 6)
     wrote = f_o != 0
-    assert np.array_equal(f_o[wrote].view(np.uint32), f_r[wrote].view(np.uint32))
-    assert np.array_equal(k_o[k_o > 0], k_r[k_o > 0])
+    assert sha(f_o[wrote]) == rec["f_written"]
+    assert sha(k_o[k_o > 0]) == rec["k_written"]
     assert k_o.max() == 3 and (k_o == 1).any() and (k_o == 2).any()
 
 
@@ -146,25 +180,7 @@ FEATURE_PARAM_DRAWS = [(3, 8, 4, 8, 6)] + [tuple(int(v) for v in r) for r in np.
     np.random.default_rng(81).integers(0, 11, 14)], 1)]
 
 
-_FEAT_CHILD = """
-import sys, numpy as np
-sys.path.insert(0, sys.argv[1])
-import feature_extractor_cpp as fe
-z = np.load(sys.argv[2])
-p = [int(v) for v in sys.argv[4:9]]
-f, k = fe.extract_features_with_segment(z['ri'], z['seg'], *p)      # first call of a fresh process
-np.savez(sys.argv[3], f=f, k=k)
-"""
-
-
-@needs_ref
-@pytest.mark.parametrize("params", FEATURE_PARAM_DRAWS)
-def test_features_parameter_sweep_matches(params, tmp_path):
-    """Key-point extraction with non-default feature_region / segments / sharp / less_sharp / flat counts (incl. zeros and
-    less_sharp < sharp): the restatement against the reference's C++.  The reference leaves unwritten cells uninitialised
-    (cpp_modules.cpp:38-43), so it runs once in a fresh process with outputs large enough (288 KB) to be mmap'd zero pages:
-    then the whole key point map can be compared, not only the cells the restatement writes."""
-    import subprocess
+def _feature_sweep_inputs(params):
     fr, segments, sharp, less, flat = params
     rng = np.random.default_rng(1000 + 7 * fr + segments)
     h, w = 48, 1500
@@ -174,25 +190,37 @@ def test_features_parameter_sweep_matches(params, tmp_path):
     ri[3, :] = 17.0                                                      # constant row: zero curvatures, ties
     seg[5, 40:] = 1                                                      # too few valid pixels
     ri[seg == 1] = 0
-    f_o, k_o = orc.extract_features_with_segment(ri, seg, fr, segments, sharp, less, flat)
-    np.savez(tmp_path / "in.npz", ri=ri, seg=seg)
-    subprocess.check_call([sys.executable, "-c", _FEAT_CHILD, REFDIR, str(tmp_path / "in.npz"), str(tmp_path / "out.npz")]
-                          + [str(v) for v in params])
-    z = np.load(tmp_path / "out.npz")
-    f_r, k_r = z["f"], z["k"]
+    return seg, ri
+
+
+@pytest.mark.parametrize("params", FEATURE_PARAM_DRAWS)
+def test_features_parameter_sweep_matches(man, params):
+    """Key-point extraction with non-default feature_region / segments / sharp / less_sharp / flat counts (incl. zeros and
+    less_sharp < sharp): the restatement against the reference's C++.  The reference leaves unwritten cells uninitialised
+    (cpp_modules.cpp:38-43), so the generator ran it once in a fresh process with outputs large enough (288 KB) to be mmap'd
+    zero pages: then the whole key point map can be compared, not only the cells the restatement writes."""
+    rec = man["feature_sweep"][",".join(str(v) for v in params)]
+    seg, ri = _feature_sweep_inputs(params)
+    check_inputs(rec, seg=seg, ri=ri)
+    f_o, k_o = orc.extract_features_with_segment(ri, seg, *params)
     wrote = f_o != 0
-    assert np.array_equal(f_o[wrote].view(np.uint32), f_r[wrote].view(np.uint32)), params
-    assert np.array_equal(k_o, k_r), params
+    assert sha(f_o[wrote]) == rec["f_written"], params
+    assert sha(k_o) == rec["k"], params
 
 
-@needs_ref
-def test_contour_roundtrip_matches(ref):
+def _contour_inputs():
     rng = np.random.default_rng(6)
     seg, _ = _seg_and_ri(rng, 16, 1800)
+    return seg
+
+
+def test_contour_roundtrip_matches(man):
+    rec = man["contour"]
+    seg = _contour_inputs()
+    check_inputs(rec, seg=seg)
     cm_o, sq_o = orc.extract_contour(seg)
-    cm_r, sq_r = ref["cont"].extract_contour(seg)
-    assert np.array_equal(cm_o, cm_r) and np.array_equal(sq_o, sq_r)
-    assert np.array_equal(orc.recover_map(cm_o, sq_o), ref["cont"].recover_map(cm_r, sq_r))
+    assert sha(cm_o) == rec["cm"] and sha(sq_o) == rec["sq"]
+    assert sha(orc.recover_map(cm_o, sq_o)) == rec["recovered"]
     assert np.array_equal(orc.recover_map(cm_o, sq_o), seg)
 
 

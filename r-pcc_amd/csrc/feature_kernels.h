@@ -504,6 +504,22 @@ __global__ __launch_bounds__(256) void salience_levels_kernel(const int32_t *__r
                                                               float *__restrict__ label_acc) {
     salience_levels_body(counts, kpn, M, sp, salience, label_acc, blockIdx.x);
 }
+// the same for any K (uint16 labels): a thread per label
+__global__ __launch_bounds__(256) void wide_salience_levels_kernel(const int32_t *__restrict__ counts, const int32_t *__restrict__ kpn, int K, SalienceParams sp,
+                                                                   uint8_t *__restrict__ salience, float *__restrict__ label_acc) {
+    const int b = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= K) return;
+    const int pn = counts[(int64_t)b * K + k], kn = kpn[(int64_t)b * K + k];
+    int lv = 0;
+    if (k == 0) lv = sp.ground_level;
+    else if (k == 1) lv = sp.levels - 1;
+    else if (pn < 30) lv = sp.levels - 1;
+    else
+        for (int l = 0; l < sp.levels; l++)
+            if (kn >= sp.level_kp_num[l]) { lv = l; break; }
+    salience[(int64_t)b * K + k] = (uint8_t)lv;
+    label_acc[(int64_t)b * K + k] = sp.level_acc[lv];
+}
 struct SalienceGroup {   // one geometry group of rpcc_compress_batch_mixed (the groups may differ in their non-uniform settings)
     const int32_t *counts, *kpn;
     SalienceParams sp;

@@ -5,6 +5,7 @@
 // and the roofline of every kernel: DESIGN.md.  Reference citations are relative to the reference
 // repository root.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1913,6 +1914,15 @@ __global__ __launch_bounds__(256) void ground_mask_kernel(float *__restrict__ ri
 
 // tiletab: dev float4 [B][3][T] (T = tiles of fps_tiling_range(H,W)) or NULL
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+// What the label type decides on the host: the cluster limit of the tuned label kernels and the alignment of a 4-pixel load of seg (the VEC variants).
+template <class L>
+struct LabelTraits {
+    static_assert(std::is_same<L, uint8_t>::value || std::is_same<L, uint16_t>::value, "labels are uint8_t or uint16_t");
+    static constexpr int max_clusters = sizeof(L) == 1 ? RPCC_MAX_CLUSTERS : RPCC_MAX_CLUSTERS_MID;
+    static constexpr uintptr_t seg4_align = 4 * sizeof(L);
+};
+template <class L>
+static inline bool seg4_aligned(const L *seg) { return ((uintptr_t)seg & (LabelTraits<L>::seg4_align - 1)) == 0; }
 static int launch_ground_mask(float *ri, const float *tm, const double *ground, double thr, int B, int H, int W,
                               float *temp, int32_t *info, float *tiletab, hipStream_t st, bool raw,
                               bool info_ready = false) {
@@ -2665,19 +2675,36 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES) ASSIGN_VGPR_ATTR void assign_ker
     }
 }
 
+// uint16 labels: 8 screening rounds of 64 centres up to 510 clusters, 16 above
+template <class L>
 static int launch_assign(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H,
-                         int W, int M, uint8_t *seg, hipStream_t st, const float *temp = nullptr) {
+                         int W, int M, L *seg, hipStream_t st, const float *temp = nullptr) {
     const int ntile = ((H + ASSIGN_ROWS - 1) / ASSIGN_ROWS) * ((W + 31) / 32);
     const dim3 grid((ntile + ASSIGN_WAVES * ASSIGN_TILES_PER_WAVE - 1) / (ASSIGN_WAVES * ASSIGN_TILES_PER_WAVE), B);
-    assign_kernel<uint8_t, 4><<<grid, 64 * ASSIGN_WAVES, (size_t)M * sizeof(float4), st>>>(ri, tm, ground, centers, H, W, M, seg, temp);
+    const size_t sh = (size_t)M * sizeof(float4);
+    if constexpr (sizeof(L) == 1) assign_kernel<L, 4><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp);
+    else if (M <= 510)            assign_kernel<L, 8><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp);
+    else                          assign_kernel<L, 16><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp);
     LAUNCH_CHECK();
     return RPCC_OK;
 }
 
-extern "C" int rpcc_assign(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H,
-                           int W, int M, uint8_t *seg, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS && ri && tm && ground && centers && seg);
+// The stage entries are one body for both label types: byte labels up to RPCC_MAX_CLUSTERS, the `_wide` twins on uint16 labels up to
+// RPCC_MAX_CLUSTERS_MID (the reference-side classes call the stages one by one: PointCloudSegment.segment / cluster_modeling / intra_predict,
+// QuantizationModule.quantize_residual with the uniform framework).
+template <class L>
+static int assign_entry(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H, int W, int M, L *seg,
+                        void *stream) {
+    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && M > 0 && M <= LabelTraits<L>::max_clusters && ri && tm && ground && centers && seg);
     return launch_assign(ri, tm, ground, centers, B, H, W, M, seg, (hipStream_t)stream);
+}
+extern "C" int rpcc_assign(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H, int W, int M, uint8_t *seg,
+                           void *stream) {
+    return assign_entry(ri, tm, ground, centers, B, H, W, M, seg, stream);
+}
+extern "C" int rpcc_assign_wide(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H, int W, int M, uint16_t *seg,
+                                void *stream) {
+    return assign_entry(ri, tm, ground, centers, B, H, W, M, seg, stream);
 }
 
 // ================================================================================================
@@ -2865,6 +2892,64 @@ __global__ __launch_bounds__(SCAN_THREADS) void model_scan_multi_kernel(const Mu
     const ScanArgs &A = multi_locate(m, b, t);
     model_scan_body(A, b);
 }
+// The scan on uint16 labels (up to RPCC_MAX_CLUSTERS_MID clusters): a thread per label (K <= 1024) -- label totals, their exclusive prefix
+// without label 1, the tiles' offsets, counts, nnz and the point model's rows (cpp_modules.cpp:471-518).
+#define SCANW_THREADS 1024
+template <class L>
+__global__ __launch_bounds__(SCANW_THREADS) void model_scan_wide_kernel(const float *__restrict__ ri, const L *__restrict__ seg, const double *__restrict__ ground,
+                                                                        int P, int M, int KP, int T, const int64_t *__restrict__ sums,
+                                                                        const int32_t *__restrict__ flags, uint32_t *__restrict__ hist,
+                                                                        float *__restrict__ model, int32_t *__restrict__ counts, int32_t *__restrict__ nnz) {
+    __shared__ uint32_t wsum[SCANW_THREADS / 64];
+    const int b = blockIdx.x, k = threadIdx.x, K = M + 2, lane = k & 63, wave = k >> 6;
+    uint32_t *gh = hist + (int64_t)b * T * KP;
+    const uint32_t kp4 = (uint32_t)KP * 4u, k4 = (uint32_t)min(k, KP - 1) * 4u;
+    uint32_t total = 0u;
+    for (int t0 = 0; t0 < T; t0 += SCAN_U) {
+        uint32_t d[SCAN_U];
+#pragma unroll
+        for (int j = 0; j < SCAN_U; j++) d[j] = ld_at(gh, (uint32_t)min(t0 + j, T - 1) * kp4 + k4);   // unconditional (clamped) loads
+#pragma unroll
+        for (int j = 0; j < SCAN_U; j++) total += (t0 + j < T && k < K) ? d[j] : 0u;
+    }
+    const uint32_t v = (k < K && k != 1) ? total : 0u;   // label 1 = empty pixels: no residuals (cpp_modules.cpp:314)
+    const uint32_t incl = dpp_scan_incl_u32(v);
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t off = 0u;
+    for (int w = 0; w < wave; w++) off += wsum[w];
+    if (k == SCANW_THREADS - 1 && nnz) nnz[b] = (int32_t)(off + incl);
+    if (k >= K) return;
+    uint32_t run = off + incl - v;
+    for (int t0 = 0; t0 < T; t0 += SCAN_U) {
+        uint32_t d[SCAN_U];
+#pragma unroll
+        for (int j = 0; j < SCAN_U; j++) d[j] = ld_at(gh, (uint32_t)min(t0 + j, T - 1) * kp4 + k4);
+#pragma unroll
+        for (int j = 0; j < SCAN_U; j++)
+            if (t0 + j < T) { st_at(gh, (uint32_t)(t0 + j) * kp4 + k4, run); run += d[j]; }
+    }
+    if (counts) counts[(int64_t)b * K + k] = (int32_t)total;
+    if (model != nullptr) {
+        float *row = model + ((int64_t)b * K + k) * 4;
+        if (k == 0) {
+            row[0] = (float)ground[4 * b]; row[1] = (float)ground[4 * b + 1]; row[2] = (float)ground[4 * b + 2]; row[3] = (float)ground[4 * b + 3];
+        } else if (k == 1) {
+            row[0] = row[1] = row[2] = row[3] = 0.0f;
+        } else {
+            double sm;
+            if (flags[4 * b]) {   // sequential double accumulation in row-major order (cpp_modules.cpp:514): ranges outside the fixed-point window, rare
+                sm = 0.0;
+                for (int p = 0; p < P; p++)
+                    if (seg[(int64_t)b * P + p] == (L)k) sm += (double)ri[(int64_t)b * P + p];
+            } else {
+                sm = (double)sums[(int64_t)b * KP + k] * (1.0 / 268435456.0);
+            }
+            row[0] = row[1] = row[2] = 0.0f;
+            row[3] = total == 0 ? u2f(0xFFC00000u) : (float)(sm / (double)total);
+        }
+    }
+}
 // A lane owns FOUR CONSECUTIVE pixels of the tile (VEC: one 4-byte load of labels, one 16-byte load of ranges), a wavefront
 // 256 consecutive pixels.  Labels are spatially coherent, so the pixels that carry the label of the wavefront's first pixel
 // -- usually most of the 256 -- are aggregated once per wavefront (four compare masks counted in scalar registers, two DPP
@@ -2999,34 +3084,48 @@ __global__ __launch_bounds__(256) void model_hist_multi_kernel(const MultiArgs<H
 static inline int scan_kp2(int M) { int v = 1; while (v < M + 2) v <<= 1; return v; }   // labels rounded up to a power of two (<= 256)
 // histogram + scan: tile x label counts (and the labels' range sums when ri is given), then the offsets of the ordered scatter, counts, nnz and
 // -- with `model` -- the point model's rows.  The sums / flags block must be zero (memset or BatchInit).
-static int launch_hist_scan(const float *ri, const uint8_t *seg, const double *ground, int B, int P, int M, const WsLayout &L, float *model,
+template <class L>
+static int launch_hist_scan(const float *ri, const L *seg, const double *ground, int B, int P, int M, const WsLayout &lay, float *model,
                             int32_t *counts, int32_t *nnz, hipStream_t st) {
     const int KP = kpad(M), T = ntiles(P);
-    const bool vec = (P & 3) == 0 && ((uintptr_t)seg & 3u) == 0 && (ri == nullptr || ((uintptr_t)ri & 15u) == 0);
-    const ScanArgs sa = {ri, seg, ground, P, M, KP, T, scan_kp2(M), L.sums, L.flags, L.hist, model, counts, nnz};
+    const bool vec = (P & 3) == 0 && seg4_aligned(seg) && (ri == nullptr || aligned16(ri));
     // (The scan as the tail of the histogram kernel -- the frame's last workgroup to finish runs it -- was measured in round 4: a workgroup must
     // release its rows device-wide before it draws its ticket, and an agent-scope fence writes the XCD's L2 back: 62 us -> 2.9 ms.)
-    if (vec) model_hist_kernel<true><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri, seg, P, KP, T, L.sums, L.flags, L.hist);
-    else     model_hist_kernel<false><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri, seg, P, KP, T, L.sums, L.flags, L.hist);
+    if (vec) model_hist_kernel<true, L><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
+    else     model_hist_kernel<false, L><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
     LAUNCH_CHECK();
-    model_scan_kernel<<<B, SCAN_THREADS, 0, st>>>(sa);
+    if constexpr (sizeof(L) == 1) {
+        const ScanArgs sa = {ri, seg, ground, P, M, KP, T, scan_kp2(M), lay.sums, lay.flags, lay.hist, model, counts, nnz};
+        model_scan_kernel<<<B, SCAN_THREADS, 0, st>>>(sa);
+    } else {
+        model_scan_wide_kernel<L><<<B, SCANW_THREADS, 0, st>>>(ri, seg, ground, P, M, KP, T, lay.sums, lay.flags, lay.hist, model, counts, nnz);
+    }
     LAUNCH_CHECK();
     return RPCC_OK;
 }
 
 // One workgroup per frame: label totals, tile offsets, label bases, means, model rows.
-static int launch_point_model(const float *ri, const uint8_t *seg, const double *ground, int B, int P, int M,
+template <class L>
+static int launch_point_model(const float *ri, const L *seg, const double *ground, int B, int P, int M,
                               float *model, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared = false) {
-    const int KP = kpad(M), T = ntiles(P);
-    WsLayout L = ws_layout(ws, B, P, M);
-    if (!cleared) HIP_TRY(hipMemsetAsync(L.sums, 0, (size_t)((char *)L.hist - (char *)L.sums), st));
-    return launch_hist_scan(ri, seg, ground, B, P, M, L, model, counts, nnz, st);
+    const WsLayout lay = ws_layout(ws, B, P, M);
+    if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
+    return launch_hist_scan(ri, seg, ground, B, P, M, lay, model, counts, nnz, st);
 }
 
-extern "C" int rpcc_point_model(const float *ri, const uint8_t *seg, const double *ground, int B, int P, int M,
-                                float *model, int32_t *counts, void *ws, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS && ri && seg && ground && model && ws);
+template <class L>
+static int point_model_entry(const float *ri, const L *seg, const double *ground, int B, int P, int M, float *model, int32_t *counts,
+                             void *ws, void *stream) {
+    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= LabelTraits<L>::max_clusters && ri && seg && ground && model && ws);
     return launch_point_model(ri, seg, ground, B, P, M, model, counts, nullptr, ws, (hipStream_t)stream);
+}
+extern "C" int rpcc_point_model(const float *ri, const uint8_t *seg, const double *ground, int B, int P, int M, float *model, int32_t *counts, void *ws,
+                                void *stream) {
+    return point_model_entry(ri, seg, ground, B, P, M, model, counts, ws, stream);
+}
+extern "C" int rpcc_point_model_wide(const float *ri, const uint16_t *seg, const double *ground, int B, int P, int M, float *model, int32_t *counts, void *ws,
+                                     void *stream) {
+    return point_model_entry(ri, seg, ground, B, P, M, model, counts, ws, stream);
 }
 
 // ================================================================================================
@@ -3241,16 +3340,17 @@ __global__ __launch_bounds__(256) void predict_quantize_multi_kernel(const Multi
     else       predict_quantize_body<false, false>(a.ri, a.tm, a.seg, a.model, a.hist, acc, a.label_acc, nullptr, a.P, M, KP, a.T, a.q16, nullptr, nullptr, a.epoch_inc, b, t);
 }
 
-static int launch_predict_quantize(const float *ri, const float *tm, const uint8_t *seg, const float *model, float acc,
+template <class L>
+static int launch_predict_quantize(const float *ri, const float *tm, const L *seg, const float *model, float acc,
                                    const float *label_acc, const float *residual_in, int B, int P, int M, int16_t *q16,
                                    int32_t *q32, float *pred, void *ws, hipStream_t st, int32_t *epoch_inc = nullptr) {
     const int KP = kpad(M), T = ntiles(P);
-    WsLayout L = ws_layout(ws, B, P, M);
+    const WsLayout lay = ws_layout(ws, B, P, M);
     const size_t sh = (size_t)KP * 16 + (size_t)4 * KP * 4 + (size_t)KP * 4 + (size_t)KP * 4;
     const bool resid = residual_in && !pred;
-    const bool vec = (P & 3) == 0 && ((uintptr_t)seg & 3u) == 0 && (resid || (aligned16(ri) && aligned16(tm))) &&
+    const bool vec = (P & 3) == 0 && seg4_aligned(seg) && (resid || (aligned16(ri) && aligned16(tm))) &&
                      (!residual_in || aligned16(residual_in));
-#define PQ_LAUNCH(R_, V_) predict_quantize_kernel<R_, V_><<<dim3(T, B), 256, sh, st>>>(ri, tm, seg, model, L.hist, acc, label_acc, residual_in, P, M, KP, T, q16, q32, pred, epoch_inc)
+#define PQ_LAUNCH(R_, V_) predict_quantize_kernel<R_, V_, L><<<dim3(T, B), 256, sh, st>>>(ri, tm, seg, model, lay.hist, acc, label_acc, residual_in, P, M, KP, T, q16, q32, pred, epoch_inc)
     if (resid) { if (vec) PQ_LAUNCH(true, true); else PQ_LAUNCH(true, false); }
     else       { if (vec) PQ_LAUNCH(false, true); else PQ_LAUNCH(false, false); }
 #undef PQ_LAUNCH
@@ -3258,21 +3358,28 @@ static int launch_predict_quantize(const float *ri, const float *tm, const uint8
     return RPCC_OK;
 }
 
-extern "C" int rpcc_predict_quantize(const float *ri, const float *tm, const uint8_t *seg, const float *model,
-                                     const float *label_acc, const float *residual_in, float acc, int B, int P, int M,
-                                     int16_t *q16, int32_t *q32, int32_t *nnz, float *pred, void *ws, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS && seg && ws);
+template <class L>
+static int predict_quantize_entry(const float *ri, const float *tm, const L *seg, const float *model, const float *label_acc,
+                                  const float *residual_in, float acc, int B, int P, int M, int16_t *q16, int32_t *q32, int32_t *nnz,
+                                  float *pred, void *ws, void *stream) {
+    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= LabelTraits<L>::max_clusters && seg && ws);
     ARG_TRY((residual_in && !pred) || (ri && tm && model));   // residual handed in, no prediction wanted: seg only
     ARG_TRY(q16 || q32);
     hipStream_t st = (hipStream_t)stream;
     // Self-contained entry: the tile offsets are rebuilt from this segmentation (histogram + scan with
     // no model output); the model rows are the caller's (point or plane models).
-    const int KP = kpad(M), T = ntiles(P);
-    WsLayout L = ws_layout(ws, B, P, M);
-    HIP_TRY(hipMemsetAsync(L.sums, 0, (size_t)((char *)L.hist - (char *)L.sums), st));
     int rc;
-    if ((rc = launch_hist_scan(ri, seg, nullptr, B, P, M, L, nullptr, nullptr, nnz, st))) return rc;
+    if ((rc = launch_point_model(ri, seg, nullptr, B, P, M, nullptr, nullptr, nnz, ws, st))) return rc;
     return launch_predict_quantize(ri, tm, seg, model, acc, label_acc, residual_in, B, P, M, q16, q32, pred, ws, st);
+}
+extern "C" int rpcc_predict_quantize(const float *ri, const float *tm, const uint8_t *seg, const float *model, const float *label_acc, const float *residual_in,
+                                     float acc, int B, int P, int M, int16_t *q16, int32_t *q32, int32_t *nnz, float *pred, void *ws, void *stream) {
+    return predict_quantize_entry(ri, tm, seg, model, label_acc, residual_in, acc, B, P, M, q16, q32, nnz, pred, ws, stream);
+}
+extern "C" int rpcc_predict_quantize_wide(const float *ri, const float *tm, const uint16_t *seg, const float *model, const float *label_acc,
+                                          const float *residual_in, float acc, int B, int P, int M, int16_t *q16, int32_t *q32, int32_t *nnz, float *pred,
+                                          void *ws, void *stream) {
+    return predict_quantize_entry(ri, tm, seg, model, label_acc, residual_in, acc, B, P, M, q16, q32, nnz, pred, ws, stream);
 }
 
 // ================================================================================================
@@ -3387,34 +3494,72 @@ static int launch_features(const float *ri, const L *seg, int B, int H, int W, i
     LAUNCH_CHECK();
     return RPCC_OK;
 }
-extern "C" int rpcc_extract_features(const float *ri, const uint8_t *seg, int B, int H, int W, int feature_region,
-                                     int segments, int sharp_num, int less_sharp_num, int flat_num, float *feat,
-                                     uint8_t *key_point_map, void *stream) {
+template <class L>
+static int extract_features_entry(const float *ri, const L *seg, int B, int H, int W, int feature_region, int segments, int sharp_num,
+                                  int less_sharp_num, int flat_num, float *feat, uint8_t *key_point_map, void *stream) {
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && ri && seg && feat && key_point_map);
-    return launch_features(ri, seg, B, H, W, feature_region, segments, sharp_num, less_sharp_num, flat_num, feat,
-                           key_point_map, (hipStream_t)stream);
+    return launch_features(ri, seg, B, H, W, feature_region, segments, sharp_num, less_sharp_num, flat_num, feat, key_point_map, (hipStream_t)stream);
+}
+extern "C" int rpcc_extract_features(const float *ri, const uint8_t *seg, int B, int H, int W, int feature_region, int segments, int sharp_num,
+                                     int less_sharp_num, int flat_num, float *feat, uint8_t *key_point_map, void *stream) {
+    return extract_features_entry(ri, seg, B, H, W, feature_region, segments, sharp_num, less_sharp_num, flat_num, feat, key_point_map, stream);
+}
+extern "C" int rpcc_extract_features_wide(const float *ri, const uint16_t *seg, int B, int H, int W, int feature_region, int segments, int sharp_num,
+                                          int less_sharp_num, int flat_num, float *feat, uint8_t *key_point_map, void *stream) {
+    return extract_features_entry(ri, seg, B, H, W, feature_region, segments, sharp_num, less_sharp_num, flat_num, feat, key_point_map, stream);
 }
 
-extern "C" int rpcc_salience(const uint8_t *seg, const uint8_t *key_point_map, const int32_t *level_kp_num,
-                             const float *level_acc, int levels, int ground_level, int B, int P, int M,
-                             uint8_t *salience, float *label_acc, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS && seg && key_point_map && salience && label_acc);
-    ARG_TRY(level_kp_num && level_acc && levels >= 1 && levels <= 8 && ground_level >= 0 && ground_level < levels);
+static SalienceParams salience_params(int levels, const int32_t *kp_num, const float *acc, int ground_level) {
     SalienceParams sp;
-    for (int i = 0; i < 8; i++) { sp.level_kp_num[i] = i < levels ? level_kp_num[i] : 0; sp.level_acc[i] = i < levels ? level_acc[i] : 0.f; }
+    for (int i = 0; i < 8; i++) { sp.level_kp_num[i] = i < levels ? kp_num[i] : 0; sp.level_acc[i] = i < levels ? acc[i] : 0.f; }
     sp.levels = levels;
     sp.ground_level = ground_level;
-    salience_kernel<uint8_t, 256><<<B, SAL_THREADS, 0, (hipStream_t)stream>>>(seg, key_point_map, P, M, sp, salience, label_acc);
+    return sp;
+}
+// salience level and quantisation step per label from the per-label pixel and key-point totals
+template <class L>
+static int launch_salience_levels(const int32_t *counts, const int32_t *kpn, int B, int M, const SalienceParams &sp, uint8_t *salience,
+                                  float *label_acc, hipStream_t st) {
+    if constexpr (sizeof(L) == 1) salience_levels_kernel<<<B, 256, 0, st>>>(counts, kpn, M, sp, salience, label_acc);
+    else                          wide_salience_levels_kernel<<<dim3((M + 2 + 255) / 256, B), 256, 0, st>>>(counts, kpn, M + 2, sp, salience, label_acc);
     LAUNCH_CHECK();
     return RPCC_OK;
 }
-
-extern "C" int rpcc_intra_predict(const uint8_t *seg, const float *model, const float *tm, int B, int P, int M, float *pred,
-                                  void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && seg && model && tm && pred);
-    intra_predict_kernel<uint8_t><<<dim3((P + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(seg, model, tm, P, M + 2, pred);
+// the same from a segmentation and a key-point map
+template <class L>
+static int salience_entry(const L *seg, const uint8_t *key_point_map, const int32_t *level_kp_num, const float *level_acc, int levels,
+                          int ground_level, int B, int P, int M, uint8_t *salience, float *label_acc, void *stream) {
+    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= LabelTraits<L>::max_clusters && seg && key_point_map && salience && label_acc);
+    ARG_TRY(level_kp_num && level_acc && levels >= 1 && levels <= 8 && ground_level >= 0 && ground_level < levels);
+    const SalienceParams sp = salience_params(levels, level_kp_num, level_acc, ground_level);
+    hipStream_t st = (hipStream_t)stream;
+    if constexpr (sizeof(L) == 1) salience_kernel<L, 256><<<B, SAL_THREADS, 0, st>>>(seg, key_point_map, P, M, sp, salience, label_acc);
+    else                          salience_kernel<L, 1024><<<B, SAL_THREADS, 0, st>>>(seg, key_point_map, P, M, sp, salience, label_acc);
     LAUNCH_CHECK();
     return RPCC_OK;
+}
+extern "C" int rpcc_salience(const uint8_t *seg, const uint8_t *key_point_map, const int32_t *level_kp_num, const float *level_acc, int levels,
+                             int ground_level, int B, int P, int M, uint8_t *salience, float *label_acc, void *stream) {
+    return salience_entry(seg, key_point_map, level_kp_num, level_acc, levels, ground_level, B, P, M, salience, label_acc, stream);
+}
+extern "C" int rpcc_salience_wide(const uint16_t *seg, const uint8_t *key_point_map, const int32_t *level_kp_num, const float *level_acc, int levels,
+                                  int ground_level, int B, int P, int M, uint8_t *salience, float *label_acc, void *stream) {
+    return salience_entry(seg, key_point_map, level_kp_num, level_acc, levels, ground_level, B, P, M, salience, label_acc, stream);
+}
+
+// max_m: the byte entry has no upper limit, the uint16 one takes any RPCC_MAX_CLUSTERS_WIDE
+template <class L>
+static int intra_predict_entry(const L *seg, const float *model, const float *tm, int B, int P, int M, int max_m, float *pred, void *stream) {
+    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= max_m && seg && model && tm && pred);
+    intra_predict_kernel<L><<<dim3((P + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(seg, model, tm, P, M + 2, pred);
+    LAUNCH_CHECK();
+    return RPCC_OK;
+}
+extern "C" int rpcc_intra_predict(const uint8_t *seg, const float *model, const float *tm, int B, int P, int M, float *pred, void *stream) {
+    return intra_predict_entry(seg, model, tm, B, P, M, INT_MAX, pred, stream);
+}
+extern "C" int rpcc_intra_predict_wide(const uint16_t *seg, const float *model, const float *tm, int B, int P, int M, float *pred, void *stream) {
+    return intra_predict_entry(seg, model, tm, B, P, M, RPCC_MAX_CLUSTERS_WIDE, pred, stream);
 }
 
 // ================================================================================================
@@ -3429,25 +3574,26 @@ extern "C" size_t rpcc_plane_workspace_bytes(int B, int P, int M) {
 }
 
 // hist / scan for a segmentation without the point sums: tile offsets (ordered scatter), counts, nnz
-static int launch_label_scan(const uint8_t *seg, int B, int P, int M, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st,
-                             bool cleared) {
-    const int KP = kpad(M), T = ntiles(P);
-    WsLayout L = ws_layout(ws, B, P, M);
-    if (!cleared) HIP_TRY(hipMemsetAsync(L.sums, 0, (size_t)((char *)L.hist - (char *)L.sums), st));
-    return launch_hist_scan(nullptr, seg, nullptr, B, P, M, L, nullptr, counts, nnz, st);
+template <class L>
+static int launch_label_scan(const L *seg, int B, int P, int M, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared) {
+    const WsLayout lay = ws_layout(ws, B, P, M);
+    if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
+    return launch_hist_scan(nullptr, seg, nullptr, B, P, M, lay, nullptr, counts, nnz, st);
 }
 // plane rows from a segmentation whose tile offsets (launch_label_scan) are in ws; extra = order | pts4 scratch.  Two launches: the
 // label-ordered lists, then the fits.
 static inline float4 *plane_pts4(void *extra, int B, int P) {
     return reinterpret_cast<float4 *>(reinterpret_cast<char *>(extra) + (((size_t)B * P * 4 + 255) & ~(size_t)255));
 }
-static int launch_label_order(const float *ri, const float *tm, const uint8_t *seg, int B, int P, int M, void *ws, void *extra, hipStream_t st) {
+template <class L>
+static int launch_label_order(const float *ri, const float *tm, const L *seg, int B, int P, int M, void *ws, void *extra, hipStream_t st) {
     const int KP = kpad(M), T = ntiles(P);
-    WsLayout L = ws_layout(ws, B, P, M);
+    const WsLayout lay = ws_layout(ws, B, P, M);
+    const size_t sh = (size_t)16 * (KP + 1) * 4 + (size_t)KP * 4;
     // (the quantiser's round-3 layout -- four consecutive pixels per lane -- was tried here as well: 121 us against 97 us, because a
     // lane's four 16-byte point stores then lie 64 bytes apart from the next lane's; this kernel is bound by its 255 MB of stores)
-    label_order_kernel<uint8_t><<<dim3(T, B), 256, (size_t)16 * (KP + 1) * 4 + (size_t)KP * 4, st>>>(seg, L.hist, P, M, KP, T, reinterpret_cast<uint32_t *>(extra), ri, tm,
-                                                                                                     plane_pts4(extra, B, P));
+    if constexpr (sizeof(L) == 2) HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&label_order_kernel<L>), (int)sh));   // above 64 KB
+    label_order_kernel<L><<<dim3(T, B), 256, sh, st>>>(seg, lay.hist, P, M, KP, T, reinterpret_cast<uint32_t *>(extra), ri, tm, plane_pts4(extra, B, P));
     LAUNCH_CHECK();
     return RPCC_OK;
 }
@@ -3473,16 +3619,27 @@ static int launch_plane_fits(const float *tm, const double *ground, int B, int P
     return RPCC_OK;
 }
 
-extern "C" int rpcc_plane_model(const float *ri, const float *tm, const uint8_t *seg, const double *ground, int B, int P,
-                                int M, double cos_cut, uint32_t seed, const int64_t *frame_ids, const double *inject_planes,
-                                float *model, int32_t *counts, void *ws, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS && ri && tm && seg && model && counts && ws);
+// (uint16 labels: ws of rpcc_plane_workspace_bytes(B, P, M) bytes as well)
+template <class L>
+static int plane_model_entry(const float *ri, const float *tm, const L *seg, const double *ground, int B, int P, int M, double cos_cut,
+                             uint32_t seed, const int64_t *frame_ids, const double *inject_planes, float *model, int32_t *counts, void *ws,
+                             void *stream) {
+    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= LabelTraits<L>::max_clusters && ri && tm && seg && model && counts && ws);
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = launch_label_scan(seg, B, P, M, counts, nullptr, ws, st, false))) return rc;
     void *extra = reinterpret_cast<char *>(ws) + ws_layout(nullptr, B, P, M).bytes + 256;
     if ((rc = launch_label_order(ri, tm, seg, B, P, M, ws, extra, st))) return rc;
     return launch_plane_fits(tm, ground, B, P, M, cos_cut, seed, frame_ids, model, counts, ws, extra, st, inject_planes);
+}
+extern "C" int rpcc_plane_model(const float *ri, const float *tm, const uint8_t *seg, const double *ground, int B, int P, int M, double cos_cut, uint32_t seed,
+                                const int64_t *frame_ids, const double *inject_planes, float *model, int32_t *counts, void *ws, void *stream) {
+    return plane_model_entry(ri, tm, seg, ground, B, P, M, cos_cut, seed, frame_ids, inject_planes, model, counts, ws, stream);
+}
+extern "C" int rpcc_plane_model_wide(const float *ri, const float *tm, const uint16_t *seg, const double *ground, int B, int P, int M, double cos_cut,
+                                     uint32_t seed, const int64_t *frame_ids, const double *inject_planes, float *model, int32_t *counts, void *ws,
+                                     void *stream) {
+    return plane_model_entry(ri, tm, seg, ground, B, P, M, cos_cut, seed, frame_ids, inject_planes, model, counts, ws, stream);
 }
 
 // ================================================================================================
@@ -3506,8 +3663,7 @@ struct BatchPlan {
     int32_t *zcnt, *epoch, *kpn;
     BatchInit bi;
 };
-static BatchPlan plan_batch(const rpcc_batch_io *io, int Bs, int64_t npts, rpcc_geom g, int M, double ground_threshold, float acc, char *ws) {
-    BatchPlan p;
+static int plan_batch(BatchPlan &p, const rpcc_batch_io *io, int Bs, int64_t npts, rpcc_geom g, int M, double ground_threshold, float acc, char *ws) {
     p.io = io; p.Bs = Bs; p.M = M; p.P = g.H * g.W; p.npts = npts; p.g = g; p.ground_threshold = ground_threshold; p.acc = acc; p.ws = ws;
     const int P = p.P;
     p.fit_ground = io->ground_seed >= 0;  // >= 0: fit the ground plane here (seed + frame identity)
@@ -3525,22 +3681,27 @@ static BatchPlan plan_batch(const rpcc_batch_io *io, int Bs, int64_t npts, rpcc_
     p.bi.tm = io->tm; p.bi.soa = p.rays_soa; p.bi.P = P; p.bi.info = io->info; p.bi.B = Bs; p.bi.on = 1;
     p.bi.z0 = {reinterpret_cast<uint32_t *>(p.zcnt), p.zcnt ? (int)rs_count_words(Bs) : 0};
     p.bi.z1 = {reinterpret_cast<uint32_t *>(p.L.sums), (int)(((char *)p.L.hist - (char *)p.L.sums) / 4)};
+    const size_t tab_bytes = (size_t)Bs * FPS_TAB_ROWS * ((P + 31) / 32 + 4096) * 4;
+    // the ground fit's hand-off lies in the tile table's bytes: count words | z-mask bytes | the deferred whole-cloud fits (their end: slot Bs)
+    if (p.zcnt) ARG_TRY(reinterpret_cast<char *>(wc_slot_of(rs_wc_of(p.zcnt, Bs, P), Bs, Bs).cnt) <= reinterpret_cast<char *>(p.tiletab) + tab_bytes);
     // model rows + the tile offsets of the ordered scatter (built once, used by the plane list and by the quantiser)
-    p.extra = reinterpret_cast<char *>(p.tiletab) + (((size_t)Bs * FPS_TAB_ROWS * ((P + 31) / 32 + 4096) * 4 + 255) & ~(size_t)255) + 256;
+    p.extra = reinterpret_cast<char *>(p.tiletab) + ((tab_bytes + 255) & ~(size_t)255) + 256;
     const size_t ksz = (((size_t)Bs * (M + 2) * 4 + 255) & ~(size_t)255);
     p.label_acc = io->nonuniform ? reinterpret_cast<float *>(p.extra + plane_extra_bytes(Bs, P, M) - 256 - ksz) : nullptr;
     p.kpn = io->nonuniform ? reinterpret_cast<int32_t *>(p.extra + plane_extra_bytes(Bs, P, M) - 256 - 2 * ksz) : nullptr;
     p.bi.z2 = {reinterpret_cast<uint32_t *>(p.kpn), p.kpn ? Bs * (M + 2) : 0};  // key points per label
     p.brute = (io->flags & (RPCC_FPS_BRUTEFORCE | RPCC_FPS_MODE_BITS)) != 0;   // a mode flag selects the reference kernel too
     p.tiled = !p.brute && fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES;
-    return p;
+    return RPCC_OK;
 }
 // The launches of a batch in order, as stages: the three marked (*) are the kernels with one workgroup per frame or per label, which
 // rpcc_compress_batch_mixed runs as one launch over all groups (the others it runs group after group).
 enum { ST_PROJECT, ST_GROUND /* (*) */, ST_MASK, ST_FPS /* (*) */, ST_ASSIGN_LABELS, ST_PLANES /* (*) */, ST_QUANTISE, ST_COUNT };
+template <class L>
 static int run_stage(const BatchPlan &p, int stage, hipStream_t st) {
     const rpcc_batch_io *io = p.io;
     const int Bs = p.Bs, M = p.M, P = p.P;
+    L *seg = reinterpret_cast<L *>(io->seg);
     int rc;
     switch (stage) {
     case ST_PROJECT:
@@ -3557,11 +3718,11 @@ static int run_stage(const BatchPlan &p, int stage, hipStream_t st) {
                                 p.tiled ? p.tiletab : nullptr, io->timer, st, FPS_SOA ? p.rays_soa : nullptr);
     case ST_ASSIGN_LABELS:
         // (the FPS state is the un-fused minimum the assignment's bound needs; a CUDA-binary mode contracts it)
-        if ((rc = launch_assign(io->ri, io->tm, io->ground, io->centers, Bs, p.g.H, p.g.W, M, io->seg, st,
+        if ((rc = launch_assign(io->ri, io->tm, io->ground, io->centers, Bs, p.g.H, p.g.W, M, seg, st,
                                 (io->flags & RPCC_FPS_MODE_BITS) ? nullptr : p.temp))) return rc;
-        if (io->model_method == 0) return launch_point_model(io->ri, io->seg, io->ground, Bs, P, M, io->model, io->counts, io->nnz, p.ws, st, true);
-        if ((rc = launch_label_scan(io->seg, Bs, P, M, io->counts, io->nnz, p.ws, st, true))) return rc;
-        return launch_label_order(io->ri, io->tm, io->seg, Bs, P, M, p.ws, p.extra, st);
+        if (io->model_method == 0) return launch_point_model(io->ri, seg, io->ground, Bs, P, M, io->model, io->counts, io->nnz, p.ws, st, true);
+        if ((rc = launch_label_scan(seg, Bs, P, M, io->counts, io->nnz, p.ws, st, true))) return rc;
+        return launch_label_order(io->ri, io->tm, seg, Bs, P, M, p.ws, p.extra, st);
     case ST_PLANES:
         if (io->model_method == 0) return RPCC_OK;
         return launch_plane_fits(io->tm, io->ground, Bs, P, M, io->plane_cos_cut, (uint32_t)io->plane_seed, io->frame_ids, io->model,
@@ -3569,30 +3730,32 @@ static int run_stage(const BatchPlan &p, int stage, hipStream_t st) {
     case ST_QUANTISE:
         if (io->nonuniform) {   // key points -> salience level and quantisation step per label
             const rpcc_nonuniform_cfg *nu = io->nonuniform;
-            if ((rc = launch_features(io->ri, io->seg, Bs, p.g.H, p.g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num,
+            if ((rc = launch_features(io->ri, seg, Bs, p.g.H, p.g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num,
                                       nu->flat_num, nullptr, io->key_point_map, st, p.kpn, M + 2)))
                 return rc;
-            SalienceParams sp;
-            for (int i = 0; i < 8; i++) { sp.level_kp_num[i] = i < nu->levels ? nu->level_kp_num[i] : 0; sp.level_acc[i] = i < nu->levels ? nu->level_acc[i] : 0.f; }
-            sp.levels = nu->levels;
-            sp.ground_level = nu->ground_level;
             // levels from the per-label totals (pixels: the scan's counts; key points: counted by the key-point kernel)
-            salience_levels_kernel<<<Bs, 256, 0, st>>>(io->counts, p.kpn, M, sp, io->salience, p.label_acc);
-            LAUNCH_CHECK();
+            if ((rc = launch_salience_levels<L>(io->counts, p.kpn, Bs, M, salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level),
+                                                io->salience, p.label_acc, st)))
+                return rc;
         }
-        return launch_predict_quantize(io->ri, io->tm, io->seg, io->model, p.acc, p.label_acc, nullptr, Bs, P, M, io->q16,
+        // (the last kernel of the batch gives the next call's projection flags a new mark: p.epoch)
+        return launch_predict_quantize(io->ri, io->tm, seg, io->model, p.acc, p.label_acc, nullptr, Bs, P, M, io->q16,
                                        nullptr, nullptr, p.ws, st, p.epoch);
     }
     return RPCC_ERR_ARG;
 }
 
-static int check_batch_io(const rpcc_batch_io *io, int B, rpcc_geom g, int M, const void *ws) {
-    ARG_TRY(io != nullptr && ws != nullptr && B > 0 && B <= RPCC_MAX_BATCH && M > 0 && M <= RPCC_MAX_CLUSTERS && g.H > 1 && g.W > 0);
+// wide: rpcc_compress_batch_wide's rules -- up to RPCC_MAX_CLUSTERS_WIDE clusters, no CUDA-binary FPS mode, and no P % 4 rule
+static int check_batch_io(const rpcc_batch_io *io, int B, rpcc_geom g, int M, const void *ws, bool wide = false) {
+    ARG_TRY(io != nullptr && ws != nullptr && B > 0 && B <= RPCC_MAX_BATCH && M > 0 && M <= (wide ? RPCC_MAX_CLUSTERS_WIDE : RPCC_MAX_CLUSTERS) &&
+            g.H > 1 && g.W > 0);
     ARG_TRY(io->offsets && io->tm && io->ground && io->ri && io->seg && io->cen_pix && io->centers && io->model &&
             io->counts && io->q16 && io->nnz && io->info);
     const int P = g.H * g.W;
-    // only the brute-force FPS kernel (16-byte loads at frame bases) needs P % 4 == 0; the tile-pruned one does not
-    ARG_TRY(P % 4 == 0 || (io->flags & RPCC_FPS_MODE_BITS) || (!(io->flags & RPCC_FPS_BRUTEFORCE) && fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES));
+    if (wide)
+        ARG_TRY(!(io->flags & RPCC_FPS_MODE_BITS));
+    else   // only the brute-force FPS kernel (16-byte loads at frame bases) needs P % 4 == 0; the tile-pruned one does not
+        ARG_TRY(P % 4 == 0 || (io->flags & RPCC_FPS_MODE_BITS) || (!(io->flags & RPCC_FPS_BRUTEFORCE) && fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES));
     ARG_TRY(io->model_method == 0 || io->model_method == 1);
     ARG_TRY(point_floats(io->point_stride_bytes) > 0 && (io->point_stride_bytes != 16 || (reinterpret_cast<uintptr_t>(io->xyz) & 15u) == 0));
     if (io->nonuniform) {
@@ -3602,14 +3765,22 @@ static int check_batch_io(const rpcc_batch_io *io, int B, rpcc_geom g, int M, co
     return RPCC_OK;
 }
 
+// the stages of stage_mask (bit i = stage i of the enum above) of one batch whose arguments passed check_batch_io, in order
+template <class L>
+static int run_batch(const rpcc_batch_io *io, int B, rpcc_geom g, int M, double ground_threshold, float acc, void *ws, int stage_mask, hipStream_t st) {
+    BatchPlan p;
+    int rc;
+    if ((rc = plan_batch(p, io, B, io->total, g, M, ground_threshold, acc, reinterpret_cast<char *>(ws)))) return rc;
+    for (int stage = 0; stage < ST_COUNT; stage++)
+        if (((stage_mask >> stage) & 1) && (rc = run_stage<L>(p, stage, st))) return rc;
+    return RPCC_OK;
+}
+
 extern "C" int rpcc_compress_batch(const rpcc_batch_io *io, int B, rpcc_geom g, int M, double ground_threshold,
                                    float acc, void *ws, void *stream) {
     int rc;
     if ((rc = check_batch_io(io, B, g, M, ws))) return rc;
-    const BatchPlan p = plan_batch(io, B, io->total, g, M, ground_threshold, acc, reinterpret_cast<char *>(ws));
-    for (int stage = 0; stage < ST_COUNT; stage++)
-        if ((rc = run_stage(p, stage, (hipStream_t)stream))) return rc;
-    return RPCC_OK;
+    return run_batch<uint8_t>(io, B, g, M, ground_threshold, acc, ws, (1 << ST_COUNT) - 1, (hipStream_t)stream);
 }
 
 // A subset of the batch's stages (bit i of stage_mask = stage i of the enum above: projection, ground fit, mask, FPS, assignment + label
@@ -3620,10 +3791,7 @@ extern "C" int rpcc_compress_batch_stages(const rpcc_batch_io *io, int B, rpcc_g
                                           int stage_mask, void *stream) {
     int rc;
     if ((rc = check_batch_io(io, B, g, M, ws))) return rc;
-    const BatchPlan p = plan_batch(io, B, io->total, g, M, ground_threshold, acc, reinterpret_cast<char *>(ws));
-    for (int stage = 0; stage < ST_COUNT; stage++)
-        if (((stage_mask >> stage) & 1) && (rc = run_stage(p, stage, (hipStream_t)stream))) return rc;
-    return RPCC_OK;
+    return run_batch<uint8_t>(io, B, g, M, ground_threshold, acc, ws, stage_mask, (hipStream_t)stream);
 }
 
 // ---- several geometry groups in one call ----------------------------------------------------------------------------------------
@@ -3671,7 +3839,7 @@ static int mixed_fps(const BatchPlan *pl, int G, hipStream_t st) {
         LAUNCH_CHECK();
     }
     for (int i = 0; i < G; i++)
-        if (!common[i] && (rc = run_stage(pl[i], ST_FPS, st))) return rc;
+        if (!common[i] && (rc = run_stage<uint8_t>(pl[i], ST_FPS, st))) return rc;
     return RPCC_OK;
 }
 static int mixed_planes(const BatchPlan *pl, int G, hipStream_t st) {
@@ -3719,7 +3887,7 @@ static int mixed_labels(const BatchPlan *pl, int G, hipStream_t st) {
         const int T = ntiles(p.P);
         const bool point = io->model_method == 0;
         const float *ri = point ? io->ri : nullptr;   // (the plane model needs no range sums)
-        const bool vec = (p.P & 3) == 0 && ((uintptr_t)io->seg & 3u) == 0 && (ri == nullptr || ((uintptr_t)ri & 15u) == 0);
+        const bool vec = (p.P & 3) == 0 && seg4_aligned(io->seg) && (ri == nullptr || aligned16(ri));
         multi_add(mh, HistGroup{ri, io->seg, p.P, T, vec ? 1 : 0, p.L.sums, p.L.flags, p.L.hist}, p.Bs, T);
         multi_add(ms, ScanArgs{ri, io->seg, point ? io->ground : nullptr, p.P, M, KP, T, scan_kp2(M), p.L.sums, p.L.flags, p.L.hist,
                                point ? io->model : nullptr, io->counts, io->nnz}, p.Bs, 1);
@@ -3749,14 +3917,11 @@ static int mixed_quantise(const BatchPlan *pl, int G, hipStream_t st) {
             if ((rc = launch_features(io->ri, io->seg, p.Bs, p.g.H, p.g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num,
                                       nu->flat_num, nullptr, io->key_point_map, st, p.kpn, M + 2)))
                 return rc;
-            SalienceGroup sg;
-            sg.counts = io->counts; sg.kpn = p.kpn; sg.salience = io->salience; sg.label_acc = p.label_acc;
-            for (int l = 0; l < 8; l++) { sg.sp.level_kp_num[l] = l < nu->levels ? nu->level_kp_num[l] : 0; sg.sp.level_acc[l] = l < nu->levels ? nu->level_acc[l] : 0.f; }
-            sg.sp.levels = nu->levels; sg.sp.ground_level = nu->ground_level;
-            multi_add(msal, sg, p.Bs, 1);
+            multi_add(msal, SalienceGroup{io->counts, p.kpn, salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level), io->salience,
+                                          p.label_acc}, p.Bs, 1);
         }
         const int T = ntiles(p.P);
-        const bool vec = (p.P & 3) == 0 && ((uintptr_t)io->seg & 3u) == 0 && aligned16(io->ri) && aligned16(io->tm);
+        const bool vec = (p.P & 3) == 0 && seg4_aligned(io->seg) && aligned16(io->ri) && aligned16(io->tm);
         // (every group's kernel advances its own workspace's epoch: its frame 0 / tile 0 workgroup)
         multi_add(mq, QuantGroup{io->ri, io->tm, io->model, p.label_acc, io->seg, p.L.hist, p.P, T, vec ? 1 : 0, io->q16, p.epoch}, p.Bs, T);
     }
@@ -3777,7 +3942,7 @@ extern "C" int rpcc_compress_batch_mixed(const rpcc_batch_io *ios, const int *Bs
     BatchPlan pl[RPCC_MAX_GROUPS];
     for (int i = 0; i < G; i++) {
         if ((rc = check_batch_io(&ios[i], Bs[i], geoms[i], M, wss[i]))) return rc;
-        pl[i] = plan_batch(&ios[i], Bs[i], ios[i].total, geoms[i], M, ground_threshold, acc, reinterpret_cast<char *>(wss[i]));
+        if ((rc = plan_batch(pl[i], &ios[i], Bs[i], ios[i].total, geoms[i], M, ground_threshold, acc, reinterpret_cast<char *>(wss[i])))) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
     for (int stage = 0; stage < ST_COUNT; stage++) {
@@ -3787,7 +3952,7 @@ extern "C" int rpcc_compress_batch_mixed(const rpcc_batch_io *ios, const int *Bs
         else if (stage == ST_ASSIGN_LABELS) { if (!(rc = mixed_assign(pl, G, st))) rc = mixed_labels(pl, G, st); }
         else if (stage == ST_QUANTISE) rc = mixed_quantise(pl, G, st);
         else
-            for (int i = 0; i < G && !(rc = run_stage(pl[i], stage, st)); i++) {}
+            for (int i = 0; i < G && !(rc = run_stage<uint8_t>(pl[i], stage, st)); i++) {}
         if (rc) return rc;
     }
     return RPCC_OK;
@@ -3798,212 +3963,15 @@ extern "C" int rpcc_compress_batch_mixed(const rpcc_batch_io *ios, const int *Bs
 // ================================================================================================
 #include "wide_kernels.h"
 
-// ---- 255 .. RPCC_MAX_CLUSTERS_MID clusters with the point model: the tuned assignment / histogram / quantiser kernels on uint16 labels ----------------
+// ---- 255 .. RPCC_MAX_CLUSTERS_MID clusters: the tuned assignment / histogram / quantiser kernels on uint16 labels -------------------------------------
 // The label tables of those kernels live in LDS (16 B per centre, 12 and 40 B per label): up to 1022 clusters they still fit, so the kernels are
 // instantiated for uint16_t labels (assign_kernel<uint16_t, 16>: sixteen screening rounds of 64 centres) instead of going through the radix sort of
-// wide_kernels.h (89 k frames/s at 300 clusters against 367 k at 100: a 4 x cliff at 254 -> 255).  The scan between histogram and quantiser is
-// model_scan_kernel's job with a thread per label (K <= 1024): label totals, their exclusive prefix without label 1, the tiles' offsets, counts, nnz and the
-// point model's rows (cpp_modules.cpp:471-518).
-#define SCANW_THREADS 1024
-template <class L>
-__global__ __launch_bounds__(SCANW_THREADS) void model_scan_wide_kernel(const float *__restrict__ ri, const L *__restrict__ seg, const double *__restrict__ ground,
-                                                                        int P, int M, int KP, int T, const int64_t *__restrict__ sums,
-                                                                        const int32_t *__restrict__ flags, uint32_t *__restrict__ hist,
-                                                                        float *__restrict__ model, int32_t *__restrict__ counts, int32_t *__restrict__ nnz) {
-    __shared__ uint32_t wsum[SCANW_THREADS / 64];
-    const int b = blockIdx.x, k = threadIdx.x, K = M + 2, lane = k & 63, wave = k >> 6;
-    uint32_t *gh = hist + (int64_t)b * T * KP;
-    const uint32_t kp4 = (uint32_t)KP * 4u, k4 = (uint32_t)min(k, KP - 1) * 4u;
-    uint32_t total = 0u;
-    for (int t0 = 0; t0 < T; t0 += SCAN_U) {
-        uint32_t d[SCAN_U];
-#pragma unroll
-        for (int j = 0; j < SCAN_U; j++) d[j] = ld_at(gh, (uint32_t)min(t0 + j, T - 1) * kp4 + k4);   // unconditional (clamped) loads
-#pragma unroll
-        for (int j = 0; j < SCAN_U; j++) total += (t0 + j < T && k < K) ? d[j] : 0u;
-    }
-    const uint32_t v = (k < K && k != 1) ? total : 0u;   // label 1 = empty pixels: no residuals (cpp_modules.cpp:314)
-    const uint32_t incl = dpp_scan_incl_u32(v);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t off = 0u;
-    for (int w = 0; w < wave; w++) off += wsum[w];
-    if (k == SCANW_THREADS - 1 && nnz) nnz[b] = (int32_t)(off + incl);
-    if (k >= K) return;
-    uint32_t run = off + incl - v;
-    for (int t0 = 0; t0 < T; t0 += SCAN_U) {
-        uint32_t d[SCAN_U];
-#pragma unroll
-        for (int j = 0; j < SCAN_U; j++) d[j] = ld_at(gh, (uint32_t)min(t0 + j, T - 1) * kp4 + k4);
-#pragma unroll
-        for (int j = 0; j < SCAN_U; j++)
-            if (t0 + j < T) { st_at(gh, (uint32_t)(t0 + j) * kp4 + k4, run); run += d[j]; }
-    }
-    if (counts) counts[(int64_t)b * K + k] = (int32_t)total;
-    if (model != nullptr) {
-        float *row = model + ((int64_t)b * K + k) * 4;
-        if (k == 0) {
-            row[0] = (float)ground[4 * b]; row[1] = (float)ground[4 * b + 1]; row[2] = (float)ground[4 * b + 2]; row[3] = (float)ground[4 * b + 3];
-        } else if (k == 1) {
-            row[0] = row[1] = row[2] = row[3] = 0.0f;
-        } else {
-            double sm;
-            if (flags[4 * b]) {   // sequential double accumulation in row-major order (cpp_modules.cpp:514): ranges outside the fixed-point window, rare
-                sm = 0.0;
-                for (int p = 0; p < P; p++)
-                    if (seg[(int64_t)b * P + p] == (L)k) sm += (double)ri[(int64_t)b * P + p];
-            } else {
-                sm = (double)sums[(int64_t)b * KP + k] * (1.0 / 268435456.0);
-            }
-            row[0] = row[1] = row[2] = 0.0f;
-            row[3] = total == 0 ? u2f(0xFFC00000u) : (float)(sm / (double)total);
-        }
-    }
-}
-// The whole batch for such a cluster count: the fused batch's own plan and stages up to the FPS (projection with its hand-over to the ground fit, planar
-// ray table, the batch's initialisations inside the first kernel), then the label kernels on uint16_t.  ws: laid out as for rpcc_compress_batch
-// (rpcc_wide_workspace_bytes covers rpcc_workspace_bytes_general for these counts).
+// wide_kernels.h (89 k frames/s at 300 clusters against 367 k at 100: a 4 x cliff at 254 -> 255).  Such a batch is the fused batch's own plan and
+// stages (run_batch<uint16_t>); ws is laid out as for rpcc_compress_batch (rpcc_wide_workspace_bytes covers rpcc_workspace_bytes_general for these counts).
 static bool mid_clusters_ok(const rpcc_batch_io *io, rpcc_geom g, int M) {
     const int P = g.H * g.W;
     (void)io;
     return M <= RPCC_MAX_CLUSTERS_MID && P < (1 << 22) && fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES;
-}
-static int compress_batch_mid(const rpcc_batch_io *io, int B, rpcc_geom g, int M, double ground_threshold, float acc, void *ws, hipStream_t st) {
-    const BatchPlan p = plan_batch(io, B, io->total, g, M, ground_threshold, acc, reinterpret_cast<char *>(ws));
-    int rc;
-    for (int stage = ST_PROJECT; stage <= ST_FPS; stage++)
-        if ((rc = run_stage(p, stage, st))) return rc;
-    const int P = p.P, K = M + 2, KP = kpad(M), T = ntiles(P);
-    uint16_t *seg = reinterpret_cast<uint16_t *>(io->seg);
-    const int ntile = ((g.H + ASSIGN_ROWS - 1) / ASSIGN_ROWS) * ((g.W + 31) / 32);
-    const dim3 agrid((ntile + ASSIGN_WAVES * ASSIGN_TILES_PER_WAVE - 1) / (ASSIGN_WAVES * ASSIGN_TILES_PER_WAVE), B);
-    if (M <= 510) assign_kernel<uint16_t, 8><<<agrid, 64 * ASSIGN_WAVES, (size_t)M * sizeof(float4), st>>>(io->ri, io->tm, io->ground, io->centers, g.H, g.W, M, seg, p.temp);
-    else          assign_kernel<uint16_t, 16><<<agrid, 64 * ASSIGN_WAVES, (size_t)M * sizeof(float4), st>>>(io->ri, io->tm, io->ground, io->centers, g.H, g.W, M, seg, p.temp);
-    LAUNCH_CHECK();
-    // (sums / flags were cleared by the batch's first kernel: BatchInit)
-    const bool vec = (P & 3) == 0 && ((uintptr_t)seg & 7u) == 0 && ((uintptr_t)io->ri & 15u) == 0 && ((uintptr_t)io->tm & 15u) == 0;
-    const bool point = io->model_method == 0;
-    const float *ri_sums = point ? io->ri : nullptr;      // (the plane model needs the label counts and offsets only)
-    if (vec) model_hist_kernel<true, uint16_t><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri_sums, seg, P, KP, T, p.L.sums, p.L.flags, p.L.hist);
-    else     model_hist_kernel<false, uint16_t><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri_sums, seg, P, KP, T, p.L.sums, p.L.flags, p.L.hist);
-    model_scan_wide_kernel<uint16_t><<<B, SCANW_THREADS, 0, st>>>(ri_sums, seg, io->ground, P, M, KP, T, p.L.sums, p.L.flags, p.L.hist, point ? io->model : nullptr,
-                                                                  io->counts, io->nnz);
-    LAUNCH_CHECK();
-    if (!point) {   // a9 on the label-ordered lists (label_order_kernel on uint16 labels; the fits never see a label)
-        const size_t osh = (size_t)16 * (KP + 1) * 4 + (size_t)KP * 4;
-        HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&label_order_kernel<uint16_t>), (int)osh));
-        label_order_kernel<uint16_t><<<dim3(T, B), 256, osh, st>>>(seg, p.L.hist, P, M, KP, T, reinterpret_cast<uint32_t *>(p.extra), io->ri, io->tm, plane_pts4(p.extra, B, P));
-        LAUNCH_CHECK();
-        if ((rc = launch_plane_fits(io->tm, io->ground, B, P, M, io->plane_cos_cut, (uint32_t)io->plane_seed, io->frame_ids, io->model, io->counts, p.ws, p.extra, st))) return rc;
-    }
-    if (io->nonuniform) {
-        const rpcc_nonuniform_cfg *nu = io->nonuniform;
-        if ((rc = launch_features<uint16_t>(io->ri, seg, B, g.H, g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num, nu->flat_num,
-                                            nullptr, io->key_point_map, st, p.kpn, K))) return rc;
-        SalienceParams sp;
-        for (int i = 0; i < 8; i++) { sp.level_kp_num[i] = i < nu->levels ? nu->level_kp_num[i] : 0; sp.level_acc[i] = i < nu->levels ? nu->level_acc[i] : 0.f; }
-        sp.levels = nu->levels; sp.ground_level = nu->ground_level;
-        wide_salience_levels_kernel<<<dim3((K + 255) / 256, B), 256, 0, st>>>(io->counts, p.kpn, K, sp, io->salience, p.label_acc);
-        LAUNCH_CHECK();
-    }
-    const size_t sh = (size_t)KP * 40;
-    // (the last kernel of the batch gives the next call's projection flags a new mark: p.epoch)
-    if (vec) predict_quantize_kernel<false, true, uint16_t><<<dim3(T, B), 256, sh, st>>>(io->ri, io->tm, seg, io->model, p.L.hist, acc, p.label_acc, nullptr, P, M, KP, T, io->q16, nullptr, nullptr, p.epoch);
-    else     predict_quantize_kernel<false, false, uint16_t><<<dim3(T, B), 256, sh, st>>>(io->ri, io->tm, seg, io->model, p.L.hist, acc, p.label_acc, nullptr, P, M, KP, T, io->q16, nullptr, nullptr, p.epoch);
-    LAUNCH_CHECK();
-    return RPCC_OK;
-}
-
-// ---- the stage entries on uint16 labels, 255 .. RPCC_MAX_CLUSTERS_MID clusters (the reference-side classes call the stages one by one:
-// PointCloudSegment.segment / cluster_modeling('point') / intra_predict, QuantizationModule.quantize_residual with the uniform framework) ------------
-static int hist_scan_u16(const float *ri, const uint16_t *seg, const double *ground, int B, int P, int M, const WsLayout &L, float *model,
-                         int32_t *counts, int32_t *nnz, hipStream_t st) {
-    const int KP = kpad(M), T = ntiles(P);
-    const bool vec = (P & 3) == 0 && ((uintptr_t)seg & 7u) == 0 && (ri == nullptr || ((uintptr_t)ri & 15u) == 0);
-    HIP_TRY(hipMemsetAsync(L.sums, 0, (size_t)((char *)L.hist - (char *)L.sums), st));
-    if (vec) model_hist_kernel<true, uint16_t><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri, seg, P, KP, T, L.sums, L.flags, L.hist);
-    else     model_hist_kernel<false, uint16_t><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri, seg, P, KP, T, L.sums, L.flags, L.hist);
-    model_scan_wide_kernel<uint16_t><<<B, SCANW_THREADS, 0, st>>>(ri, seg, ground, P, M, KP, T, L.sums, L.flags, L.hist, model, counts, nnz);
-    LAUNCH_CHECK();
-    return RPCC_OK;
-}
-extern "C" int rpcc_assign_wide(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H, int W, int M,
-                                uint16_t *seg, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS_MID && ri && tm && ground && centers && seg);
-    hipStream_t st = (hipStream_t)stream;
-    const int ntile = ((H + ASSIGN_ROWS - 1) / ASSIGN_ROWS) * ((W + 31) / 32);
-    const dim3 grid((ntile + ASSIGN_WAVES * ASSIGN_TILES_PER_WAVE - 1) / (ASSIGN_WAVES * ASSIGN_TILES_PER_WAVE), B);
-    if (M <= 510) assign_kernel<uint16_t, 8><<<grid, 64 * ASSIGN_WAVES, (size_t)M * sizeof(float4), st>>>(ri, tm, ground, centers, H, W, M, seg, nullptr);
-    else          assign_kernel<uint16_t, 16><<<grid, 64 * ASSIGN_WAVES, (size_t)M * sizeof(float4), st>>>(ri, tm, ground, centers, H, W, M, seg, nullptr);
-    LAUNCH_CHECK();
-    return RPCC_OK;
-}
-extern "C" int rpcc_point_model_wide(const float *ri, const uint16_t *seg, const double *ground, int B, int P, int M, float *model, int32_t *counts,
-                                     void *ws, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS_MID && ri && seg && ground && model && ws);
-    return hist_scan_u16(ri, seg, ground, B, P, M, ws_layout(ws, B, P, M), model, counts, nullptr, (hipStream_t)stream);
-}
-// rpcc_extract_features / rpcc_salience on uint16 labels
-extern "C" int rpcc_extract_features_wide(const float *ri, const uint16_t *seg, int B, int H, int W, int feature_region, int segments, int sharp_num,
-                                          int less_sharp_num, int flat_num, float *feat, uint8_t *key_point_map, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && ri && seg && feat && key_point_map);
-    return launch_features<uint16_t>(ri, seg, B, H, W, feature_region, segments, sharp_num, less_sharp_num, flat_num, feat, key_point_map, (hipStream_t)stream);
-}
-extern "C" int rpcc_salience_wide(const uint16_t *seg, const uint8_t *key_point_map, const int32_t *level_kp_num, const float *level_acc, int levels,
-                                  int ground_level, int B, int P, int M, uint8_t *salience, float *label_acc, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS_MID && seg && key_point_map && salience && label_acc);
-    ARG_TRY(level_kp_num && level_acc && levels >= 1 && levels <= 8 && ground_level >= 0 && ground_level < levels);
-    SalienceParams sp;
-    for (int i = 0; i < 8; i++) { sp.level_kp_num[i] = i < levels ? level_kp_num[i] : 0; sp.level_acc[i] = i < levels ? level_acc[i] : 0.f; }
-    sp.levels = levels;
-    sp.ground_level = ground_level;
-    salience_kernel<uint16_t, 1024><<<B, SAL_THREADS, 0, (hipStream_t)stream>>>(seg, key_point_map, P, M, sp, salience, label_acc);
-    LAUNCH_CHECK();
-    return RPCC_OK;
-}
-// rpcc_plane_model on uint16 labels (ws: rpcc_plane_workspace_bytes(B, P, M) bytes)
-extern "C" int rpcc_plane_model_wide(const float *ri, const float *tm, const uint16_t *seg, const double *ground, int B, int P, int M, double cos_cut,
-                                     uint32_t seed, const int64_t *frame_ids, const double *inject_planes, float *model, int32_t *counts, void *ws,
-                                     void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS_MID && ri && tm && seg && model && counts && ws);
-    hipStream_t st = (hipStream_t)stream;
-    const WsLayout L = ws_layout(ws, B, P, M);
-    const int KP = kpad(M), T = ntiles(P);
-    int rc;
-    if ((rc = hist_scan_u16(nullptr, seg, nullptr, B, P, M, L, nullptr, counts, nullptr, st))) return rc;
-    void *extra = reinterpret_cast<char *>(ws) + L.bytes + 256;
-    const size_t osh = (size_t)16 * (KP + 1) * 4 + (size_t)KP * 4;
-    HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&label_order_kernel<uint16_t>), (int)osh));
-    label_order_kernel<uint16_t><<<dim3(T, B), 256, osh, st>>>(seg, L.hist, P, M, KP, T, reinterpret_cast<uint32_t *>(extra), ri, tm, plane_pts4(extra, B, P));
-    LAUNCH_CHECK();
-    return launch_plane_fits(tm, ground, B, P, M, cos_cut, seed, frame_ids, model, counts, ws, extra, st, inject_planes);
-}
-extern "C" int rpcc_intra_predict_wide(const uint16_t *seg, const float *model, const float *tm, int B, int P, int M, float *pred, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS_WIDE && seg && model && tm && pred);
-    intra_predict_kernel<uint16_t><<<dim3((P + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(seg, model, tm, P, M + 2, pred);
-    LAUNCH_CHECK();
-    return RPCC_OK;
-}
-extern "C" int rpcc_predict_quantize_wide(const float *ri, const float *tm, const uint16_t *seg, const float *model, const float *label_acc,
-                                          const float *residual_in, float acc, int B, int P, int M, int16_t *q16, int32_t *q32, int32_t *nnz,
-                                          float *pred, void *ws, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS_MID && seg && ws);
-    ARG_TRY((residual_in && !pred) || (ri && tm && model));   // residual handed in, no prediction wanted: seg only
-    ARG_TRY(q16 || q32);
-    hipStream_t st = (hipStream_t)stream;
-    const int KP = kpad(M), T = ntiles(P);
-    const WsLayout L = ws_layout(ws, B, P, M);
-    int rc;
-    if ((rc = hist_scan_u16(ri, seg, nullptr, B, P, M, L, nullptr, nullptr, nnz, st))) return rc;
-    const size_t sh = (size_t)KP * 40;
-    const bool resid = residual_in && !pred;
-    const bool vec = (P & 3) == 0 && ((uintptr_t)seg & 7u) == 0 && (resid || (aligned16(ri) && aligned16(tm))) && (!residual_in || aligned16(residual_in));
-#define PQW_LAUNCH(R_, V_) predict_quantize_kernel<R_, V_, uint16_t><<<dim3(T, B), 256, sh, st>>>(ri, tm, seg, model, L.hist, acc, label_acc, residual_in, P, M, KP, T, q16, q32, pred, nullptr)
-    if (resid) { if (vec) PQW_LAUNCH(true, true); else PQW_LAUNCH(true, false); }
-    else       { if (vec) PQW_LAUNCH(false, true); else PQW_LAUNCH(false, false); }
-#undef PQW_LAUNCH
-    LAUNCH_CHECK();
-    return RPCC_OK;
 }
 
 // carve-up of a wide workspace: [ keys, vals (in / out) u32 4 x [B,P] | pos i32 [B,P] | order u32 [B,P] | pts4 float4 [B,P] | sums u64 [B,K] |
@@ -4049,7 +4017,7 @@ static WideWs wide_layout(void *ws, int B, int P, int M, int64_t total_points) {
 extern "C" size_t rpcc_wide_workspace_bytes(int B, int P, int M, int64_t total_points) {
     if (B <= 0 || P <= 0 || M <= 0) return 0;
     const size_t sorted = wide_layout(nullptr, B, P, M, total_points).bytes + 4096;
-    // (up to RPCC_MAX_CLUSTERS_MID clusters the point model runs on the fused batch's own layout: compress_batch_mid)
+    // (up to RPCC_MAX_CLUSTERS_MID clusters the batch runs on the fused batch's own layout: run_batch<uint16_t>)
     return M <= RPCC_MAX_CLUSTERS_MID ? std::max(sorted, rpcc_workspace_bytes_general(B, P, M, total_points)) : sorted;
 }
 // counts, sums, the sort and the positions of a segmentation (encoder and decoder)
@@ -4072,20 +4040,14 @@ static int wide_order(const L *seg, const float *ri_for_sums, const float *ri, c
 }
 
 extern "C" int rpcc_compress_batch_wide(const rpcc_batch_io *io, int B, rpcc_geom g, int M, double ground_threshold, float acc, void *ws, void *stream) {
-    ARG_TRY(io != nullptr && ws != nullptr && B > 0 && B <= RPCC_MAX_BATCH && M > 0 && M <= RPCC_MAX_CLUSTERS_WIDE && g.H > 1 && g.W > 0);
-    ARG_TRY(io->offsets && io->tm && io->ground && io->ri && io->seg && io->cen_pix && io->centers && io->model && io->counts && io->q16 && io->nnz && io->info);
-    ARG_TRY(io->model_method == 0 || io->model_method == 1);
-    ARG_TRY(!(io->flags & RPCC_FPS_MODE_BITS));
-    ARG_TRY(point_floats(io->point_stride_bytes) > 0 && (io->point_stride_bytes != 16 || (reinterpret_cast<uintptr_t>(io->xyz) & 15u) == 0));
-    if (io->nonuniform) ARG_TRY(io->salience && io->key_point_map && io->nonuniform->levels >= 1 && io->nonuniform->levels <= 8 &&
-                                io->nonuniform->ground_level >= 0 && io->nonuniform->ground_level < io->nonuniform->levels);
+    int rc;
+    if ((rc = check_batch_io(io, B, g, M, ws, true))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int P = g.H * g.W, K = M + 2;
     ARG_TRY(fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES && P < (1 << 22));
-    if (mid_clusters_ok(io, g, M)) return compress_batch_mid(io, B, g, M, ground_threshold, acc, ws, st);
+    if (mid_clusters_ok(io, g, M)) return run_batch<uint16_t>(io, B, g, M, ground_threshold, acc, ws, (1 << ST_COUNT) - 1, st);
     const WideWs w = wide_layout(ws, B, P, M, io->total);
     uint16_t *seg = reinterpret_cast<uint16_t *>(io->seg);
-    int rc;
     if ((rc = launch_project(io->xyz, io->offsets, io->total, 0, B, g, io->ri, w.proj, w.proj_bytes, st, nullptr, nullptr, nullptr, nullptr,
                              point_floats(io->point_stride_bytes), order_mode_of(io->flags), io->tm))) return rc;
     if (io->ground_seed >= 0 && (rc = launch_ground_ransac(io->ri, io->tm, B, P, (uint32_t)io->ground_seed, false, io->ground, nullptr, st, nullptr, io->frame_ids))) return rc;
@@ -4113,11 +4075,9 @@ extern "C" int rpcc_compress_batch_wide(const rpcc_batch_io *io, int B, rpcc_geo
         HIP_TRY(hipMemsetAsync(w.kpn, 0, (size_t)B * K * 4, st));
         if ((rc = launch_features<uint16_t>(io->ri, seg, B, g.H, g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num, nu->flat_num,
                                             nullptr, io->key_point_map, st, w.kpn, K))) return rc;
-        SalienceParams sp;
-        for (int i = 0; i < 8; i++) { sp.level_kp_num[i] = i < nu->levels ? nu->level_kp_num[i] : 0; sp.level_acc[i] = i < nu->levels ? nu->level_acc[i] : 0.f; }
-        sp.levels = nu->levels; sp.ground_level = nu->ground_level;
-        wide_salience_levels_kernel<<<dim3((K + 255) / 256, B), 256, 0, st>>>(io->counts, w.kpn, K, sp, io->salience, w.label_acc);
-        LAUNCH_CHECK();
+        if ((rc = launch_salience_levels<uint16_t>(io->counts, w.kpn, B, M, salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level),
+                                                   io->salience, w.label_acc, st)))
+            return rc;
         label_acc = w.label_acc;
     }
     wide_quantise_kernel<uint16_t><<<dim3((P + 255) / 256, B), 256, 0, st>>>(io->ri, io->tm, seg, io->model, w.pos, acc, label_acc, P, K, io->q16);

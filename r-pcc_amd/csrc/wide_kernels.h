@@ -204,22 +204,6 @@ __global__ __launch_bounds__(256) void wide_point_model_kernel(const float *__re
         row[3] = total == 0 ? u2f(0xFFC00000u) : (float)(s / (double)total);
     }
 }
-// a13 from the per-label totals (salience_levels_kernel for any K)
-__global__ __launch_bounds__(256) void wide_salience_levels_kernel(const int32_t *__restrict__ counts, const int32_t *__restrict__ kpn, int K, SalienceParams sp,
-                                                                   uint8_t *__restrict__ salience, float *__restrict__ label_acc) {
-    const int b = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= K) return;
-    const int pn = counts[(int64_t)b * K + k], kn = kpn[(int64_t)b * K + k];
-    int lv = 0;
-    if (k == 0) lv = sp.ground_level;
-    else if (k == 1) lv = sp.levels - 1;
-    else if (pn < 30) lv = sp.levels - 1;
-    else
-        for (int l = 0; l < sp.levels; l++)
-            if (kn >= sp.level_kp_num[l]) { lv = l; break; }
-    salience[(int64_t)b * K + k] = (uint8_t)lv;
-    label_acc[(int64_t)b * K + k] = sp.level_acc[lv];
-}
 // a10 + a11 / a13: prediction, residual, quantisation, the integer to its position (cpp_modules.cpp:248-285,288-334, compress.py:106)
 template <class L>
 __global__ __launch_bounds__(256) void wide_quantise_kernel(const float *__restrict__ ri, const float *__restrict__ tm, const L *__restrict__ seg,

@@ -74,7 +74,7 @@ def test_wide_batch_vs_oracle(env, M, uniform, method):
 
 
 def test_mid_cluster_counts_with_the_bruteforce_fps_and_groundless_frames(env):
-    """cluster_num = 300 through the fused plan (compress_batch_mid): the one-pass-per-centre FPS (RPCC_FPS_BRUTEFORCE) gives the same centres, labels
+    """cluster_num = 300 through the fused plan (run_batch<uint16_t>): the one-pass-per-centre FPS (RPCC_FPS_BRUTEFORCE) gives the same centres, labels
     and integers as the pruned one, and a batch that holds a sweep without ground returns (whole-cloud fit, scored chip-wide) equals the oracle."""
     torch, ops, orc, dev = env["torch"], env["ops"], env["orc"], env["dev"]
     gd, g, geom, tm = _geom(env, "VelodyneVLP16")

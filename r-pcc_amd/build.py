@@ -9,6 +9,12 @@ DEPS = [os.path.join(_HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(_
 LIB = os.path.join(_HERE, "lib", "librpcc_hip.so")
 HOST_SRC = os.path.join(_HERE, "csrc", "rpcc_host.c")
 HOST_LIB = os.path.join(_HERE, "lib", "librpcc_host.so")
+# librpcc_eval.so (reconstruction metrics, include/rpcc_eval.h): a library of its own, so that neither DEPS nor
+# source_digest() -- the compression library's identity -- changes with it.
+EVAL_SRC = os.path.join(_HERE, "csrc_eval", "eval_kernels.hip")
+EVAL_DEPS = [os.path.join(_HERE, "csrc_eval", f) for f in sorted(os.listdir(os.path.join(_HERE, "csrc_eval")))] + \
+            [os.path.join(os.path.dirname(_HERE), "include", "rpcc_eval.h")]
+EVAL_LIB = os.path.join(_HERE, "lib", "librpcc_eval.so")
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -41,21 +47,31 @@ def build_host(force=False, verbose=False):
     return HOST_LIB
 
 
+def _hipcc(src, lib, deps, force, verbose):
+    os.makedirs(os.path.dirname(lib), exist_ok=True)
+    if not force and os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(d) for d in deps):
+        return lib
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    extra = os.environ.get("RPCC_EXTRA_FLAGS", "").split()   # developer builds only: -DRPCC_DEVTRACE (csrc/rpcc_trace.h)
+    cmd = [hipcc] + HIPCC_FLAGS + extra + [src, "-o", lib]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return lib
+
+
+def build_eval(force=False, verbose=False):
+    """librpcc_eval.so: the reconstruction-metrics kernels (csrc_eval/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(EVAL_SRC, EVAL_LIB, EVAL_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
     except (subprocess.CalledProcessError, OSError) as e:   # no libbz2.so.1.0 / no gcc: compress_utils.pack_frames then
         print("librpcc_host.so not built (%s): containers are packed by the interpreter's bz2 module" % e)  # takes the Python path
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    if not force and os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    extra = os.environ.get("RPCC_EXTRA_FLAGS", "").split()   # developer builds only: -DRPCC_DEVTRACE (csrc/rpcc_trace.h)
-    cmd = [hipcc] + HIPCC_FLAGS + extra + [SRC, "-o", LIB]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    return LIB
+    build_eval(force, verbose)
+    return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 
 if __name__ == "__main__":

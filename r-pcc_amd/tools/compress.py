@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Single-frame compression -- same flags and stage structure as the reference's tools/compress.py,
-running on the HIP path.  (--eval prints the depth-error check only: the chamfer / PSNR metrics of the
-reference need packages that are out of scope.)"""
+running on the HIP path.  --eval prints the reference's reconstruction-quality lines: the depth error, then the Chamfer
+distance, F-score and point-to-point / point-to-plane PSNR of rpcc_amd.evaluate_metrics (librpcc_eval.so)."""
 import argparse
 import os
 import sys
@@ -42,6 +42,8 @@ def make_parser(datalist=False):
     else:
         p.add_argument("--input", help="single frame input for static compression.")
         p.add_argument("--output", help="output bitstream.")
+        p.add_argument("--original_point_cloud", default=None,
+                       help="decompress.py --eval: the original point cloud file to compare the reconstruction with.")
     p.add_argument("--lidar", help="lidar type of this point cloud collection.")
     p.add_argument("--compressor_yaml", default=os.path.join(PKG, "cfgs/compressor.yaml"))
     p.add_argument("--basic_compressor", type=str, default=None, help="for manual setting.")
@@ -103,6 +105,17 @@ def make_quantizer(cfg, accuracy, uniform):
                               less_sharp_num=cfg["less_sharp_num"], flat_num=cfg["flat_num"])
 
 
+def print_quality(point_cloud, point_cloud_rec):
+    """The four metric lines of the reference's --eval (tools/compress.py:185-192, tools/decompress.py:146-150)."""
+    from rpcc_amd.evaluate_metrics import calc_chamfer_distance, calc_point_to_point_plane_psnr
+    chamfer = calc_chamfer_distance(point_cloud, point_cloud_rec, out=False)
+    point_to_point, point_to_plane = calc_point_to_point_plane_psnr(point_cloud, point_cloud_rec, out=False)
+    print("    Chamfer Distance (mean): ", chamfer["mean"])
+    print("    F1 score (threshold=0.02): ", chamfer["f_score"])
+    print("    Point-to-Point PSNR (r=59.7): ", point_to_point["psnr_mean"])
+    print("    Point-to-Plane PSNR (r=59.7): ", point_to_plane["psnr_mean"])
+
+
 def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform):
     """cluster_num above 254 (labels as uint16): the per-stage mirror classes keep labels in a byte, so the frame goes through the batch front-end
     (pipeline.BatchCompressor -> rpcc_compress_batch_wide) as a batch of one.  Same container, same decoder."""
@@ -139,6 +152,8 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
         print("    Depth Error (max): ", float(np.max(dif)))
         if float(np.max(dif)) > bound:
             raise AssertionError("Reconstruction error... Please check...")
+        T = dataset.PCTransformer
+        print_quality(T.range_image_to_point_cloud(ri), T.range_image_to_point_cloud(rec))
 
 
 def compress(args):
@@ -204,6 +219,7 @@ def compress(args):
         print("    Depth Error (max): ", float(np.max(dif)))
         if float(np.max(dif)) > bound:
             raise AssertionError("Reconstruction error... Please check...")
+        print_quality(point_cloud, dataset.PCTransformer.range_image_to_point_cloud(rec))
 
 
 if __name__ == "__main__":

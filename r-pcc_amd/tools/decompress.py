@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Single-frame decompression -- counterpart of the reference's tools/decompress.py on the HIP path.
 Nothing about the configuration is stored in the .rpcc file: the decoder needs the same YAML / flags /
-lidar type as the encoder (as in the reference)."""
+lidar type as the encoder (as in the reference).  --eval --original_point_cloud FILE compares the reconstruction with
+the original (tools/decompress.py:117-150 of the reference)."""
 import os
 import sys
 import time
@@ -16,7 +17,7 @@ import rpcc_amd  # noqa: E402,F401
 from rpcc_amd import ops  # noqa: E402
 from rpcc_amd.compress_utils import decompress_point_cloud, read_compressed_bitstream  # noqa: E402
 from rpcc_amd.dataset import build_dataset  # noqa: E402
-from rpcc_amd.tools.compress import make_parser, resolve_cfg  # noqa: E402
+from rpcc_amd.tools.compress import make_parser, print_quality, resolve_cfg  # noqa: E402
 
 
 def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy, level_acc, uniform, want_points=True):
@@ -78,6 +79,8 @@ def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy
 
 
 def decompress(args):
+    if args.eval and args.original_point_cloud is None:
+        raise ValueError("--eval compares with the original point cloud: set --original_point_cloud")
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
     dataset = build_dataset(lidar_type=args.lidar)
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
@@ -91,6 +94,18 @@ def decompress(args):
     print("reconstructed point cloud save in ", args.output)
     print("    Decode time: ", t1 - t0)
     print("    Points: ", int((rec != 0).sum()))
+    if args.eval:
+        print("\nStart evaluation...")
+        point_cloud, range_image, _ = dataset.load_range_image_points_from_file(args.original_point_cloud)
+        n_points = int((range_image != 0).sum())
+        dif = np.abs(rec - range_image[..., 0])
+        bits = os.path.getsize(args.input) * 8
+        print("\nCompared with ", args.original_point_cloud)
+        print("    BPP: ", bits / n_points)
+        print("    Compression Ratio: ", (n_points * 32 * 3) / bits)
+        print("    Depth Error (mean): ", float(np.mean(dif)))
+        print("    Depth Error (max): ", float(np.max(dif)))
+        print_quality(point_cloud, pc)
 
 
 if __name__ == "__main__":

@@ -15,6 +15,11 @@ EVAL_SRC = os.path.join(_HERE, "csrc_eval", "eval_kernels.hip")
 EVAL_DEPS = [os.path.join(_HERE, "csrc_eval", f) for f in sorted(os.listdir(os.path.join(_HERE, "csrc_eval")))] + \
             [os.path.join(os.path.dirname(_HERE), "include", "rpcc_eval.h")]
 EVAL_LIB = os.path.join(_HERE, "lib", "librpcc_eval.so")
+# librpcc_seg.so (DBSCAN segmentation, include/rpcc_seg.h): a library of its own for the same reason.
+SEG_SRC = os.path.join(_HERE, "csrc_seg", "dbscan_kernels.hip")
+SEG_DEPS = [os.path.join(_HERE, "csrc_seg", f) for f in sorted(os.listdir(os.path.join(_HERE, "csrc_seg")))] + \
+           [os.path.join(os.path.dirname(_HERE), "include", "rpcc_seg.h")]
+SEG_LIB = os.path.join(_HERE, "lib", "librpcc_seg.so")
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -65,12 +70,18 @@ def build_eval(force=False, verbose=False):
     return _hipcc(EVAL_SRC, EVAL_LIB, EVAL_DEPS, force, verbose)
 
 
+def build_seg(force=False, verbose=False):
+    """librpcc_seg.so: the DBSCAN segmentation kernels (csrc_seg/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(SEG_SRC, SEG_LIB, SEG_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
     except (subprocess.CalledProcessError, OSError) as e:   # no libbz2.so.1.0 / no gcc: compress_utils.pack_frames then
         print("librpcc_host.so not built (%s): containers are packed by the interpreter's bz2 module" % e)  # takes the Python path
     build_eval(force, verbose)
+    build_seg(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

@@ -9,7 +9,10 @@ tools/compress.py-style drivers read the same.  What differs, by construction:
 * the ground plane: the reference calls Open3D's random RANSAC; here `ransac_plane_segmentation` is the
   build's seeded RANSAC on the device (rpcc_ground_ransac).  Assigning a different callable to
   `PointCloudSegment.ransac_plane_segmentation` (as the reference's users can) injects a model.
-* DBSCAN segmentation (utils/segment_utils.py:149-164) is out of scope.
+* `segment_method: 'DBSCAN'` (utils/segment_utils.py:149-169, Open3D's cluster_dbscan with min_points 10) runs the
+  exact DBSCAN of librpcc_seg.so (rpcc_amd.dbscan) on the same ground plane as the FPS branch.
+  Its labels go to the same stage entries, which take labels up to RPCC_MAX_CLUSTERS_MID + 1; a frame with more
+  clusters raises RpccError instead of being truncated.
 """
 import numpy as np
 import torch
@@ -46,12 +49,28 @@ class PointCloudSegment:
         assert self.transform_map is not None, "Must set transform_map first."
         method = segment_cfg["segment_method"]
         assert method in ["FPS", "DBSCAN"]
-        if method != "FPS":
-            raise NotImplementedError("DBSCAN segmentation is out of scope (SURVEY.md section 2)")
+        ri = self._ri(range_image)
+        if method == "DBSCAN":
+            ground = self._ground(point_cloud, ri)
+            return self._dbscan(ri, ground, segment_cfg["DBSCAN_eps"])
         thr = segment_cfg["ground_vertical_threshold"]
         # the stage entries: byte labels up to 254, uint16 ones (rpcc_assign_wide) up to 1022 -- a larger value is named in the error (BatchCompressor: 65533)
         M = ops.check_cluster_num(segment_cfg["cluster_num"], stage="mid")
-        ri = self._ri(range_image)
+        ground = self._ground(point_cloud, ri)
+        # RPCC_FPS_FMA / RPCC_FPS_TIE_CUDA (environment): the CUDA binary's contraction / tree tie rule (ops.fps_range)
+        from ._lib import fps_mode_flags
+        if fps_mode_flags(None, None):
+            temp, info = ops.ground_mask(ri, self._tm, ground, thr, fps_table=False)
+            cen_pix, centers = ops.fps_range(ri, self._tm, temp, info, M, fma=None, cuda_tie=None)
+        else:
+            temp, info, tab = ops.ground_mask(ri, self._tm, ground, thr, fps_table=True)
+            cen_pix, centers = ops.fps_range(ri, self._tm, temp, info, M, fps_table=tab)
+        seg = ops.assign(ri, self._tm, ground, centers)
+        self._cache = dict(ri=ri, ground=ground, seg=seg, M=M)
+        return seg[0].cpu().numpy().astype(np.int64), ground[0].cpu().numpy()
+
+    def _ground(self, point_cloud, ri):
+        """The ground plane f64 [1,4]: the injected fit on the reference's candidates, else the seeded device RANSAC."""
         inject = type(self).ransac_plane_segmentation
         if inject is not None:
             # the reference's candidate selection (utils/segment_utils.py:101-106) feeding the injected fit
@@ -64,16 +83,19 @@ class PointCloudSegment:
             ground = torch.from_numpy(np.asarray(gm, np.float64).reshape(1, 4)).to(self.device)
         else:
             ground, _ = ops.ground_ransac(ri, self._tm, seed=self.seed, frame_ids=[self.frame_id])
-        # RPCC_FPS_FMA / RPCC_FPS_TIE_CUDA (environment): the CUDA binary's contraction / tree tie rule (ops.fps_range)
-        from ._lib import fps_mode_flags
-        if fps_mode_flags(None, None):
-            temp, info = ops.ground_mask(ri, self._tm, ground, thr, fps_table=False)
-            cen_pix, centers = ops.fps_range(ri, self._tm, temp, info, M, fma=None, cuda_tie=None)
-        else:
-            temp, info, tab = ops.ground_mask(ri, self._tm, ground, thr, fps_table=True)
-            cen_pix, centers = ops.fps_range(ri, self._tm, temp, info, M, fps_table=tab)
-        seg = ops.assign(ri, self._tm, ground, centers)
-        self._cache = dict(ri=ri, ground=ground, seg=seg, M=M)
+        return ground
+
+    def _dbscan(self, ri, ground, eps):
+        """utils/segment_utils.py:149-169 (min_points = 10, as the reference hard-codes it)."""
+        from . import _lib
+        from .dbscan import dbscan_segment
+        seg, max_label = dbscan_segment(ri, self._tm, ground, eps, min_points=10)
+        top = int(max_label[0])
+        if top > _lib.MAX_CLUSTERS_MID + 1:
+            raise _lib.RpccError("DBSCAN found labels up to %d in this frame: the stage-by-stage entries for the point model, prediction and "
+                                 "the quantisers take labels up to RPCC_MAX_CLUSTERS_MID + 1 = %d (include/rpcc_hip.h); use a larger "
+                                 "DBSCAN_eps" % (top, _lib.MAX_CLUSTERS_MID + 1))
+        self._cache = dict(ri=ri, ground=ground, seg=seg, M=max(top - 1, 1))
         return seg[0].cpu().numpy().astype(np.int64), ground[0].cpu().numpy()
 
     def cluster_modeling(self, point_cloud, range_image, seg_idx, model_cfg, ground_model=None):

@@ -160,7 +160,8 @@ def compress(args):
     apply_fps_mode(args)
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
     from rpcc_amd import ops
-    if ops.is_wide(ops.check_cluster_num(segment_cfg["cluster_num"])):
+    # DBSCAN: always the per-frame stages (the batch front-end runs FPS only); cluster_num does not apply
+    if segment_cfg["segment_method"] != "DBSCAN" and ops.is_wide(ops.check_cluster_num(segment_cfg["cluster_num"])):
         return compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform)
     dataset = build_dataset(lidar_type=args.lidar)
     model_num = segment_cfg["cluster_num"] + 1

@@ -20,16 +20,25 @@ from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.tools.compress import make_parser, print_quality, resolve_cfg  # noqa: E402
 
 
+def stream_cluster_num(segment_cfg):
+    """cluster_num as decode_frame takes it: the configured value for FPS; None for DBSCAN, whose label count is set by the
+    frame, so decode_frame sizes it from the stream's model rows."""
+    return None if segment_cfg["segment_method"] == "DBSCAN" else segment_cfg["cluster_num"]
+
+
 def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy, level_acc, uniform, want_points=True):
-    """decompress_point_cloud + dequantise + predict + back-project (tools/decompress.py:79-112)."""
+    """decompress_point_cloud + dequantise + predict + back-project (tools/decompress.py:79-112).  cluster_num None
+    (DBSCAN, stream_cluster_num): the labels 0 .. rows - 1 of the stream's model rows."""
     H, W = transformer.H, transformer.W
     d = basic_compressor.decompress_dict(blob_dict)
     # The .rpcc file stores no configuration (as in the reference): a wrong --lidar / cluster_num / framework shows up as
     # payload sizes that do not fit.  Check them here instead of letting the kernels index past their buffers.
-    P, K = H * W, cluster_num + 2
     if len(d["plane_param"]) % 16 != 0:
         raise ValueError("plane_param payload is not a whole number of float32 [.,4] rows")
     plane_param = np.frombuffer(d["plane_param"], dtype=np.float32).reshape(-1, 4)
+    if cluster_num is None:
+        cluster_num = max(plane_param.shape[0] - 2, 1)
+    P, K = H * W, cluster_num + 2
     if plane_param.shape[0] > K:
         raise ValueError("bitstream holds %d model rows, the configuration allows cluster_num + 2 = %d" % (plane_param.shape[0], K))
     if len(d["contour_map"]) != (P + 7) // 8:
@@ -86,7 +95,7 @@ def decompress(args):
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     t0 = time.time()
     cd = read_compressed_bitstream(args.input, uniform=uniform)
-    rec, pc, seg = decode_frame(cd, basic_compressor, dataset.PCTransformer, segment_cfg["cluster_num"], accuracy,
+    rec, pc, seg = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
                                 level_acc, uniform)
     t1 = time.time()
     dataset.save_point_cloud_to_file(args.output, pc.reshape(-1, 3))

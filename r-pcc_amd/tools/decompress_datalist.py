@@ -15,7 +15,7 @@ from rpcc_amd.compress_utils import read_compressed_bitstream  # noqa: E402
 from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.sharding import shard_indices  # noqa: E402
 from rpcc_amd.tools.compress import make_parser, resolve_cfg  # noqa: E402
-from rpcc_amd.tools.decompress import decode_frame  # noqa: E402
+from rpcc_amd.tools.decompress import decode_frame, stream_cluster_num  # noqa: E402
 
 
 def decompress(args):
@@ -28,7 +28,7 @@ def decompress(args):
     for i in shard_indices(len(dataset), rank, world):
         name = dataset.data_list[i]
         cd = read_compressed_bitstream(name, uniform=uniform)
-        rec, pc, _ = decode_frame(cd, basic_compressor, dataset.PCTransformer, segment_cfg["cluster_num"], accuracy,
+        rec, pc, _ = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
                                   level_acc, uniform)
         rel = name[1:] if name.startswith("/") else name
         out = os.path.join(args.output_dir, rel)

@@ -58,8 +58,6 @@ class RpccError(RuntimeError):
     pass
 
 
-_lib = None
-
 _VP, _I, _I64, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _SIGS = {
     "rpcc_version": (C.c_int, []),
@@ -149,31 +147,42 @@ def host_lib():
     return _host
 
 
-def exported_symbols():
-    return sorted(_SIGS)
+class Binding:
+    """One of the package's HIP libraries, loaded on first use: the ctypes signatures of sigs, then the library's
+    <prefix>_version() checked against abi, since the structs carry no size field and a library of another layout must not be
+    called.  check(rc) raises RpccError with the library's <prefix>_last_error() text."""
+
+    def __init__(self, name, path, prefix, sigs, abi):
+        self.name, self.path, self.prefix, self.sigs, self.abi = name, path, prefix, sigs, abi
+        self._h = None
+
+    def exported_symbols(self):
+        return sorted(self.sigs)
+
+    def lib(self):
+        if self._h is None:
+            if not os.path.exists(self.path):
+                raise RpccError("%s.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`"
+                                % (self.name, self.path))
+            h = C.CDLL(self.path)
+            for name, (res, args) in self.sigs.items():
+                fn = getattr(h, name)
+                fn.restype = res
+                fn.argtypes = args
+            version = getattr(h, self.prefix + "_version")()
+            if version != self.abi:
+                raise RpccError("%s.so (%s) reports interface version %d, this binding needs %d (stale build: rebuild with "
+                                "`python -c 'import __graft_entry__ as g; g.build()'`)" % (self.name, self.path, version, self.abi))
+            self._h = h
+        return self._h
+
+    def check(self, rc):
+        if rc != 0:
+            raise RpccError("%s: %s (code %d)" % (self.name, getattr(self.lib(), self.prefix + "_last_error")().decode(), rc))
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RpccError("librpcc_hip.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`"
-                            % LIB_PATH)
-        h = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        if h.rpcc_version() != ABI_VERSION:   # the structs carry no size field: a library of another layout must not be called
-            raise RpccError("librpcc_hip.so (%s) reports interface version %d, this binding needs %d (stale build: rebuild with "
-                            "`python -c 'import __graft_entry__ as g; g.build()'`)" % (LIB_PATH, h.rpcc_version(), ABI_VERSION))
-        _lib = h
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise RpccError("librpcc_hip: %s (code %d)" % (lib().rpcc_last_error().decode(), rc))
+_hip = Binding("librpcc_hip", LIB_PATH, "rpcc", _SIGS, ABI_VERSION)
+lib, check, exported_symbols = _hip.lib, _hip.check, _hip.exported_symbols
 
 
 def ptr(t):

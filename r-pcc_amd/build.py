@@ -9,17 +9,19 @@ DEPS = [os.path.join(_HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(_
 LIB = os.path.join(_HERE, "lib", "librpcc_hip.so")
 HOST_SRC = os.path.join(_HERE, "csrc", "rpcc_host.c")
 HOST_LIB = os.path.join(_HERE, "lib", "librpcc_host.so")
-# librpcc_eval.so (reconstruction metrics, include/rpcc_eval.h): a library of its own, so that neither DEPS nor
-# source_digest() -- the compression library's identity -- changes with it.
-EVAL_SRC = os.path.join(_HERE, "csrc_eval", "eval_kernels.hip")
-EVAL_DEPS = [os.path.join(_HERE, "csrc_eval", f) for f in sorted(os.listdir(os.path.join(_HERE, "csrc_eval")))] + \
-            [os.path.join(os.path.dirname(_HERE), "include", "rpcc_eval.h")]
-EVAL_LIB = os.path.join(_HERE, "lib", "librpcc_eval.so")
-# librpcc_seg.so (DBSCAN segmentation, include/rpcc_seg.h): a library of its own for the same reason.
-SEG_SRC = os.path.join(_HERE, "csrc_seg", "dbscan_kernels.hip")
-SEG_DEPS = [os.path.join(_HERE, "csrc_seg", f) for f in sorted(os.listdir(os.path.join(_HERE, "csrc_seg")))] + \
-           [os.path.join(os.path.dirname(_HERE), "include", "rpcc_seg.h")]
-SEG_LIB = os.path.join(_HERE, "lib", "librpcc_seg.so")
+
+
+def _side_library(subdir, src, header, lib):
+    """(src, deps, lib) of a HIP library of its own beside librpcc_hip.so: its directory, its public header and csrc_tile/ (the
+    tile preparation it shares with the other side library), so that neither DEPS nor source_digest() -- the compression
+    library's identity -- changes with it."""
+    deps = [os.path.join(_HERE, d, f) for d in (subdir, "csrc_tile") for f in sorted(os.listdir(os.path.join(_HERE, d)))]
+    return (os.path.join(_HERE, subdir, src), deps + [os.path.join(os.path.dirname(_HERE), "include", header)],
+            os.path.join(_HERE, "lib", lib))
+
+
+EVAL_SRC, EVAL_DEPS, EVAL_LIB = _side_library("csrc_eval", "eval_kernels.hip", "rpcc_eval.h", "librpcc_eval.so")   # reconstruction metrics
+SEG_SRC, SEG_DEPS, SEG_LIB = _side_library("csrc_seg", "dbscan_kernels.hip", "rpcc_seg.h", "librpcc_seg.so")     # DBSCAN segmentation
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into

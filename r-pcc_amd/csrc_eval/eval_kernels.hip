@@ -1,37 +1,19 @@
 // eval_kernels.hip -- librpcc_eval.so: reconstruction-quality metrics (include/rpcc_eval.h) for gfx950.
 //
-// Per call and cloud, four small kernels prepare the frame (tile_box, row_count, row_scan, rank): validity, the rank of
+// Per call and cloud, four small kernels prepare the frame (tile_box, row_count, scan, rank): validity, the rank of
 // every valid pixel in row-major order, the pixel of every rank, and per 8x32-pixel tile the bounding box of its valid
 // points and their count.  search_kernel then runs one workgroup of 256 threads per (query tile, frame), one query per
 // lane: exact nearest neighbour (NnState) or the 12 nearest within r (KnnState, followed by the fp64 covariance and its
 // eigenvector).  The metrics entry carries cloud 1's normals over to cloud 2 with fixed-point atomics and reduces every
 // per-point term of a frame in fp64 in a fixed order (partial sums per chunk, then one pass over the chunks).
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-
 #include "../../include/rpcc_eval.h"
+#include "../csrc_tile/tiles.h"
 
-#define EV_TR 8       // tile rows
-#define EV_TC 32      // tile columns (8 x 32 = 256 pixels: the FPS tile of fps_kernels.h)
-#define EV_LIST 1024  // target tiles tested per round of the tile list (any table size: the rounds cover it)
+static_assert(RPCC_EVAL_ERR_ARG == TILE_ERR_ARG && RPCC_EVAL_ERR_HIP == TILE_ERR_HIP && RPCC_EVAL_MAX_BATCH == TILE_MAX_BATCH &&
+                  RPCC_EVAL_MAX_PIXELS == TILE_MAX_PIXELS,
+              "rpcc_eval.h and tiles.h disagree");
+
 #define EV_CHUNK 4096 // points per workgroup of the metrics reduction
-
-static thread_local char g_err[512] = "";
-static int set_err(int code, const char *fmt, const char *a = "", const char *b = "") {
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
-    return code;
-}
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return set_err(RPCC_EVAL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define ARG_TRY(cond)                                                                   \
-    do {                                                                                \
-        if (!(cond)) return set_err(RPCC_EVAL_ERR_ARG, "bad argument: %s%s", #cond); \
-    } while (0)
-#define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
 
 extern "C" int rpcc_eval_version(void) { return RPCC_EVAL_ABI_VERSION; }
 extern "C" const char *rpcc_eval_last_error(void) { return g_err; }
@@ -51,121 +33,25 @@ struct Cloud {
 
 __device__ __forceinline__ bool valid3(float x, float y, float z) { return ((x + y) + z) != 0.f; }
 
-__device__ __forceinline__ float dist3(float qx, float qy, float qz, float px, float py, float pz) {
-    const float dx = qx - px, dy = qy - py, dz = qz - pz;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
-
-// Lower bound of dist3 between any point of box Q = [qlo, qhi] and any point of box S = [lo, hi] (a query point: qlo = qhi).
-// Per axis the gap is ONE rounded subtraction of box faces: for q in Q and p in S with qhi < lo, q - p <= qhi - lo < 0, and
-// rounding is monotone, so |fl(q - p)| >= fl(lo - qhi); likewise fl(qlo - hi) when qlo > hi; 0 when the extents overlap.
-// Squares and the two sums are monotone in their (non-negative) operands and are evaluated in the same order as dist3, so
-// bound <= dist3(q, p) for every pair, bit for bit.  A tile is therefore skipped only when bound > best, never at equality
-// (a tile at equality may hold an equal distance with a lower rank).
-__device__ __forceinline__ float box_bound(float3 qlo, float3 qhi, float4 lo, float4 hi) {
-    const float gx = fmaxf(fmaxf(lo.x - qhi.x, qlo.x - hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(lo.y - qhi.y, qlo.y - hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(lo.z - qhi.z, qlo.z - hi.z), 0.f);
-    return ((gx * gx) + (gy * gy)) + (gz * gz);
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-// Exclusive scan of one flag per thread over a 256-thread block; returns the flag's offset, *total = the block's count.
-__device__ __forceinline__ int block_scan_flag(bool f, int *s_w, int *total) {
-    const unsigned long long m = __ballot(f);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[w] = __popcll(m);
-    __syncthreads();
-    int off = 0;
-    for (int k = 0; k < w; ++k) off += s_w[k];
-    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
-    return off + in_wave;
-}
-
 // ------------------------------------------------------------------------------------------------
 // preparation: tile boxes, row counts, row offsets, ranks
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void tile_box_kernel(const float *__restrict__ pts, int H, int W, int ntc, int T,
-                                                       float4 *__restrict__ tiles) {
-    const int t = blockIdx.x, b = blockIdx.y;
-    const size_t P = (size_t)H * W;
-    const int row = (t / ntc) * EV_TR + (threadIdx.x >> 5), col = (t % ntc) * EV_TC + (threadIdx.x & 31);
-    float x = 0.f, y = 0.f, z = 0.f;
-    bool v = false;
-    if (row < H && col < W) {
-        const float *p = pts + ((size_t)b * P + (size_t)row * W + col) * 3;
-        x = p[0], y = p[1], z = p[2];
-        v = valid3(x, y, z);
+// tile_box_kernel's loader and row_count_kernel's predicate: a pixel of the cloud f32 [B,H,W,3] that holds a point.
+struct LoadPoint {
+    const float *pts;
+    __device__ bool operator()(size_t i, float3 &p) const {
+        const float *q = pts + i * 3;
+        p = make_float3(q[0], q[1], q[2]);
+        return valid3(p.x, p.y, p.z);
     }
-    float lx = v ? x : INFINITY, ly = v ? y : INFINITY, lz = v ? z : INFINITY;
-    float hx = v ? x : -INFINITY, hy = v ? y : -INFINITY, hz = v ? z : -INFINITY;
-    lx = wave_min(lx), ly = wave_min(ly), lz = wave_min(lz);
-    hx = wave_max(hx), hy = wave_max(hy), hz = wave_max(hz);
-    const int cnt = __popcll(__ballot(v));
-    __shared__ float s[4][6];
-    __shared__ int sc[4];
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s[w][0] = lx, s[w][1] = ly, s[w][2] = lz, s[w][3] = hx, s[w][4] = hy, s[w][5] = hz;
-        sc[w] = cnt;
+};
+struct IsPoint {
+    const float *pts;
+    __device__ bool operator()(int b, int h, int x, int H, int W) const {
+        const float *row = pts + ((size_t)b * H + h) * (size_t)W * 3;
+        return valid3(row[3 * x], row[3 * x + 1], row[3 * x + 2]);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            lx = fminf(lx, s[k][0]), ly = fminf(ly, s[k][1]), lz = fminf(lz, s[k][2]);
-            hx = fmaxf(hx, s[k][3]), hy = fmaxf(hy, s[k][4]), hz = fmaxf(hz, s[k][5]);
-        }
-        float4 *o = tiles + ((size_t)b * T + t) * 2;
-        o[0] = make_float4(lx, ly, lz, __int_as_float(sc[0] + sc[1] + sc[2] + sc[3]));
-        o[1] = make_float4(hx, hy, hz, 0.f);
-    }
-}
-
-__global__ __launch_bounds__(256) void row_count_kernel(const float *__restrict__ pts, int H, int W, int32_t *__restrict__ rowcnt) {
-    const int h = blockIdx.x, b = blockIdx.y;
-    const float *row = pts + ((size_t)b * H + h) * (size_t)W * 3;
-    int c = 0;
-    for (int x = threadIdx.x; x < W; x += 256) c += valid3(row[3 * x], row[3 * x + 1], row[3 * x + 2]) ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    __shared__ int s[4];
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) rowcnt[(size_t)b * H + h] = s[0] + s[1] + s[2] + s[3];
-}
-
-// One workgroup per frame: exclusive prefix of the row counts, and the frame's point count.
-__global__ __launch_bounds__(256) void row_scan_kernel(const int32_t *__restrict__ rowcnt, int H, int32_t *__restrict__ rowoff,
-                                                       int32_t *__restrict__ n) {
-    const int b = blockIdx.x;
-    __shared__ int s_v[256];
-    int base = 0;
-    for (int h0 = 0; h0 < H; h0 += 256) {
-        const int h = h0 + threadIdx.x;
-        const int v = h < H ? rowcnt[(size_t)b * H + h] : 0;
-        s_v[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {   // Hillis-Steele inclusive scan
-            const int a = threadIdx.x >= o ? s_v[threadIdx.x - o] : 0;
-            __syncthreads();
-            s_v[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (h < H) rowoff[(size_t)b * H + h] = base + s_v[threadIdx.x] - v;
-        base += s_v[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) n[2 * b] = base;
-}
+};
 
 __global__ __launch_bounds__(256) void rank_kernel(const float *__restrict__ pts, int H, int W, const int32_t *__restrict__ rowoff,
                                                    int32_t *__restrict__ rank, int32_t *__restrict__ pix) {
@@ -322,10 +208,11 @@ __device__ __forceinline__ void empty_target(const KnnOut &, size_t, int) {}   /
 
 // One workgroup per (query tile, frame); lane l holds the query pixel (row 8*tr + l/32, column 32*tc + l%32).
 //   1. seed: the target tile at the same position (the clouds share pixels: usually the answer already);
-//   2. rounds of up to EV_LIST target tiles: keep those whose box bound to the query tile's box is <= the largest lane
+//   2. rounds of up to TILE_LIST target tiles: keep those whose box bound to the query tile's box is <= the largest lane
 //      bound, stage each kept tile's points in LDS, and let every lane whose own point-to-box bound is <= its bound scan them.
-// Brute force: every tile, no bound.  The result is the minimum of (distance, pixel) over the scanned candidates, which
-// does not depend on the order the tiles are visited in: pruned and brute force agree bit for bit.
+// A tile is skipped only when its box_bound > the bound, never at equality (a tile at equality may hold an equal distance with
+// a lower rank).  Brute force: every tile, no bound.  The result is the minimum of (distance, pixel) over the scanned
+// candidates, which does not depend on the order the tiles are visited in: pruned and brute force agree bit for bit.
 template <class State, class Out>
 __global__ __launch_bounds__(256) void search_kernel(Cloud Q, Cloud S, int H, int W, int ntc, int T, int brute, float r2, Out out,
                                                      int32_t *visits) {
@@ -336,7 +223,7 @@ __global__ __launch_bounds__(256) void search_kernel(Cloud Q, Cloud S, int H, in
     if (__float_as_int(qlo4.w) == 0) return;   // no query in this tile (uniform over the block)
     const float4 *stab = S.tiles + (size_t)b * T * 2;
     const float *spts = S.pts + fb * 3;
-    const int row = (t0 / ntc) * EV_TR + (tid >> 5), col = (t0 % ntc) * EV_TC + (tid & 31);
+    const int row = (t0 / ntc) * TILE_R + (tid >> 5), col = (t0 % ntc) * TILE_C + (tid & 31);
     const bool in_img = row < H && col < W;
     const int qp = in_img ? row * W + col : 0;
     const int qrank = in_img ? Q.rank[fb + qp] : -1;
@@ -355,13 +242,13 @@ __global__ __launch_bounds__(256) void search_kernel(Cloud Q, Cloud S, int H, in
     int nvis = 0;
 
     __shared__ float4 s_pts[256];
-    __shared__ int s_list[EV_LIST];
+    __shared__ int s_list[TILE_LIST];
     __shared__ int s_cnt;
     __shared__ unsigned s_maxb;
 
     auto scan_tile = [&](int t, bool check) {
         __syncthreads();   // the previous tile's readers are done
-        const int sr = (t / ntc) * EV_TR + (tid >> 5), sc = (t % ntc) * EV_TC + (tid & 31);
+        const int sr = (t / ntc) * TILE_R + (tid >> 5), sc = (t % ntc) * TILE_C + (tid & 31);
         float4 v = make_float4(NAN, NAN, NAN, 0.f);   // no point: NaN coordinates, a distance no comparison accepts
         if (sr < H && sc < W) {
             const int sp = sr * W + sc;
@@ -386,14 +273,14 @@ __global__ __launch_bounds__(256) void search_kernel(Cloud Q, Cloud S, int H, in
 
     scan_tile(t0, false);
     const float3 qlo = make_float3(qlo4.x, qlo4.y, qlo4.z), qhi = make_float3(qhi4.x, qhi4.y, qhi4.z);
-    for (int c0 = 0; c0 < T; c0 += EV_LIST) {
+    for (int c0 = 0; c0 < T; c0 += TILE_LIST) {
         __syncthreads();   // every lane has read s_cnt / s_list of the previous round
         if (tid == 0) s_cnt = 0, s_maxb = 0u;
         __syncthreads();
         if (act) atomicMax(&s_maxb, __float_as_uint(st.bound()));   // bounds are >= 0 (or +inf): their bits order as unsigned
         __syncthreads();
         const float maxb = __uint_as_float(s_maxb);
-        const int c1 = min(T, c0 + EV_LIST);
+        const int c1 = min(T, c0 + TILE_LIST);
         for (int t = c0 + tid; t < c1; t += 256) {
             if (t == t0) continue;
             bool keep = brute != 0;
@@ -509,22 +396,16 @@ __global__ void finalize_kernel(const int32_t *__restrict__ n1s, const int32_t *
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
     int H, W, ntc, T, nch;
     size_t P, off_rank[2], off_pix[2], off_rowcnt[2], off_rowoff[2], off_n, off_tiles[2], off_acc, off_cnt, off_part, total;
 };
 
-static bool shape_ok(int B, int H, int W) {
-    return B > 0 && B <= RPCC_EVAL_MAX_BATCH && H > 0 && W > 0 && (long long)H * W <= RPCC_EVAL_MAX_PIXELS;
-}
-
 static Layout layout(int B, int H, int W) {
     Layout L;
     L.H = H, L.W = W, L.P = (size_t)H * W;
-    L.ntc = (W + EV_TC - 1) / EV_TC;
-    L.T = ((H + EV_TR - 1) / EV_TR) * L.ntc;
+    L.ntc = tile_cols(W);
+    L.T = tile_count(H, W);
     L.nch = (int)((L.P + EV_CHUNK - 1) / EV_CHUNK);
     size_t o = 0;
     for (int c = 0; c < 2; ++c) {
@@ -555,9 +436,9 @@ static Cloud cloud(const Layout &L, char *ws, int c, const float *pts) {
 }
 
 static int prepare(const Layout &L, const Cloud &C, int B, hipStream_t st) {
-    tile_box_kernel<<<dim3(L.T, B), 256, 0, st>>>(C.pts, L.H, L.W, L.ntc, L.T, C.tiles);
-    row_count_kernel<<<dim3(L.H, B), 256, 0, st>>>(C.pts, L.H, L.W, C.rowcnt);
-    row_scan_kernel<<<B, 256, 0, st>>>(C.rowcnt, L.H, C.rowoff, C.n);
+    tile_box_kernel<<<dim3(L.T, B), 256, 0, st>>>(LoadPoint{C.pts}, L.H, L.W, L.ntc, L.T, C.tiles);
+    row_count_kernel<<<dim3(L.H, B), 256, 0, st>>>(IsPoint{C.pts}, L.H, L.W, C.rowcnt);
+    scan_kernel<2><<<B, 256, 0, st>>>(C.rowcnt, L.H, C.rowoff, C.n);
     rank_kernel<<<dim3(L.H, B), 256, 0, st>>>(C.pts, L.H, L.W, C.rowoff, C.rank, C.pix);
     LAUNCH_CHECK();
     return 0;

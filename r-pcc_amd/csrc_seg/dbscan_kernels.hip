@@ -14,36 +14,18 @@
 // Between them: the origin point's core flag, root compression, and cluster numbers by an exclusive scan of the roots in
 // rank order.  Components, roots and minima do not depend on the order anything is visited in, so pruned and brute-force
 // results are equal bit for bit.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-
 #include "../../include/rpcc_seg.h"
+#include "../csrc_tile/tiles.h"
 
-#define SG_TR 8        // tile rows
-#define SG_TC 32       // tile columns (8 x 32 = 256 pixels, one per lane)
-#define SG_LIST 1024   // candidate tiles kept per round of the tile list (any table size: the rounds cover it)
+static_assert(RPCC_SEG_ERR_ARG == TILE_ERR_ARG && RPCC_SEG_ERR_HIP == TILE_ERR_HIP && RPCC_SEG_MAX_BATCH == TILE_MAX_BATCH &&
+                  RPCC_SEG_MAX_PIXELS == TILE_MAX_PIXELS,
+              "rpcc_seg.h and tiles.h disagree");
+
 #define SG_CHUNK 4096  // ranks per workgroup of the cluster numbering (16 steps of 256)
 #define SG_NFR 8       // ints per frame: n, Z, o0, real points near the origin, clusters, capped, origin core, spare
 
 enum { FR_N = 0, FR_Z, FR_O0, FR_ONEAR, FR_NCL, FR_CAP, FR_OCORE };
 enum { MODE_CORE = 0, MODE_UNION = 1, MODE_BORDER = 2 };
-
-static thread_local char g_err[512] = "";
-static int set_err(int code, const char *fmt, const char *a = "", const char *b = "") {
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
-    return code;
-}
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return set_err(RPCC_SEG_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define ARG_TRY(cond)                                                                  \
-    do {                                                                               \
-        if (!(cond)) return set_err(RPCC_SEG_ERR_ARG, "bad argument: %s%s", #cond); \
-    } while (0)
-#define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
 
 extern "C" int rpcc_seg_version(void) { return RPCC_SEG_ABI_VERSION; }
 extern "C" const char *rpcc_seg_last_error(void) { return g_err; }
@@ -55,11 +37,6 @@ extern "C" const char *rpcc_seg_last_error(void) { return g_err; }
 __device__ __forceinline__ bool exact_nb(float px, float py, float pz, float qx, float qy, float qz, double e2) {
     const double dx = (double)px - (double)qx, dy = (double)py - (double)qy, dz = (double)pz - (double)qz;
     return ((dx * dx) + (dy * dy)) + (dz * dz) < e2;
-}
-
-__device__ __forceinline__ float dist3(float px, float py, float pz, float qx, float qy, float qz) {
-    const float dx = px - qx, dy = py - qy, dz = pz - qz;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
 }
 
 // fp32 screen.  Let D be the exact (real-number) squared distance of the two fp32 points.  In fp32 a term dx*dx is
@@ -77,44 +54,11 @@ __device__ __forceinline__ bool screen_nb(float px, float py, float pz, float qx
     return exact_nb(px, py, pz, qx, qy, qz, e2);
 }
 
-// Lower bound of dist3 between a point and any point of the box [lo, hi] (as eval_kernels.hip's box_bound): per axis one
-// rounded subtraction of box faces, monotone under rounding, squares and sums in dist3's order, so the bound is <= d2f
-// of every pair.  A tile is skipped only when the bound exceeds the screen's hi: every pair then fails.
-__device__ __forceinline__ float box_bound(float3 qlo, float3 qhi, float4 lo, float4 hi) {
-    const float gx = fmaxf(fmaxf(lo.x - qhi.x, qlo.x - hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(lo.y - qhi.y, qlo.y - hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(lo.z - qhi.z, qlo.z - hi.z), 0.f);
-    return ((gx * gx) + (gy * gy)) + (gz * gz);
-}
-
 // fp64 non-ground test: |double(r) - r_plane| > 0.5, r_plane = -d / ((a*A + b*B) + c*C); NaN is ground.
 __device__ __forceinline__ bool nonground(float r, const float *t, const double *g) {
     const double den = ((double)t[0] * g[0] + (double)t[1] * g[1]) + (double)t[2] * g[2];
     const double res = (double)r - (-g[3] / den);
     return fabs(res) > 0.5;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-// Exclusive scan of one flag per thread over a 256-thread block; returns the flag's offset, *total = the block's count.
-__device__ __forceinline__ int block_scan_flag(bool f, int *s_w, int *total) {
-    const unsigned long long m = __ballot(f);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[w] = __popcll(m);
-    __syncthreads();
-    int off = 0;
-    for (int k = 0; k < w; ++k) off += s_w[k];
-    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
-    return off + in_wave;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -167,43 +111,14 @@ __global__ void init_kernel(int32_t *__restrict__ frame, int32_t *__restrict__ m
     if (stats && k < RPCC_SEG_NSTATS) stats[b * RPCC_SEG_NSTATS + k] = 0ull;
 }
 
-__global__ __launch_bounds__(256) void row_count_kernel(const float *__restrict__ ri, const float *__restrict__ tm,
-                                                        const double *__restrict__ ground, int H, int W, int32_t *__restrict__ rowcnt) {
-    const int h = blockIdx.x, b = blockIdx.y;
-    const float *row = ri + ((size_t)b * H + h) * W;
-    const double *g = ground + 4 * b;
-    int c = 0;
-    for (int x = threadIdx.x; x < W; x += 256) c += nonground(row[x], tm + ((size_t)h * W + x) * 3, g) ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    __shared__ int s[4];
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) rowcnt[(size_t)b * H + h] = s[0] + s[1] + s[2] + s[3];
-}
-
-// One workgroup per frame: exclusive prefix of len counts, the total to *out (frame b's slot).
-__global__ __launch_bounds__(256) void scan_kernel(const int32_t *__restrict__ cnt, int len, int32_t *__restrict__ off,
-                                                   int32_t *__restrict__ frame, int slot) {
-    const int b = blockIdx.x;
-    __shared__ int s_v[256];
-    int base = 0;
-    for (int h0 = 0; h0 < len; h0 += 256) {
-        const int h = h0 + threadIdx.x;
-        const int v = h < len ? cnt[(size_t)b * len + h] : 0;
-        s_v[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {   // Hillis-Steele inclusive scan
-            const int a = threadIdx.x >= o ? s_v[threadIdx.x - o] : 0;
-            __syncthreads();
-            s_v[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (h < len) off[(size_t)b * len + h] = base + s_v[threadIdx.x] - v;
-        base += s_v[255];
-        __syncthreads();
+// row_count_kernel's predicate: a non-ground pixel.
+struct IsNonground {
+    const float *ri, *tm;
+    const double *ground;
+    __device__ bool operator()(int b, int h, int x, int H, int W) const {
+        return nonground(ri[((size_t)b * H + h) * W + x], tm + ((size_t)h * W + x) * 3, ground + 4 * b);
     }
-    if (threadIdx.x == 0) frame[b * SG_NFR + slot] = base;
-}
+};
 
 // pts[b][p] = (x, y, z, tag): tag = rank of a real point, -1 ground, -2 zero-range non-ground (the origin point).
 __global__ __launch_bounds__(256) void rank_kernel(const float *__restrict__ ri, const float *__restrict__ tm,
@@ -246,38 +161,15 @@ __global__ __launch_bounds__(256) void rank_kernel(const float *__restrict__ ri,
     }
 }
 
-// Per tile: box of the real points, their count in lo.w.
-__global__ __launch_bounds__(256) void tile_box_kernel(const float4 *__restrict__ pts, int H, int W, int ntc, int T,
-                                                       float4 *__restrict__ tiles) {
-    const int t = blockIdx.x, b = blockIdx.y;
-    const size_t P = (size_t)H * W;
-    const int row = (t / ntc) * SG_TR + (threadIdx.x >> 5), col = (t % ntc) * SG_TC + (threadIdx.x & 31);
-    float4 p = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-    if (row < H && col < W) p = pts[(size_t)b * P + (size_t)row * W + col];
-    const bool v = __float_as_int(p.w) >= 0;
-    float lx = v ? p.x : INFINITY, ly = v ? p.y : INFINITY, lz = v ? p.z : INFINITY;
-    float hx = v ? p.x : -INFINITY, hy = v ? p.y : -INFINITY, hz = v ? p.z : -INFINITY;
-    lx = wave_min(lx), ly = wave_min(ly), lz = wave_min(lz);
-    hx = wave_max(hx), hy = wave_max(hy), hz = wave_max(hz);
-    const int cnt = __popcll(__ballot(v));
-    __shared__ float s[4][6];
-    __shared__ int sc[4];
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s[w][0] = lx, s[w][1] = ly, s[w][2] = lz, s[w][3] = hx, s[w][4] = hy, s[w][5] = hz;
-        sc[w] = cnt;
+// tile_box_kernel's loader: the real points of pts (tag >= 0).
+struct LoadReal {
+    const float4 *pts;
+    __device__ bool operator()(size_t i, float3 &p) const {
+        const float4 q = pts[i];
+        p = make_float3(q.x, q.y, q.z);
+        return __float_as_int(q.w) >= 0;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            lx = fminf(lx, s[k][0]), ly = fminf(ly, s[k][1]), lz = fminf(lz, s[k][2]);
-            hx = fmaxf(hx, s[k][3]), hy = fmaxf(hy, s[k][4]), hz = fmaxf(hz, s[k][5]);
-        }
-        float4 *o = tiles + ((size_t)b * T + t) * 2;
-        o[0] = make_float4(lx, ly, lz, __int_as_float(sc[0] + sc[1] + sc[2] + sc[3]));
-        o[1] = make_float4(hx, hy, hz, 0.f);
-    }
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // search
@@ -308,7 +200,7 @@ __global__ __launch_bounds__(256) void search_kernel(SegWs S, SegParams prm, uns
     int32_t *fr = S.frame + b * SG_NFR;
     const int n = fr[FR_N], Z = fr[FR_Z], o0 = fr[FR_O0];
     const bool ocore = fr[FR_OCORE] != 0;
-    const int row = (t0 / ntc) * SG_TR + (tid >> 5), col = (t0 % ntc) * SG_TC + (tid & 31);
+    const int row = (t0 / ntc) * TILE_R + (tid >> 5), col = (t0 % ntc) * TILE_C + (tid & 31);
     float4 q = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
     if (row < H && col < W) q = S.pts[fb + (size_t)row * W + col];
     const int qr = __float_as_int(q.w);
@@ -334,7 +226,7 @@ __global__ __launch_bounds__(256) void search_kernel(SegWs S, SegParams prm, uns
     unsigned long long npair = 0, ntile = 0;
 
     __shared__ float4 s_pts[256];
-    __shared__ int s_list[SG_LIST];
+    __shared__ int s_list[TILE_LIST];
     __shared__ int s_cnt, s_maxb;
 
     // pending: the lane still needs candidates (CORE: fewer than min_points found so far; brute force never stops early)
@@ -342,7 +234,7 @@ __global__ __launch_bounds__(256) void search_kernel(SegWs S, SegParams prm, uns
 
     auto scan_tile = [&](int t) {
         __syncthreads();   // the previous tile's readers are done
-        const int sr = (t / ntc) * SG_TR + (tid >> 5), sc = (t % ntc) * SG_TC + (tid & 31);
+        const int sr = (t / ntc) * TILE_R + (tid >> 5), sc = (t % ntc) * TILE_C + (tid & 31);
         float4 v = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));   // tag < 0: no candidate
         if (sr < H && sc < W) {
             const float4 p = S.pts[fb + (size_t)sr * W + sc];
@@ -356,7 +248,7 @@ __global__ __launch_bounds__(256) void search_kernel(SegWs S, SegParams prm, uns
         __syncthreads();
         if (!pending()) return;
         if (!brute) {
-            const float4 lo = tab[2 * t], hi = tab[2 * t + 1];
+            const float4 lo = tab[2 * t], hi = tab[2 * t + 1];   // a bound above the screen's hi: every pair of the tile fails
             if (box_bound(make_float3(q.x, q.y, q.z), make_float3(q.x, q.y, q.z), lo, hi) > prm.hi) return;
             if (MODE == MODE_BORDER && S.tmin[(size_t)b * T + t] >= best) return;
         }
@@ -380,7 +272,7 @@ __global__ __launch_bounds__(256) void search_kernel(SegWs S, SegParams prm, uns
 
     scan_tile(t0);   // the co-located tile first: CORE usually stops there
     const float3 qlo = make_float3(qlo4.x, qlo4.y, qlo4.z), qhi = make_float3(qhi4.x, qhi4.y, qhi4.z);
-    for (int c0 = 0; c0 < T; c0 += SG_LIST) {
+    for (int c0 = 0; c0 < T; c0 += TILE_LIST) {
         __syncthreads();   // every lane has read s_cnt / s_list of the previous round
         if (tid == 0) s_cnt = 0, s_maxb = -1;
         __syncthreads();
@@ -388,7 +280,7 @@ __global__ __launch_bounds__(256) void search_kernel(SegWs S, SegParams prm, uns
         __syncthreads();
         const int maxb = s_maxb;
         if (maxb < 0) break;   // no lane needs more candidates (uniform: read after the barrier)
-        const int c1 = min(T, c0 + SG_LIST);
+        const int c1 = min(T, c0 + TILE_LIST);
         for (int t = c0 + tid; t < c1; t += 256) {
             if (t == t0) continue;
             bool keep = brute;
@@ -492,7 +384,7 @@ __global__ __launch_bounds__(256) void tile_min_kernel(const float4 *__restrict_
                                                        int32_t *__restrict__ tmin) {
     const int t = blockIdx.x, b = blockIdx.y;
     const size_t P = (size_t)H * W;
-    const int row = (t / ntc) * SG_TR + (threadIdx.x >> 5), col = (t % ntc) * SG_TC + (threadIdx.x & 31);
+    const int row = (t / ntc) * TILE_R + (threadIdx.x >> 5), col = (t % ntc) * TILE_C + (threadIdx.x & 31);
     int m = 0x7fffffff;
     if (row < H && col < W) {
         const int r = __float_as_int(pts[(size_t)b * P + (size_t)row * W + col].w);
@@ -533,22 +425,16 @@ __global__ void finish_kernel(const int32_t *__restrict__ frame, int32_t *__rest
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
     int ntc, T, nch;
     size_t P, off_pts, off_tiles, off_tmin, off_par, off_cl, off_rowcnt, off_rowoff, off_chcnt, off_choff, off_frame, total;
 };
 
-static bool shape_ok(int B, int H, int W) {
-    return B > 0 && B <= RPCC_SEG_MAX_BATCH && H > 0 && W > 0 && (long long)H * W <= RPCC_SEG_MAX_PIXELS;
-}
-
 static Layout layout(int B, int H, int W) {
     Layout L;
     L.P = (size_t)H * W;
-    L.ntc = (W + SG_TC - 1) / SG_TC;
-    L.T = ((H + SG_TR - 1) / SG_TR) * L.ntc;
+    L.ntc = tile_cols(W);
+    L.T = tile_count(H, W);
     L.nch = (int)((L.P + SG_CHUNK - 1) / SG_CHUNK);
     size_t o = 0;
     L.off_pts = o, o += al((size_t)B * L.P * sizeof(float4));
@@ -602,16 +488,16 @@ extern "C" int rpcc_seg_dbscan(const float *ri, const float *tm, const double *g
     const unsigned pblocks = (unsigned)((L.P + 255) / 256);
     init_kernel<<<B, 64, 0, st>>>(S.frame, max_label, st64);
     HIP_TRY(hipMemsetAsync(S.par, 0xff, (size_t)B * L.P * 4, st));
-    row_count_kernel<<<dim3(H, B), 256, 0, st>>>(ri, tm, ground, H, W, rowcnt);
-    scan_kernel<<<B, 256, 0, st>>>(rowcnt, H, rowoff, S.frame, FR_N);
+    row_count_kernel<<<dim3(H, B), 256, 0, st>>>(IsNonground{ri, tm, ground}, H, W, rowcnt);
+    scan_kernel<SG_NFR><<<B, 256, 0, st>>>(rowcnt, H, rowoff, S.frame + FR_N);
     rank_kernel<<<dim3(H, B), 256, 0, st>>>(ri, tm, ground, H, W, rowoff, (float4 *)S.pts, S.frame);
-    tile_box_kernel<<<dim3(L.T, B), 256, 0, st>>>(S.pts, H, W, L.ntc, L.T, (float4 *)S.tiles);
+    tile_box_kernel<<<dim3(L.T, B), 256, 0, st>>>(LoadReal{S.pts}, H, W, L.ntc, L.T, (float4 *)S.tiles);
     search_kernel<MODE_CORE><<<dim3(L.T, B), 256, 0, st>>>(S, prm, st64);
     origin_kernel<<<B, 64, 0, st>>>(S.frame, S.par, L.P, min_points);
     search_kernel<MODE_UNION><<<dim3(L.T, B), 256, 0, st>>>(S, prm, st64);
     compress_kernel<<<dim3(pblocks, B), 256, 0, st>>>(S.par, S.frame, L.P);
     root_count_kernel<<<dim3(L.nch, B), 256, 0, st>>>(S.par, S.frame, L.P, L.nch, chcnt);
-    scan_kernel<<<B, 256, 0, st>>>(chcnt, L.nch, choff, S.frame, FR_NCL);
+    scan_kernel<SG_NFR><<<B, 256, 0, st>>>(chcnt, L.nch, choff, S.frame + FR_NCL);
     root_number_kernel<<<dim3(L.nch, B), 256, 0, st>>>(S.par, S.frame, L.P, L.nch, choff, S.cl);
     core_label_kernel<<<dim3(pblocks, B), 256, 0, st>>>(S.par, S.frame, L.P, S.cl);
     tile_min_kernel<<<dim3(L.T, B), 256, 0, st>>>(S.pts, S.par, S.cl, H, W, L.ntc, L.T, (int32_t *)S.tmin);

@@ -60,6 +60,8 @@ def test_source_digest_unchanged_by_the_eval_library(built):
     assert b.source_digest() == before
     assert not any("csrc_eval" in d or d.endswith("rpcc_eval.h") for d in b.DEPS)
     assert os.path.exists(b.EVAL_LIB)
+    tiles = os.path.join(os.path.dirname(b.__file__), "csrc_tile", "tiles.h")   # shared with the other side library
+    assert tiles in b.EVAL_DEPS and tiles not in b.DEPS
 
 
 def test_numpy_reference_search_is_exact():

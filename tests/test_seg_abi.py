@@ -68,6 +68,8 @@ def test_source_digest_unchanged_by_the_seg_library(built):
     assert b.source_digest() == before
     assert not any("csrc_seg" in d or d.endswith("rpcc_seg.h") for d in b.DEPS)
     assert os.path.exists(b.SEG_LIB)
+    tiles = os.path.join(os.path.dirname(b.__file__), "csrc_tile", "tiles.h")   # shared with the other side library
+    assert tiles in b.SEG_DEPS and tiles not in b.DEPS
 
 
 @pytest.mark.parametrize("name", ["boundary_strict", "boundary_inside", "min_points_self", "border_lowest", "origin_keeps_number",

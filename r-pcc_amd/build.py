@@ -22,6 +22,7 @@ def _side_library(subdir, src, header, lib):
 
 EVAL_SRC, EVAL_DEPS, EVAL_LIB = _side_library("csrc_eval", "eval_kernels.hip", "rpcc_eval.h", "librpcc_eval.so")   # reconstruction metrics
 SEG_SRC, SEG_DEPS, SEG_LIB = _side_library("csrc_seg", "dbscan_kernels.hip", "rpcc_seg.h", "librpcc_seg.so")     # DBSCAN segmentation
+LZ4_SRC, LZ4_DEPS, LZ4_LIB = _side_library("csrc_lz4", "lz4_kernels.hip", "rpcc_lz4.h", "librpcc_lz4.so")        # LZ4 entropy back-end
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -77,6 +78,11 @@ def build_seg(force=False, verbose=False):
     return _hipcc(SEG_SRC, SEG_LIB, SEG_DEPS, force, verbose)
 
 
+def build_lz4(force=False, verbose=False):
+    """librpcc_lz4.so: the LZ4 encode / decode / container kernels (csrc_lz4/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(LZ4_SRC, LZ4_LIB, LZ4_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -84,6 +90,7 @@ def build(force=False, verbose=False):
         print("librpcc_host.so not built (%s): containers are packed by the interpreter's bz2 module" % e)  # takes the Python path
     build_eval(force, verbose)
     build_seg(force, verbose)
+    build_lz4(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

@@ -132,6 +132,11 @@ def pack_frames(basic_compressor, frames, uniform=True):
             host = _lib.host_lib()     # not built / not loadable / stale: remembered by _lib, the Python path below gives the same bytes
         except _lib.RpccError:
             host = None
+    if basic_compressor.lz4_batched() and frames:   # every array of the chunk in one dumps_many (one launch)
+        keys = (() if uniform else ("salience_level",)) + _ORDER
+        blobs = basic_compressor._lz4().dumps_many([np.ascontiguousarray(od[k]) for od in frames for k in keys])
+        na = len(keys)
+        return [b"".join(struct.pack("i", len(b)) + b for b in blobs[i * na: (i + 1) * na]) for i in range(len(frames))]
     if host is None:
         return [pack_bitstream(basic_compressor.compress_dict(od), uniform=uniform) for od in frames]
     keys = (() if uniform else ("salience_level",)) + _ORDER
@@ -191,8 +196,8 @@ def decompress_point_cloud(compressed_data, basic_compressor, model_num, H, W):
 
 
 class BasicCompressor:
-    """utils/compress_utils.py:232-310.  bzip2 / deflate are stdlib; lz4 needs the lz4 package
-    (lz4==0.7.0 API in the reference), which this image does not ship."""
+    """utils/compress_utils.py:232-310.  bzip2 / deflate are stdlib; lz4 is the lz4 package (lz4==0.7.0 API in the reference)
+    where it is installed, else rpcc_amd.lz4_codec (the same dumps / loads forms, coded on the GPU)."""
 
     METHODS = ["lz4", "bzip2", "gzip", "deflate"]
 
@@ -209,10 +214,21 @@ class BasicCompressor:
         assert method_name in self.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate)"
         self.method_name = method_name
 
+    def lz4_batched(self):
+        """True when 'lz4' runs through rpcc_amd.lz4_codec, which codes a list of arrays in one launch."""
+        if self.method_name != "lz4":
+            return False
+        from . import lz4_codec
+        return self._lz4() is lz4_codec
+
     def compress_dict(self, data_dict):
+        if self.lz4_batched():
+            return dict(zip(data_dict, self._lz4().dumps_many([np.ascontiguousarray(v) for v in data_dict.values()])))
         return {k: self.compress(v) for k, v in data_dict.items()}
 
     def decompress_dict(self, data_dict):
+        if self.lz4_batched():
+            return dict(zip(data_dict, self._lz4().loads_many(list(data_dict.values()))))
         return {k: self.decompress(v) for k, v in data_dict.items()}
 
     def compress(self, np_array):
@@ -242,5 +258,6 @@ class BasicCompressor:
         try:
             import lz4
             return lz4
-        except ImportError as e:
-            raise RuntimeError("basic_compressor 'lz4' needs the lz4 package, which is not installed") from e
+        except ImportError:
+            from . import lz4_codec
+            return lz4_codec

@@ -89,8 +89,36 @@ class BatchCompressor:
         qp, qtot = ops.pack_payload(buf.q16, buf.nnz, capacity=npts)
         sp, stot = ops.pack_payload(seq.view(torch.int16), nseq)
         buf.in_flight = True    # until collect() has read it (_buffers)
-        return dict(n=n, buf=buf, bits=bits, nseq=nseq, sal=sal, qp=qp, qtot=qtot, sp=sp, stot=stot,
-                    stream=torch.cuda.current_stream(self.device), keep=(xyz, g, seq))
+        ctx = dict(n=n, buf=buf, bits=bits, nseq=nseq, sal=sal, qp=qp, qtot=qtot, sp=sp, stot=stot,
+                   stream=torch.cuda.current_stream(self.device), keep=(xyz, g, seq))
+        if self.bc.lz4_batched():
+            ctx["lz4"] = self._lz4_containers(n, buf, bits, nseq, sal, qp, sp)
+        return ctx
+
+    def _lz4_containers(self, B, buf, bits, nseq, sal, qp, sp):
+        """basic_compressor 'lz4' without the lz4 package: the batch's .rpcc containers are built in HBM (rpcc_lz4_encode over the
+        arrays where they lie, then rpcc_lz4_pack_containers) on the current stream.  -> (containers, frame offsets / lengths)."""
+        from . import lz4_codec
+        dev, K, P = self.device, buf.counts.shape[1], self.T.H * self.T.W
+        i64 = dict(dtype=torch.int64, device=dev)
+        nrow = ((buf.counts != 0).to(torch.int64) * torch.arange(1, K + 1, **i64)).amax(1)   # max(seg) + 1 (tools/compress.py:102)
+        nnz, ns = buf.nnz.to(torch.int64), nseq.to(torch.int64)
+        excl = lambda v: torch.cumsum(v, 0) - v
+        rows = torch.arange(B, **i64)
+        nb = bits.shape[1]
+        # per frame, in container order: (device address, bytes, host bound of the bytes)
+        cols = [(bits.data_ptr() + rows * nb, torch.full((B,), nb, **i64), nb),
+                (sp.data_ptr() + 2 * excl(ns), 2 * ns, 2 * P),
+                (buf.model.data_ptr() + rows * (K * 16), 16 * nrow, 16 * K),
+                (qp.data_ptr() + 2 * excl(nnz), 2 * nnz, 2 * P)]
+        if sal is not None:
+            cols.insert(0, (sal.data_ptr() + rows * K, nrow, K))
+        addr = torch.stack([c[0] for c in cols], 1).reshape(-1)
+        lens = torch.stack([c[1] for c in cols], 1).reshape(-1)
+        slots, dst_off, dst_len, _ = lz4_codec.encode_descriptors(addr, lens, [c[2] for c in cols] * B)
+        cap = int(slots.numel()) + 4 * len(cols) * B
+        out, frame = lz4_codec.pack_containers(slots, dst_off, dst_len, B, len(cols), cap)
+        return out, frame, (addr, lens, slots, dst_off, dst_len)
 
     def submit(self, frames, ground=None, frame_ids=None):
         """Device part of compress() on the current stream, nothing waited for.  -> a context for collect()."""
@@ -102,6 +130,8 @@ class BatchCompressor:
         pool: a concurrent.futures executor -- the frames' entropy coding then runs on its threads (bz2 / zlib / lz4
         release the GIL), like the reference's --workers ThreadPoolExecutor (tools/compress_datalist.py:202-206)."""
         buf = ctx["buf"]
+        if "lz4" in ctx:
+            return self._collect_lz4(ctx)
         try:
             ctx["stream"].synchronize()
             bits, nseq, sal = ctx["bits"], ctx["nseq"], ctx["sal"]
@@ -129,6 +159,20 @@ class BatchCompressor:
         chunk = lambda lo: pack_frames(self.bc, [assemble(b) for b in range(lo, min(lo + step, n))], uniform=self.uniform)
         parts = list(pool.map(chunk, range(0, n, step))) if pool is not None else [chunk(lo) for lo in range(0, n, step)]
         return [blob for part in parts for blob in part]
+
+    def _collect_lz4(self, ctx):
+        """The containers _lz4_containers built: the frames' places, then the containers in one copy."""
+        out, frame, _ = ctx["lz4"]
+        try:
+            ctx["stream"].synchronize()
+            fr = frame.cpu().numpy()
+        finally:
+            ctx["buf"].in_flight = False
+        n = ctx["n"]
+        if (fr[1, :n] < 0).any():
+            raise RuntimeError("rpcc_lz4: the containers of frames %s were not built" % np.flatnonzero(fr[1, :n] < 0).tolist())
+        h = out[: int((fr[0, :n] + fr[1, :n]).max()) if n else 0].cpu().numpy()
+        return [h[o: o + l].tobytes() for o, l in zip(fr[0, :n], fr[1, :n])]
 
     def discard(self, ctx):
         """Gives up a submit() whose results are not wanted (a caller that aborts a batch): waits for its stream -- the kernels may still

@@ -69,10 +69,10 @@ class QuantizationModule:
 
     def dequantize_residual(self, quantized_residual, seg_idx, salience_level=None):
         """utils/compress_utils.py:114-132 -> f32 [H,W,1] (decoder; on the device via rpcc_decode with a
-        zero model, so pred = 0 and rec = residual)."""
+        zero model, so pred = 0 and rec = residual; labels above 255: uint16 through rpcc_decode_wide)."""
         h, w = seg_idx.shape[:2]
-        seg = _dev(seg_idx, self.device, np.uint8).reshape(1, h, w)
         M = max(int(seg_idx.max()) - 1, 1)
+        seg = _dev(seg_idx, self.device, np.uint16 if ops.is_wide(M) else np.uint8).reshape(1, h, w)
         K = M + 2
         q = torch.zeros((1, h * w), dtype=torch.int16, device=self.device)
         qq = _dev(quantized_residual, self.device, np.int16)

@@ -4,7 +4,7 @@ scope."""
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 class ContourExtractor:
@@ -13,7 +13,9 @@ class ContourExtractor:
     @staticmethod
     def extract_contour(idx_map):
         """-> (contour_map int32 [H,W] of 0/1, idx_sequence int32 [n]) like contour_utils_cpp.extract_contour."""
-        seg = torch.from_numpy(np.ascontiguousarray(idx_map).astype(np.uint8)[None]).to(ContourExtractor.device)
+        a = np.ascontiguousarray(idx_map)
+        wide = a.size > 0 and int(a.max()) > 255     # labels above a byte: uint16 on the device (rpcc_contour_encode_wide)
+        seg = torch.from_numpy(a.astype(np.uint16 if wide else np.uint8)[None]).to(ContourExtractor.device)
         bits, seq, nseq = ops.contour_encode(seg)
         h, w = idx_map.shape
         cm = np.unpackbits(bits[0].cpu().numpy())[: h * w].reshape(h, w).astype(np.int32)
@@ -26,6 +28,9 @@ class ContourExtractor:
         dev = ContourExtractor.device
         bits = torch.from_numpy(np.packbits(np.ascontiguousarray(contour_map).astype(bool), axis=None)[None]).to(dev)
         seq = torch.zeros((1, h * w), dtype=torch.uint16, device=dev)
-        s = torch.from_numpy(np.ascontiguousarray(idx_sequence).astype(np.uint16))
+        sq = np.ascontiguousarray(idx_sequence).astype(np.uint16)
+        s = torch.from_numpy(sq)
         seq[0, : s.numel()] = s.to(dev)
-        return ops.contour_decode(bits, seq, h, w)[0].cpu().numpy().astype(np.int32)
+        # cluster_num = largest label - 1 picks the label width: uint16 (rpcc_contour_decode_wide) for labels above 255
+        M = min(max(int(sq.max()) - 1, 1), _lib.MAX_CLUSTERS_WIDE) if sq.size else ops.DEFAULT_CLUSTERS
+        return ops.contour_decode(bits, seq, h, w, M)[0].cpu().numpy().astype(np.int32)

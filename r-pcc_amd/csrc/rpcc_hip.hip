@@ -44,6 +44,16 @@ static int set_err(int code, const char *fmt, const char *a = "", const char *b 
 extern "C" int rpcc_version(void) { return RPCC_ABI_VERSION; }
 extern "C" const char *rpcc_last_error(void) { return g_err; }
 
+// Every workspace is described once, by a layout function that carves it: given the caller's base pointer it returns each region,
+// given nullptr it only sizes it (the regions are then their offsets), and the exported *_bytes function returns its `bytes`.
+static inline size_t round_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+struct Carve {   // take(): the next `n` bytes from the running offset rounded up to `align` (a power of two; relative to the base)
+    uintptr_t base; size_t off = 0;
+    explicit Carve(void *ws) : base(reinterpret_cast<uintptr_t>(ws)) {}
+    template <class T = char> T *take(size_t n, size_t align = 256) { off = round_up(off, align) + n; return reinterpret_cast<T *>(base + off - n); }
+    size_t bytes() const { return off; }
+};
+
 // Developer trace: the shipped library carries none.  Only a build with -DRPCC_DEVTRACE includes rpcc_trace.h (cycle stamps at
 // phase boundaries of the instrumented kernels); here its hooks are empty and rpcc_debug_stamps() refuses a buffer.
 #ifdef RPCC_DEVTRACE
@@ -940,16 +950,22 @@ __device__ void project_fixup_frame(const float *__restrict__ xyz, const int64_t
 
 static inline int band_bins_even(int P) { return (((P + BIN_PX - 1) / BIN_PX) + 1) & ~1; }   // record bins per frame, rounded up to even
 static inline int64_t pix_chunk_ids(int64_t total, int B) { return ((total > 0 ? total : 0) >> PIX_CH_SHIFT) + B; }
-static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-static inline size_t project_small_bytes(int B, int P) { return align16(((size_t)B * ((size_t)P + 8)) * 4 + 256); }   // lastz + flags
-static inline size_t project_cursor_bytes(int B, int P) { return align16((size_t)B * band_bins_even(P) * 4); }
-static inline size_t project_counts_bytes(int64_t total, int B, int P) { return align16((size_t)pix_chunk_ids(total, B) * band_bins_even(P) * 4); }
-static inline size_t project_lists_bytes(int64_t total, int B, int P) { return (size_t)pix_chunk_ids(total, B) * band_bins_even(P) * SHARE_BYTES; }
-static size_t project_scratch_bytes(int64_t total, int B, int P) {   // lastz, flags | cursors | counts | shares | exact path's lists
-    return project_small_bytes(B, P) + project_cursor_bytes(B, P) + project_counts_bytes(total, B, P) + project_lists_bytes(total, B, P) +
-           (size_t)(band_bins_even(P) / 2) * (size_t)((total > 0 ? total : 0) + B) * 8 + 16;
+// Projection scratch: lastz i32 [B,P] | flags | (binned path) cursors | counts | shares | exact path's lists
+struct ProjectLayout { int32_t *lastz, *flags; BandBins bb; size_t atomic_bytes, bytes; };
+static ProjectLayout project_layout(void *scratch, int64_t total, int B, int P) {   // (atomic_bytes: all the atomic path uses)
+    const size_t nbe = (size_t)band_bins_even(P), ids = (size_t)pix_chunk_ids(total, B);
+    Carve c(scratch);
+    ProjectLayout l;
+    l.lastz = c.take<int32_t>((size_t)B * P * 4, 4);
+    l.flags = c.take<int32_t>((size_t)B * 8 * 4, 4);   // B + 1 flags, then the ordered kernel's accept words
+    l.atomic_bytes = c.bytes(); c.take(256, 1);   // (256 spare bytes)
+    l.bb.nbe = (int)nbe;
+    l.bb.ocursor = c.take<uint32_t>((size_t)B * nbe * 4, 16); l.bb.counts = c.take<uint32_t>(ids * nbe * 4, 16); l.bb.lists = c.take(ids * nbe * SHARE_BYTES, 16);
+    l.bb.olists = c.take<uint2>((nbe / 2) * (size_t)((total > 0 ? total : 0) + B) * 8 + 16, 16);   // (+ 16: records are read in 16-byte pairs)
+    l.bytes = c.bytes();
+    return l;
 }
-extern "C" size_t rpcc_project_scratch_bytes(int64_t total, int B, int P) { return project_scratch_bytes(total, B, P); }
+extern "C" size_t rpcc_project_scratch_bytes(int64_t total, int B, int P) { return project_layout(nullptr, total, B, P).bytes; }
 
 extern "C" int rpcc_project_fastpath_check(const float *xyz, int64_t total, rpcc_geom g, uint64_t *counts, void *stream) {
     ARG_TRY(xyz && counts && total > 0 && g.H > 0 && g.W > 0);
@@ -961,7 +977,7 @@ extern "C" int rpcc_project_fastpath_check(const float *xyz, int64_t total, rpcc
 }
 
 // On return ri is final (0 = empty pixel).  scratch_bytes < rpcc_project_scratch_bytes() selects the
-// atomic path, which only needs B*(P+8)*4 bytes.
+// atomic path, which only needs the first regions of project_layout: atomic_bytes = B*(P+8)*4.
 // order_mode: ORD_MODE_OFF (the default: pixel + band kernels), ORD_MODE_PROBE (a frame whose points come in scanner order is projected by
 // project_ordered_kernel, the others by the pixel + band kernels), ORD_MODE_FORCE (test hook: every frame by the former).  tm: the [P,3] ray table
 // (needed by the ordered kernel when zcnt is wanted).  accept_out: dev i32 [B] or nullptr -- which frames the ordered kernel took.
@@ -973,21 +989,15 @@ static int launch_project(const float *xyz, const int64_t *offsets, int64_t tota
     const bool cleared = init != nullptr;   // fused batch: the pixel kernel initialises, flags are marked by epoch
     const int P = g.H * g.W;
     uint32_t *rb = reinterpret_cast<uint32_t *>(ri);
-    int32_t *lastz = reinterpret_cast<int32_t *>(scratch);
-    int32_t *flags = lastz + (int64_t)B * P;
+    const ProjectLayout pl = project_layout(scratch, total, B, P);
+    int32_t *lastz = pl.lastz, *flags = pl.flags;
     const dim3 fg((P + 1023) / 1024 < 64 ? (P + 1023) / 1024 : 64, B);
     const unsigned nb = (unsigned)((total + 255) / 256);
     const unsigned nb_small = nb < 2048 ? (nb ? nb : 1) : 2048;
-    BandBins bb;
-    bb.nbe = band_bins_even(P);
+    BandBins bb = pl.bb;
     // the binned path: room for the lists, a counter per band and wavefront in the pixel kernel's LDS
-    const bool fast = scratch_bytes >= project_scratch_bytes(total, B, P) && bb.nbe <= PIX_MAX_BANDS && total < ((int64_t)1 << 32);
+    const bool fast = scratch_bytes >= pl.bytes && bb.nbe <= PIX_MAX_BANDS && total < ((int64_t)1 << 32);
     if (fast) {
-        char *q = reinterpret_cast<char *>(scratch) + project_small_bytes(B, P);
-        bb.ocursor = reinterpret_cast<uint32_t *>(q); q += project_cursor_bytes(B, P);
-        bb.counts = reinterpret_cast<uint32_t *>(q); q += project_counts_bytes(total, B, P);
-        bb.lists = q; q += project_lists_bytes(total, B, P);
-        bb.olists = reinterpret_cast<uint2 *>(q);
         HIP_TRY(hipMemsetAsync(bb.ocursor, 0, (size_t)B * bb.nbe * 4, st));
         if (!cleared) HIP_TRY(hipMemsetAsync(flags, 0, (size_t)(B + 1) * 4, st));
         BatchInit bi;
@@ -1062,7 +1072,7 @@ extern "C" int rpcc_project_ordered(const float *points, int point_stride_bytes,
     ARG_TRY(total == 0 || points != nullptr);
     ARG_TRY(point_floats(point_stride_bytes) > 0);
     ARG_TRY(point_stride_bytes != 16 || (reinterpret_cast<uintptr_t>(points) & 15u) == 0);   // rows are read with 16-byte loads
-    ARG_TRY(scratch_bytes >= ((size_t)B * ((size_t)g.H * g.W + 8)) * 4);
+    ARG_TRY(scratch_bytes >= project_layout(nullptr, total, B, g.H * g.W).atomic_bytes);
     ARG_TRY((order_flags & ~(RPCC_PROJECT_ORDER_PROBE | RPCC_PROJECT_FORCE_ORDERED)) == 0);
     return launch_project(points, offsets, total, 0, B, g, ri, scratch, scratch_bytes, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr,
                           point_floats(point_stride_bytes), order_mode_of(order_flags), nullptr, accepted);
@@ -1949,6 +1959,8 @@ static int launch_ground_mask(float *ri, const float *tm, const double *ground, 
 extern "C" size_t rpcc_fps_table_bytes(int B, int H, int W) {
     return (size_t)B * FPS_TAB_ROWS * fps_tiling_range(H, W).T * 4;
 }
+// what a batch workspace holds for the tile table: a generous bound on rpcc_fps_table_bytes over every H x W = P
+static inline size_t fps_tab_bound_bytes(int B, int P) { return (size_t)B * FPS_TAB_ROWS * ((P + 31) / 32 + 4096) * 4; }
 
 extern "C" int rpcc_ground_mask(const float *ri, const float *tm, const double *ground, double threshold, int B, int H,
                                 int W, float *temp, int32_t *info, void *fps_table, void *stream) {
@@ -2710,7 +2722,7 @@ extern "C" int rpcc_assign_wide(const float *ri, const float *tm, const double *
 // ================================================================================================
 // a8  point model  (cpp_modules.cpp:471-518)  +  per-tile label histograms for the ordered scatter
 // ================================================================================================
-// Workspace layout (rpcc_workspace_bytes):  [ sums i64 B*KP | flags i32 B*4 (pad to 16 B) | hist u32 B*T*KP ]
+// Model part of a workspace (ws_layout; it opens the batch, plane model and decoder workspaces):  [ sums i64 B*KP | flags i32 B*4 | hist u32 B*T*KP ]
 // KP = K rounded up to 64, T = ceil(P / TILE).  hist[b][t][k] is first the pixel count of label k in
 // tile t, then (after model_scan_kernel) the output offset of that tile's first label-k pixel.
 #define TILE 1024
@@ -2725,37 +2737,54 @@ struct WsLayout {
     size_t bytes;
 };
 static WsLayout ws_layout(void *ws, int B, int P, int M) {
-    WsLayout L;
     const size_t KP = (size_t)kpad(M), T = (size_t)ntiles(P);
-    char *p = reinterpret_cast<char *>(ws);
-    L.sums = reinterpret_cast<int64_t *>(p);
-    size_t off = (size_t)B * KP * 8;
-    L.flags = reinterpret_cast<int32_t *>(p + off);
-    off += (((size_t)B * 4 * 4) + 255) & ~(size_t)255;
-    L.hist = reinterpret_cast<uint32_t *>(p + off);
-    off += (size_t)B * T * KP * 4;
-    L.bytes = off;
+    Carve c(ws);
+    WsLayout L;
+    L.sums = c.take<int64_t>((size_t)B * KP * 8); L.flags = c.take<int32_t>((size_t)B * 4 * 4); L.hist = c.take<uint32_t>((size_t)B * T * KP * 4);
+    L.bytes = c.bytes();
     return L;
 }
-// Workspace of one batch: [ model part | projection scratch | FPS temp | planar rays | FPS tile table ]
-static size_t plane_extra_bytes(int B, int P, int M) {   // label-ordered pixel list u32 [B,P] | points float4 [B,P] | key points per label i32 [B,K] | label steps f32 [B,K]
-    return (((size_t)B * P * 4 + 255) & ~(size_t)255) + (size_t)B * P * 16 + 2 * (((size_t)B * (M + 2) * 4 + 255) & ~(size_t)255) + 256;
+// The plane model's area (`extra`): label-ordered pixel list u32 [B,P] | the same list as points (x, y, z, r) float4 [B,P]
+struct PlaneLayout { uint32_t *order; float4 *pts4; size_t bytes; };
+static PlaneLayout plane_layout(void *extra, int B, int P) {
+    Carve c(extra);
+    uint32_t *order = c.take<uint32_t>((size_t)B * P * 4);
+    float4 *pts4 = c.take<float4>((size_t)B * P * 16);
+    return {order, pts4, c.bytes()};
 }
-static size_t slice_workspace_bytes(int B, int P, int M, int64_t total_points) {
-    const size_t model_ws = ws_layout(nullptr, B, P, M).bytes;
-    const size_t proj_ws = (project_scratch_bytes(total_points, B, P) + 255) & ~(size_t)255;
-    return model_ws + 256 + proj_ws + (size_t)B * P * 4        // + FPS temp [B,P] f32
-           + (size_t)3 * P * 4 + 256                            // + SoA copy of the ray table
-           + (size_t)B * FPS_TAB_ROWS * ((P + 31) / 32 + 4096) * 4 + 256;  // + FPS tile table (generous bound)
+// Workspace of one batch: [ model part | epoch | projection scratch | FPS temp | planar rays | FPS tile table | (general) plane area | key
+// points per label i32 [B,K] | label steps f32 [B,K] ], carved from the tile table's own start on (256-aligned in ws only for P % 64 == 0).
+// The ground fit's hand-off (count words | z-mask bytes | deferred whole-cloud fits) lies in the tile table's bytes; bytes = 0 if not.
+struct BatchLayout {
+    WsLayout L;
+    int32_t *epoch, *kpn = nullptr; char *proj_scratch, *extra = nullptr; float *temp, *rays_soa, *tiletab, *label_acc = nullptr;
+    size_t proj_bytes, bytes;
+};
+static BatchLayout batch_layout(void *ws, int B, int P, int M, int64_t total_points, bool general) {
+    Carve c(ws);
+    BatchLayout l;
+    l.L = ws_layout(ws, B, P, M); c.take(l.L.bytes); l.epoch = c.take<int32_t>(256);
+    l.proj_bytes = round_up(project_layout(nullptr, total_points, B, P).bytes, 256); l.proj_scratch = c.take(l.proj_bytes);
+    l.temp = c.take<float>((size_t)B * P * 4);
+    l.rays_soa = c.take<float>((size_t)3 * P * 4 + 256, 4);   // SoA copy of the ray table
+    l.tiletab = c.take<float>(0, 4);
+    const size_t tab_bytes = fps_tab_bound_bytes(B, P), ksz = round_up((size_t)B * (M + 2) * 4, 256);
+    Carve t(l.tiletab);
+    t.take(tab_bytes + 256);   // the tile table, 256 spare
+    if (general) {
+        l.extra = t.take(plane_layout(nullptr, B, P).bytes);
+        l.kpn = t.take<int32_t>(ksz, 4); l.label_acc = t.take<float>(ksz, 4); t.take(256, 1);
+    }
+    char *handoff_end = reinterpret_cast<char *>(wc_slot_of(rs_wc_of(reinterpret_cast<int32_t *>(l.tiletab), B, P), B, B).cnt);
+    l.bytes = handoff_end <= reinterpret_cast<char *>(l.tiletab) + tab_bytes ? c.bytes() + t.bytes() : 0;
+    return l;
 }
-extern "C" size_t rpcc_workspace_bytes(int B, int P, int M, int64_t total_points) {
-    if (B <= 0 || P <= 0 || M <= 0) return 0;
-    return slice_workspace_bytes(B, P, M, total_points) + 4096;
+static size_t batch_ws_bytes(int B, int P, int M, int64_t total_points, bool general) {   // the layout + 4096 spare (0: bad arguments)
+    const size_t n = B > 0 && P > 0 && M > 0 ? batch_layout(nullptr, B, P, M, total_points, general).bytes : 0;
+    return n ? n + 4096 : 0;
 }
-extern "C" size_t rpcc_workspace_bytes_general(int B, int P, int M, int64_t total_points) {
-    if (B <= 0 || P <= 0 || M <= 0) return 0;
-    return slice_workspace_bytes(B, P, M, total_points) + 4096 + plane_extra_bytes(B, P, M);
-}
+extern "C" size_t rpcc_workspace_bytes(int B, int P, int M, int64_t total_points) { return batch_ws_bytes(B, P, M, total_points, false); }
+extern "C" size_t rpcc_workspace_bytes_general(int B, int P, int M, int64_t total_points) { return batch_ws_bytes(B, P, M, total_points, true); }
 
 // Round 3: thread k walks label k's column of the tile x label table straight from global memory (the loads of consecutive
 // threads are consecutive words; SCAN_U tiles' loads in flight per thread) in two passes -- totals, then offsets with the label's
@@ -3387,17 +3416,21 @@ extern "C" int rpcc_predict_quantize_wide(const float *ri, const float *tm, cons
 // ================================================================================================
 #include "codec_kernels.h"
 
-extern "C" size_t rpcc_codec_workspace_bytes(int B, int P, int M) {
-    if (B <= 0 || P <= 0 || M <= 0) return 0;
-    return ws_layout(nullptr, B, P, M).bytes + 256 + (size_t)B * ntiles(P) * 4;
+// Workspace of the contour codec and the decoder: two views from offset 0 -- the contour entries' tile counts u32 [B,T] (they take no M;
+// a wide workspace holds them there too) and rpcc_decode's model part.  The size covers the model part, 256 bytes and the tile counts.
+struct CodecLayout { uint32_t *tile_cnt; WsLayout L; size_t bytes; };
+static CodecLayout codec_layout(void *ws, int B, int P, int M) {
+    const WsLayout L = ws_layout(ws, B, P, M);
+    return CodecLayout{reinterpret_cast<uint32_t *>(ws), L, L.bytes + 256 + (size_t)B * ntiles(P) * 4};
 }
+extern "C" size_t rpcc_codec_workspace_bytes(int B, int P, int M) { return B > 0 && P > 0 && M > 0 ? codec_layout(nullptr, B, P, M).bytes : 0; }
 
 extern "C" int rpcc_contour_encode(const uint8_t *seg, int B, int H, int W, uint8_t *contour_bits, uint16_t *idx_sequence,
                                    int32_t *nseq, void *ws, void *stream) {
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && seg && contour_bits && idx_sequence && nseq && ws);
     hipStream_t st = (hipStream_t)stream;
     const int P = H * W, T = ntiles(P);
-    uint32_t *tile_cnt = reinterpret_cast<uint32_t *>(ws);
+    uint32_t *tile_cnt = codec_layout(ws, B, P, 1).tile_cnt;   // (M places no tile count)
     contour_count_kernel<uint8_t><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt);
     tile_scan_kernel<<<B, 256, 0, st>>>(tile_cnt, T, nseq);
     contour_write_kernel<uint8_t><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt, contour_bits, idx_sequence);
@@ -3410,7 +3443,7 @@ extern "C" int rpcc_contour_decode(const uint8_t *contour_bits, const uint16_t *
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && seg && contour_bits && idx_sequence && ws);
     hipStream_t st = (hipStream_t)stream;
     const int P = H * W, T = ntiles(P);
-    uint32_t *tile_cnt = reinterpret_cast<uint32_t *>(ws);
+    uint32_t *tile_cnt = codec_layout(ws, B, P, 1).tile_cnt;   // (M places no tile count)
     contour_bits_count_kernel<<<dim3(T, B), 256, 0, st>>>(contour_bits, P, T, tile_cnt);
     tile_scan_kernel<<<B, 256, 0, st>>>(tile_cnt, T, nullptr);
     recover_map_kernel<uint8_t><<<dim3(T, B), 256, 0, st>>>(contour_bits, idx_sequence, P, T, tile_cnt, seg);
@@ -3425,7 +3458,7 @@ extern "C" int rpcc_decode(const uint8_t *seg, const int16_t *q16, const float *
     ARG_TRY(levels >= 0 && levels <= 8 && (levels == 0 || salience != nullptr));
     hipStream_t st = (hipStream_t)stream;
     const int KP = kpad(M), T = ntiles(P);
-    WsLayout L = ws_layout(ws, B, P, M);
+    const WsLayout L = codec_layout(ws, B, P, M).L;
     HIP_TRY(hipMemsetAsync(L.sums, 0, (size_t)((char *)L.hist - (char *)L.sums), st));
     int rc;
     if ((rc = launch_hist_scan(nullptr, seg, nullptr, B, P, M, L, nullptr, nullptr, nullptr, st))) return rc;
@@ -3567,11 +3600,9 @@ extern "C" int rpcc_intra_predict_wide(const uint16_t *seg, const float *model, 
 // ================================================================================================
 #include "plane_kernels.h"
 
-extern "C" size_t rpcc_plane_workspace_bytes(int B, int P, int M) {
-    if (B <= 0 || P <= 0 || M <= 0) return 0;
-    // model part | label-ordered pixel list u32 [B,P] | the same list as points (x, y, z, r) float4 [B,P]
-    return ws_layout(nullptr, B, P, M).bytes + 256 + (((size_t)B * P * 4 + 255) & ~(size_t)255) + (size_t)B * P * 16;
-}
+// ws of the plane model entries: [ model part | 256 | plane area (plane_layout) ]
+static inline size_t plane_extra_offset(int B, int P, int M) { return ws_layout(nullptr, B, P, M).bytes + 256; }
+extern "C" size_t rpcc_plane_workspace_bytes(int B, int P, int M) { return B > 0 && P > 0 && M > 0 ? plane_extra_offset(B, P, M) + plane_layout(nullptr, B, P).bytes : 0; }
 
 // hist / scan for a segmentation without the point sums: tile offsets (ordered scatter), counts, nnz
 template <class L>
@@ -3580,11 +3611,8 @@ static int launch_label_scan(const L *seg, int B, int P, int M, int32_t *counts,
     if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
     return launch_hist_scan(nullptr, seg, nullptr, B, P, M, lay, nullptr, counts, nnz, st);
 }
-// plane rows from a segmentation whose tile offsets (launch_label_scan) are in ws; extra = order | pts4 scratch.  Two launches: the
-// label-ordered lists, then the fits.
-static inline float4 *plane_pts4(void *extra, int B, int P) {
-    return reinterpret_cast<float4 *>(reinterpret_cast<char *>(extra) + (((size_t)B * P * 4 + 255) & ~(size_t)255));
-}
+// plane rows from a segmentation whose tile offsets (launch_label_scan) are in ws; extra = the plane area (plane_layout).  Two launches:
+// the label-ordered lists, then the fits.
 template <class L>
 static int launch_label_order(const float *ri, const float *tm, const L *seg, int B, int P, int M, void *ws, void *extra, hipStream_t st) {
     const int KP = kpad(M), T = ntiles(P);
@@ -3593,15 +3621,17 @@ static int launch_label_order(const float *ri, const float *tm, const L *seg, in
     // (the quantiser's round-3 layout -- four consecutive pixels per lane -- was tried here as well: 121 us against 97 us, because a
     // lane's four 16-byte point stores then lie 64 bytes apart from the next lane's; this kernel is bound by its 255 MB of stores)
     if constexpr (sizeof(L) == 2) HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&label_order_kernel<L>), (int)sh));   // above 64 KB
-    label_order_kernel<L><<<dim3(T, B), 256, sh, st>>>(seg, lay.hist, P, M, KP, T, reinterpret_cast<uint32_t *>(extra), ri, tm, plane_pts4(extra, B, P));
+    const PlaneLayout pa = plane_layout(extra, B, P);
+    label_order_kernel<L><<<dim3(T, B), 256, sh, st>>>(seg, lay.hist, P, M, KP, T, pa.order, ri, tm, pa.pts4);
     LAUNCH_CHECK();
     return RPCC_OK;
 }
 static PlaneGroupArgs plane_group_args(const float *tm, const double *ground, int B, int P, int M, double cos_cut, uint32_t seed,
                                        const int64_t *frame_ids, float *model, const int32_t *counts, void *ws, void *extra, const double *inject) {
     WsLayout L = ws_layout(ws, B, P, M);
+    const PlaneLayout pa = plane_layout(extra, B, P);
     PlaneGroupArgs a;
-    a.tm = tm; a.order_all = reinterpret_cast<const uint32_t *>(extra); a.pts_all = plane_pts4(extra, B, P); a.hist = L.hist; a.counts = counts;
+    a.tm = tm; a.order_all = pa.order; a.pts_all = pa.pts4; a.hist = L.hist; a.counts = counts;
     a.ground = ground; a.B = B; a.P = P; a.T = ntiles(P); a.model = model;
     a.pp.cos_cut = cos_cut; a.pp.thr = 0.1f; a.pp.min_points = 30; a.pp.iters = 10; a.pp.seed = seed; a.pp.frame_ids = frame_ids; a.pp.inject = inject;
     return a;
@@ -3628,7 +3658,7 @@ static int plane_model_entry(const float *ri, const float *tm, const L *seg, con
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = launch_label_scan(seg, B, P, M, counts, nullptr, ws, st, false))) return rc;
-    void *extra = reinterpret_cast<char *>(ws) + ws_layout(nullptr, B, P, M).bytes + 256;
+    void *extra = reinterpret_cast<char *>(ws) + plane_extra_offset(B, P, M);
     if ((rc = launch_label_order(ri, tm, seg, B, P, M, ws, extra, st))) return rc;
     return launch_plane_fits(tm, ground, B, P, M, cos_cut, seed, frame_ids, model, counts, ws, extra, st, inject_planes);
 }
@@ -3647,48 +3677,27 @@ extern "C" int rpcc_plane_model_wide(const float *ri, const float *tm, const uin
 // ================================================================================================
 // Everything a call derives from its arguments for ONE geometry group (one io, one rpcc_geom): the carve-up of the workspace and the
 // choices that follow from the flags.  rpcc_compress_batch has one plan, rpcc_compress_batch_mixed one per group.
-struct BatchPlan {
+struct BatchPlan : BatchLayout {
     const rpcc_batch_io *io;
-    int Bs, M, P;
-    int64_t npts;
-    rpcc_geom g;
-    double ground_threshold;
-    float acc;
-    char *ws;
-    WsLayout L;
+    int Bs, M, P; int64_t npts; rpcc_geom g; double ground_threshold; float acc; char *ws;
     bool fit_ground, brute, tiled;
-    char *proj_scratch, *extra;
-    size_t proj_bytes;
-    float *temp, *rays_soa, *tiletab, *label_acc;
-    int32_t *zcnt, *epoch, *kpn;
+    int32_t *zcnt;
     BatchInit bi;
 };
 static int plan_batch(BatchPlan &p, const rpcc_batch_io *io, int Bs, int64_t npts, rpcc_geom g, int M, double ground_threshold, float acc, char *ws) {
     p.io = io; p.Bs = Bs; p.M = M; p.P = g.H * g.W; p.npts = npts; p.g = g; p.ground_threshold = ground_threshold; p.acc = acc; p.ws = ws;
     const int P = p.P;
     p.fit_ground = io->ground_seed >= 0;  // >= 0: fit the ground plane here (seed + frame identity)
-    p.L = ws_layout(ws, Bs, P, M);
-    p.proj_scratch = ws + p.L.bytes + 256;
-    p.proj_bytes = (project_scratch_bytes(npts, Bs, P) + 255) & ~(size_t)255;
-    p.temp = reinterpret_cast<float *>(p.proj_scratch + p.proj_bytes);
-    p.rays_soa = p.temp + (size_t)Bs * P;
-    p.tiletab = p.rays_soa + (size_t)3 * P + 64;
+    static_cast<BatchLayout &>(p) = batch_layout(ws, Bs, P, M, npts, true);
+    ARG_TRY(p.bytes != 0);   // the ground fit's hand-off fits in the tile table's bytes
     p.zcnt = p.fit_ground ? reinterpret_cast<int32_t *>(p.tiletab) : nullptr;  // the tile table is written later
     // The first kernel of the batch (the pixel kernel) also writes the planar ray table (band kernel's z), initialises the info
     // counters of the ground mask and clears the RANSAC candidate counts and the label sums; the projection's per-frame
     // flags are marked with an epoch kept in the workspace (BatchInit), so the batch has no initialisation launch.
-    p.epoch = reinterpret_cast<int32_t *>(ws + p.L.bytes);   // the 256 bytes between the model part and the projection scratch
     p.bi.tm = io->tm; p.bi.soa = p.rays_soa; p.bi.P = P; p.bi.info = io->info; p.bi.B = Bs; p.bi.on = 1;
     p.bi.z0 = {reinterpret_cast<uint32_t *>(p.zcnt), p.zcnt ? (int)rs_count_words(Bs) : 0};
     p.bi.z1 = {reinterpret_cast<uint32_t *>(p.L.sums), (int)(((char *)p.L.hist - (char *)p.L.sums) / 4)};
-    const size_t tab_bytes = (size_t)Bs * FPS_TAB_ROWS * ((P + 31) / 32 + 4096) * 4;
-    // the ground fit's hand-off lies in the tile table's bytes: count words | z-mask bytes | the deferred whole-cloud fits (their end: slot Bs)
-    if (p.zcnt) ARG_TRY(reinterpret_cast<char *>(wc_slot_of(rs_wc_of(p.zcnt, Bs, P), Bs, Bs).cnt) <= reinterpret_cast<char *>(p.tiletab) + tab_bytes);
-    // model rows + the tile offsets of the ordered scatter (built once, used by the plane list and by the quantiser)
-    p.extra = reinterpret_cast<char *>(p.tiletab) + ((tab_bytes + 255) & ~(size_t)255) + 256;
-    const size_t ksz = (((size_t)Bs * (M + 2) * 4 + 255) & ~(size_t)255);
-    p.label_acc = io->nonuniform ? reinterpret_cast<float *>(p.extra + plane_extra_bytes(Bs, P, M) - 256 - ksz) : nullptr;
-    p.kpn = io->nonuniform ? reinterpret_cast<int32_t *>(p.extra + plane_extra_bytes(Bs, P, M) - 256 - 2 * ksz) : nullptr;
+    if (!io->nonuniform) { p.label_acc = nullptr; p.kpn = nullptr; }
     p.bi.z2 = {reinterpret_cast<uint32_t *>(p.kpn), p.kpn ? Bs * (M + 2) : 0};  // key points per label
     p.brute = (io->flags & (RPCC_FPS_BRUTEFORCE | RPCC_FPS_MODE_BITS)) != 0;   // a mode flag selects the reference kernel too
     p.tiled = !p.brute && fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES;
@@ -3891,7 +3900,8 @@ static int mixed_labels(const BatchPlan *pl, int G, hipStream_t st) {
         multi_add(mh, HistGroup{ri, io->seg, p.P, T, vec ? 1 : 0, p.L.sums, p.L.flags, p.L.hist}, p.Bs, T);
         multi_add(ms, ScanArgs{ri, io->seg, point ? io->ground : nullptr, p.P, M, KP, T, scan_kp2(M), p.L.sums, p.L.flags, p.L.hist,
                                point ? io->model : nullptr, io->counts, io->nnz}, p.Bs, 1);
-        if (!point) multi_add(mo, OrderGroup{io->seg, p.L.hist, p.P, T, reinterpret_cast<uint32_t *>(p.extra), io->ri, io->tm, plane_pts4(p.extra, p.Bs, p.P)}, p.Bs, T);
+        const PlaneLayout pa = plane_layout(p.extra, p.Bs, p.P);
+        if (!point) multi_add(mo, OrderGroup{io->seg, p.L.hist, p.P, T, pa.order, io->ri, io->tm, pa.pts4}, p.Bs, T);
     }
     model_hist_multi_kernel<<<mh.first[mh.n], 256, (size_t)KP * 12, st>>>(mh, KP);
     LAUNCH_CHECK();
@@ -3978,15 +3988,8 @@ static bool mid_clusters_ok(const rpcc_batch_io *io, rpcc_geom g, int M) {
 //   base u32 [B,K] | kpn i32 [B,K] | label_acc f32 [B,K] | flags i32 [B,4] | cen4 float4 [B,M] | FPS temp f32 [B,P] | FPS tile table |
 //   projection scratch | radix sort scratch ]
 struct WideWs {
-    uint32_t *keys_in, *vals_in, *keys_out, *vals_out, *order, *base;
-    int32_t *pos, *kpn, *flags;
-    float4 *pts4, *cen4;
-    unsigned long long *sums;
-    float *label_acc, *temp, *tiletab;
-    char *proj;
-    size_t proj_bytes;
-    void *sort_tmp;
-    size_t sort_bytes, bytes;
+    uint32_t *keys_in, *vals_in, *keys_out, *vals_out, *order, *base; int32_t *pos, *kpn, *flags; float4 *pts4, *cen4; unsigned long long *sums;
+    float *label_acc, *temp, *tiletab; char *proj; void *sort_tmp; size_t proj_bytes, sort_bytes, bytes;
 };
 static size_t wide_sort_bytes(int64_t n, int end_bit) {
     size_t b = 0;
@@ -3997,21 +4000,16 @@ static size_t wide_sort_bytes(int64_t n, int end_bit) {
 static inline int wide_key_bits(int B) { int v = 16; while ((1 << (v - 16)) < B) v++; return v; }
 static WideWs wide_layout(void *ws, int B, int P, int M, int64_t total_points) {
     WideWs w;
-    const size_t BP = (size_t)B * P, K = (size_t)M + 2, a = 255;
-    char *p = reinterpret_cast<char *>(ws);
-    size_t off = 0;
-    auto take = [&](size_t n) { char *r = p + off; off += (n + a) & ~a; return r; };
-    w.keys_in = (uint32_t *)take(BP * 4); w.vals_in = (uint32_t *)take(BP * 4); w.keys_out = (uint32_t *)take(BP * 4); w.vals_out = (uint32_t *)take(BP * 4);
-    w.pos = (int32_t *)take(BP * 4); w.order = (uint32_t *)take(BP * 4); w.pts4 = (float4 *)take(BP * 16);
-    w.sums = (unsigned long long *)take((size_t)B * K * 8); w.base = (uint32_t *)take((size_t)B * K * 4); w.kpn = (int32_t *)take((size_t)B * K * 4);
-    w.label_acc = (float *)take((size_t)B * K * 4); w.flags = (int32_t *)take((size_t)B * 16); w.cen4 = (float4 *)take((size_t)B * M * 16);
-    w.temp = (float *)take(BP * 4);
-    w.tiletab = (float *)take((size_t)B * FPS_TAB_ROWS * ((P + 31) / 32 + 4096) * 4);
-    w.proj_bytes = (project_scratch_bytes(total_points, B, P) + 255) & ~(size_t)255;
-    w.proj = take(w.proj_bytes);
-    w.sort_bytes = wide_sort_bytes((int64_t)BP, wide_key_bits(B));
-    w.sort_tmp = take(w.sort_bytes + 256);
-    w.bytes = off;
+    const size_t BP = (size_t)B * P, K = (size_t)M + 2;
+    Carve c(ws);
+    w.keys_in = c.take<uint32_t>(BP * 4); w.vals_in = c.take<uint32_t>(BP * 4); w.keys_out = c.take<uint32_t>(BP * 4); w.vals_out = c.take<uint32_t>(BP * 4);
+    w.pos = c.take<int32_t>(BP * 4); w.order = c.take<uint32_t>(BP * 4); w.pts4 = c.take<float4>(BP * 16);
+    w.sums = c.take<unsigned long long>((size_t)B * K * 8); w.base = c.take<uint32_t>((size_t)B * K * 4); w.kpn = c.take<int32_t>((size_t)B * K * 4);
+    w.label_acc = c.take<float>((size_t)B * K * 4); w.flags = c.take<int32_t>((size_t)B * 16); w.cen4 = c.take<float4>((size_t)B * M * 16);
+    w.temp = c.take<float>(BP * 4); w.tiletab = c.take<float>(fps_tab_bound_bytes(B, P));
+    w.proj_bytes = round_up(project_layout(nullptr, total_points, B, P).bytes, 256); w.proj = c.take(w.proj_bytes);
+    w.sort_bytes = wide_sort_bytes((int64_t)BP, wide_key_bits(B)); w.sort_tmp = c.take(w.sort_bytes + 256);
+    w.bytes = round_up(c.bytes(), 256);
     return w;
 }
 extern "C" size_t rpcc_wide_workspace_bytes(int B, int P, int M, int64_t total_points) {
@@ -4089,7 +4087,7 @@ extern "C" int rpcc_contour_encode_wide(const uint16_t *seg, int B, int H, int W
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && seg && contour_bits && idx_sequence && nseq && ws);
     hipStream_t st = (hipStream_t)stream;
     const int P = H * W, T = ntiles(P);
-    uint32_t *tile_cnt = reinterpret_cast<uint32_t *>(ws);
+    uint32_t *tile_cnt = codec_layout(ws, B, P, 1).tile_cnt;   // (M places no tile count)
     contour_count_kernel<uint16_t><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt);
     tile_scan_kernel<<<B, 256, 0, st>>>(tile_cnt, T, nseq);
     contour_write_kernel<uint16_t><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt, contour_bits, idx_sequence);
@@ -4100,7 +4098,7 @@ extern "C" int rpcc_contour_decode_wide(const uint8_t *contour_bits, const uint1
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && seg && contour_bits && idx_sequence && ws);
     hipStream_t st = (hipStream_t)stream;
     const int P = H * W, T = ntiles(P);
-    uint32_t *tile_cnt = reinterpret_cast<uint32_t *>(ws);
+    uint32_t *tile_cnt = codec_layout(ws, B, P, 1).tile_cnt;   // (M places no tile count)
     contour_bits_count_kernel<<<dim3(T, B), 256, 0, st>>>(contour_bits, P, T, tile_cnt);
     tile_scan_kernel<<<B, 256, 0, st>>>(tile_cnt, T, nullptr);
     recover_map_kernel<uint16_t><<<dim3(T, B), 256, 0, st>>>(contour_bits, idx_sequence, P, T, tile_cnt, seg);

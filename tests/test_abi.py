@@ -34,6 +34,110 @@ def test_version_and_workspace(built):
     assert lib.rpcc_workspace_bytes(0, 64 * 2048, 100, 0) == 0
 
 
+# Workspace sizes the library returned before its workspaces were carved by layout functions (csrc/rpcc_hip.hip: Carve and the *_layout
+# functions), over B x geometry (x M (x total_points)) in the loop order of test_workspace_sizes_are_pinned.  An odd P is included.
+_SIZE_BS = (1, 3, 129, 256)
+_SIZE_GEOMS = ((16, 1800), (32, 2250), (64, 2000), (64, 2048), (80, 2000), (31, 997))
+_SIZE_MS = (1, 100, 254)
+_WS = [
+    853952, 1428416, 2003136, 861888, 1436352, 2011072, 877760, 1452224, 2026944, 1818080, 4690912, 7564000, 1836768, 4709600, 7582688,
+    1874144, 4746976, 7620064, 3035904, 8132352, 13277952, 3068416, 8164864, 13310464, 3133440, 8229888, 13375488, 3102720, 8346624,
+    13590528, 3136000, 8379904, 13623808, 3202560, 8446464, 13690368, 3756672, 13349248, 22942080, 3797376, 13389952, 22982784, 3878784,
+    13471360, 23064192, 899792, 1515728, 2131920, 908240, 1524176, 2140368, 925136, 1541072, 2157264, 1859392, 3583296, 5306944, 1883200,
+    3607104, 5330752, 1930816, 3654720, 5378368, 3714976, 12333728, 20952480, 3771040, 12389792, 21008544, 3883168, 12501920, 21120672,
+    6024448, 21362944, 36750592, 6121984, 21460480, 36848128, 6317056, 21655552, 37043200, 6151168, 21882880, 37614848, 6251008, 21982720,
+    37714688, 6450688, 22182400, 37914368, 7419008, 36196992, 64974976, 7541120, 36319104, 65097088, 7785344, 36563328, 65341312, 1946344,
+    3794408, 5642472, 1971688, 3819752, 5667816, 2022376, 3870440, 5718504, 65211328, 139528384, 213845184, 66235072, 140552128, 214868928,
+    68282560, 142599616, 216916416, 123231712, 494816480, 866401504, 125642464, 497227232, 868812256, 130463968, 502048736, 873633760,
+    194315008, 854899456, 1515533056, 198509056, 859093504, 1519727104, 206897152, 867481600, 1528115200, 198215680, 874679296, 1551142912,
+    202508800, 878972416, 1555436032, 211095040, 887558656, 1564022272, 238145152, 1476777856, 2715410560, 243395968, 1482028672,
+    2720661376, 253897600, 1492530304, 2731163008, 67885776, 147622096, 227383248, 68975568, 148711888, 228473040, 71155152, 150891472,
+    230652624, 129065728, 276550400, 424035328, 131097344, 278582016, 426066944, 135160576, 282645248, 430130176, 243696640, 981120512,
+    1718544640, 248480768, 985904640, 1723328768, 258049024, 995472896, 1732897024, 384099584, 1695075584, 3006051584, 392422656,
+    1703398656, 3014374656, 409068800, 1720044800, 3031020800, 391804160, 1734243584, 3076683008, 400323840, 1742763264, 3085202688,
+    417363200, 1759802624, 3102242048, 470702336, 2928782336, 5386862336, 481122560, 2939202560, 5397282560, 501963008, 2960043008,
+    5418123008, 134348228, 292613572, 450879172, 136510916, 294776260, 453041860, 140836292, 299101636, 457367236,
+]
+
+_WS_GENERAL = [
+    1430720, 2005184, 2579904, 1439168, 2013632, 2588352, 1456064, 2030528, 2605248, 3258848, 6131680, 9004768, 3278048, 6150880, 9023968,
+    3316448, 6189280, 9062368, 5596672, 10693120, 15838720, 5629696, 10726144, 15871744, 5695744, 10792192, 15937792, 5724928, 10968832,
+    16212736, 5758720, 11002624, 16246528, 5826304, 11070208, 16314112, 6957440, 16550016, 26142848, 6998656, 16591232, 26184064, 7081088,
+    16673664, 26266496, 1518720, 2134656, 2750848, 1527680, 2143616, 2759808, 1545600, 2161536, 2777728, 3588160, 5312064, 7035712, 3614016,
+    5337920, 7061568, 3665216, 5389120, 7112768, 8035744, 16654496, 25273248, 8093856, 16712608, 25331360, 8209568, 16828320, 25447072,
+    13705216, 29043712, 44431360, 13804800, 29143296, 44530944, 14003456, 29341952, 44729600, 14016256, 29747968, 45479936, 14118144,
+    29849856, 45581824, 14321408, 30053120, 45785088, 17019776, 45797760, 74575744, 17143936, 45921920, 74699904, 17391744, 46169728,
+    74947712, 3801592, 5649656, 7497720, 3828984, 5677048, 7525112, 3883256, 5731320, 7579384, 139519168, 213836224, 288153024, 140644800,
+    214961856, 289278656, 142851008, 217168064, 291484864, 308995552, 680580320, 1052165344, 311508192, 683092960, 1054677984, 316488416,
+    688073184, 1059658208, 524558848, 1185143296, 1845776896, 528854784, 1189439232, 1850072832, 537401600, 1197986048, 1858619648,
+    536385280, 1212848896, 1889312512, 540780288, 1217243904, 1893707520, 549525248, 1225988864, 1902452480, 650948992, 1889581696,
+    3128214400, 656301696, 1894934400, 3133567104, 666962048, 1905594752, 3144227456, 147629696, 227366016, 307127168, 148821376, 228557696,
+    308318848, 151159680, 230896000, 310657152, 276528128, 424012800, 571497728, 278762496, 426247168, 573732096, 283141120, 430625792,
+    578110720, 612343040, 1349766912, 2087191040, 617329920, 1354753792, 2092177920, 627213568, 1364637440, 2102061568, 1039465984,
+    2350441984, 3661417984, 1047991808, 2358967808, 3669943808, 1064953344, 2375929344, 3686905344, 1062899200, 2405338624, 3747778048,
+    1071621632, 2414061056, 3756500480, 1088976384, 2431415808, 3773855232, 1289908736, 3747988736, 6206068736, 1300531712, 3758611712,
+    6216691712, 1321687552, 3779767552, 6237847552, 292598468, 450863812, 609129412, 294963908, 453229252, 611494852, 299604676, 457870020,
+    616135620,
+]
+
+_PROJECT_SCRATCH = [
+    140120, 714696, 1289328, 337504, 3210384, 6083376, 561504, 5657920, 10803616, 573792, 5817696, 11061712, 714120, 10306776, 19899600,
+    148552, 764560, 1380640, 419784, 2143512, 3867296, 1011968, 9630608, 18249360, 1683968, 17022384, 32410080, 1720832, 17452544, 33184368,
+    2141784, 30919752, 59697888, 445080, 2293120, 4141232, 18038616, 92355592, 166672624, 43503200, 415088080, 786673072, 72399200,
+    732983616, 1393617312, 73984352, 750447968, 1426911696, 92084616, 1330717272, 2569350096, 19125832, 98862320, 178623440, 35797264,
+    183282064, 330766920, 86331664, 823755664, 1561179776, 143675664, 1454651664, 2765627776, 146821392, 1489260816, 2831700352, 182741264,
+    2640821264, 5098901432, 37954832, 196220368, 354485944,
+]
+
+_PLANE_WS = [
+    584448, 592384, 608256, 1459200, 1477888, 1515264, 2593024, 2625536, 2690560, 2655232, 2688512, 2755072, 3241216, 3281920, 3363328,
+    627120, 635568, 652464, 1752320, 1776128, 1823744, 4376576, 4432640, 4544768, 7778048, 7875584, 8070656, 7964672, 8064512, 8264192,
+    9722624, 9844736, 10088960, 1880336, 1905680, 1956368, 75330304, 76354048, 78401536, 188173312, 190584064, 195405568, 334436608,
+    338630656, 347018752, 342461440, 346754560, 355340800, 418053376, 423304192, 433805824, 80832432, 81922224, 84101808, 149491968,
+    151523584, 155586816, 373428480, 378212608, 387780864, 663687424, 672010496, 688656640, 679612672, 688132352, 705171712, 829624576,
+    840044800, 860885248, 160410880, 162573568, 166898944,
+]
+
+_CODEC_WS = [
+    8564, 16500, 32372, 19484, 38172, 75548, 33524, 66036, 131060, 34304, 67584, 134144, 41844, 82548, 163956, 9084, 17532, 34428, 24668,
+    48476, 96092, 57428, 113492, 225620, 99548, 197084, 392156, 101888, 201728, 401408, 124508, 246620, 490844, 26228, 51572, 102260,
+    1041268, 2065012, 4112500, 2449948, 4860700, 9682204, 4261108, 8455156, 16843252, 4361728, 8654848, 17241088, 5334388, 10585204,
+    21086836, 1108348, 2198140, 4377724, 2065664, 4097280, 8160512, 4861184, 9645312, 19213568, 8455424, 16778496, 33424640, 8655104,
+    17174784, 34214144, 10585344, 21005568, 41846016, 2198784, 4361472, 8686848,
+]
+
+_FPS_TABLE = [
+    5472, 13632, 24192, 24576, 30240, 6144, 16416, 40896, 72576, 73728, 90720, 18432, 705888, 1758528, 3120768, 3170304, 3900960, 792576,
+    1400832, 3489792, 6193152, 6291456, 7741440, 1572864,
+]
+
+
+def test_workspace_sizes_are_pinned(built):
+    """The exported sizes equal the recorded ones.  The one exception is rpcc_workspace_bytes_general: its plane area starts after the FPS
+    tile table rounded up to 256 bytes, which the size now counts -- exactly that round-up more, always under 256 bytes."""
+    lib = built.lib()
+    ws, gen, proj, plane, codec, fps = (iter(v) for v in (_WS, _WS_GENERAL, _PROJECT_SCRATCH, _PLANE_WS, _CODEC_WS, _FPS_TABLE))
+    for B in _SIZE_BS:
+        for H, W in _SIZE_GEOMS:
+            P = H * W
+            assert lib.rpcc_fps_table_bytes(B, H, W) == next(fps)
+            for t in (0, B * P, 2 * B * P + 7):
+                assert lib.rpcc_project_scratch_bytes(t, B, P) == next(proj), (B, P, t)
+            tab = B * 12 * ((P + 31) // 32 + 4096) * 4       # the tile-table bound of a batch workspace
+            for M in _SIZE_MS:
+                assert lib.rpcc_plane_workspace_bytes(B, P, M) == next(plane), (B, P, M)
+                assert lib.rpcc_codec_workspace_bytes(B, P, M) == next(codec), (B, P, M)
+                for t in (0, B * P, 2 * B * P + 7):
+                    assert lib.rpcc_workspace_bytes(B, P, M, t) == next(ws), (B, P, M, t)
+                    grown = lib.rpcc_workspace_bytes_general(B, P, M, t) - next(gen)
+                    assert grown == -tab % 256 and 0 <= grown < 256, (B, P, M, t, grown)
+                    assert lib.rpcc_wide_workspace_bytes(B, P, M, t) >= lib.rpcc_workspace_bytes_general(B, P, M, t)
+    for v in (ws, gen, proj, plane, codec, fps):
+        assert next(v, None) is None
+    for M in (255, 1022):
+        assert lib.rpcc_wide_workspace_bytes(3, 64 * 2048, M, 0) >= lib.rpcc_workspace_bytes_general(3, 64 * 2048, M, 0)
+
+
 def test_argument_errors_do_not_crash(built):
     lib = built.lib()
     rc = lib.rpcc_fps_xyz(0, 10, 5, None, None, None, None)

@@ -45,8 +45,9 @@ extern "C" {
 /* Interface version: changes whenever the layout of a struct below or the meaning of an argument changes (the structs carry no size
  * field).  A binding compares rpcc_version() with the RPCC_ABI_VERSION of the header it was built against before it calls anything else
  * (r-pcc_amd/_lib.py does).  100: round 3.  101: rpcc_batch_io.point_stride_bytes.  102: the uint16-label entries (rpcc_*_wide), rpcc_compress_batch_stages.
- * 103: rpcc_project_ordered, the RPCC_PROJECT_* bits of rpcc_batch_io.flags, the uint16 stage entries (rpcc_assign_wide ...). */
-#define RPCC_ABI_VERSION 103
+ * 103: the scanner-order window projection entry, the RPCC_PROJECT_* bits of rpcc_batch_io.flags, the uint16 stage entries (rpcc_assign_wide ...).
+ * 104: the window projection entry and the RPCC_PROJECT_* bits removed (rpcc_batch_io.flags takes the FPS bits only). */
+#define RPCC_ABI_VERSION 104
 int rpcc_version(void);
 const char *rpcc_last_error(void);
 
@@ -87,22 +88,6 @@ int rpcc_project(const float *xyz, const int64_t *offsets, int64_t total, int B,
  * 16-byte row per point (points 16-byte aligned); 12 (or 0) = packed xyz = rpcc_project.  offsets / total count POINTS. */
 int rpcc_project_strided(const float *points, int point_stride_bytes, const int64_t *offsets, int64_t total, int B,
                          rpcc_geom g, float *ri, void *scratch, size_t scratch_bytes, void *stream);
-/* Sweeps in SCANNER ORDER (opt-in).  The reference's inputs are .bin files as the scanner wrote them (dataset/dataset.py:48-50): ring after ring, so
- * consecutive points fall into neighbouring rows of the range image.  With RPCC_PROJECT_ORDER_PROBE one workgroup per frame first PROBES the order
- * of the frame's points (16 runs of 64 points); a frame whose points move through the image ring by ring is projected by one kernel that keeps a
- * window of image rows in LDS and never writes a per-point record (csrc/project_ordered.h), any other frame -- shuffled points, as the synthetic
- * benchmark sweeps -- by the two record kernels.  Both give the reference's image bit for bit for ANY order (the window kernel re-opens rows it has
- * already written when a late point asks for one); the probe only chooses.  Off by default: measured on MI355X the window kernel -- one
- * 1024-thread workgroup per frame, 4 wavefronts per SIMD -- takes 290 us per 256 stored sweeps against 236 us of the two record kernels, and the
- * probe launch costs the shuffled benchmark 1.3 % (profiles/HISTORY.md, round 6).  order_flags / rpcc_batch_io.flags:
- *   RPCC_PROJECT_ORDER_PROBE      probe every frame's point order, window kernel for the frames that pass
- *   RPCC_PROJECT_FORCE_ORDERED    test hook: every frame with a point through the window kernel, whatever its order
- * rpcc_project_ordered = rpcc_project_strided with those flags and, in `accepted` (dev i32 [B], may be NULL), which frames the window kernel took.
- * Images the window kernel does not take (more than 128 rows, a width that is no multiple of four or above 16384) are never probed. */
-#define RPCC_PROJECT_ORDER_PROBE 16
-#define RPCC_PROJECT_FORCE_ORDERED 32
-int rpcc_project_ordered(const float *points, int point_stride_bytes, const int64_t *offsets, int64_t total, int B,
-                         rpcc_geom g, float *ri, void *scratch, size_t scratch_bytes, int order_flags, int32_t *accepted, void *stream);
 
 /* ---- a4: ground plane ----------------------------------------------------------------------- *
  * replaces the ground branch of PointCloudSegment.segment: candidate selection + RANSAC
@@ -317,8 +302,8 @@ typedef struct rpcc_batch_io {
     int16_t *q16;            /* dev i16 [B,P] out */
     int32_t *nnz;            /* dev i32 [B] out */
     int32_t *info;           /* dev i32 [B,8] out */
-    int32_t flags;           /* 0, RPCC_FPS_BRUTEFORCE, or the CUDA-binary FPS modes RPCC_FPS_FMA1 / _FMA2 / _TIE_CUDA; | RPCC_PROJECT_ORDER_PROBE /
-                                RPCC_PROJECT_FORCE_ORDERED (see rpcc_project_ordered) */
+    int32_t flags;           /* 0, RPCC_FPS_BRUTEFORCE, or the CUDA-binary FPS modes RPCC_FPS_FMA1 / _FMA2 / _TIE_CUDA; any other bit is
+                                refused (RPCC_ERR_ARG) */
     void *timer;             /* rpcc_timer_create() handle or NULL: times this call's FPS launch (bench.py) */
     /* framework / model selection (tools/compress.py:109-124, cfgs/compressor.yaml: compress_framework, modeling_method) */
     int32_t model_method;    /* 0: point model (a8);  1: plane model (a9: rpcc_plane_model with plane_cos_cut, plane_seed,

@@ -144,6 +144,20 @@ def test_argument_errors_do_not_crash(built):
     assert rc == -1 and b"bad argument" in lib.rpcc_last_error()
 
 
+def test_unknown_batch_flags_are_refused(built):
+    """rpcc_batch_io.flags takes the FPS bits only: 16 and 32 (the scanner-order projection bits of ABI 103) are an argument error,
+    raised before anything touches the device (every pointer below is a host dummy that must never reach a kernel)."""
+    lib = built.lib()
+    dummy = ctypes.create_string_buffer(256)
+    p = ctypes.addressof(dummy)
+    geom = built.Geom(64, 2048, 6.2831855, 0.034906585, -0.43458698)
+    for flags in (16, 32, 16 | 1):
+        io = built.BatchIO(p, p, 1000, p, p, -1, None, p, p, p, p, p, p, p, p, p, flags, None, 0, 0.0, 0, None, None, None, 12)
+        for name, extra in (("rpcc_compress_batch", ()), ("rpcc_compress_batch_stages", (1,)), ("rpcc_compress_batch_wide", ())):
+            rc = getattr(lib, name)(ctypes.byref(io), 2, geom, 100, 0.1, 0.04, p, *extra, None)
+            assert rc == -1 and b"flags" in lib.rpcc_last_error(), (name, flags, rc, lib.rpcc_last_error())
+
+
 def test_product_never_imports_oracle():
     """The oracle is test infrastructure: nothing under r-pcc_amd/ may import, link or load it."""
     bad = re.compile(r"(^|\n)\s*(from|import)\s+oracle\b|liborpcc|oracle/_ref|oracle\.oracle")

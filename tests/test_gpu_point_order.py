@@ -1,8 +1,7 @@
-"""-m gpu: a2 for sweeps in scanner order -- project_ordered_kernel (csrc/project_ordered.h: a window of image rows in LDS, no per-point
-records, chosen per frame by a probe of the points' order) against the oracle (cpp_modules.cpp:427-467 restated) and against the two
-record kernels, bit for bit, for ANY order of the points: the stored order of a real sweep (dataset/dataset.py:48-50), reversed, shuffled,
-rings in random order, late points that make the window re-open rows it has written, depth-0 points, special values, ragged batches that
-mix accepted and rejected frames, both point layouts, and the fused batch's hand-over to the ground fit."""
+"""-m gpu: a2 for any order of the points -- the record kernels (project_pix_kernel + project_band_kernel) against the oracle
+(cpp_modules.cpp:427-467 restated) and against the all-exact device-atomic path, bit for bit: the stored order of a real sweep
+(dataset/dataset.py:48-50), reversed, shuffled, rings in random order, late points that come back to rows already filled, depth-0
+points, special values, ragged batches, both point layouts, and the fused batch's hand-over to the ground fit."""
 import os
 
 import numpy as np
@@ -11,7 +10,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-PROBE, FORCE = 16, 32      # include/rpcc_hip.h: RPCC_PROJECT_ORDER_PROBE, RPCC_PROJECT_FORCE_ORDERED
 
 
 @pytest.fixture(scope="module")
@@ -40,7 +38,7 @@ def _beq(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
-def _project(env, frames, geom, flags, rows=False):
+def _project(env, frames, geom, rows=False, atomic_path=False):
     torch, ops = env["torch"], env["ops"]
     offs = np.zeros(len(frames) + 1, np.int64)
     offs[1:] = np.cumsum([f.shape[0] for f in frames])
@@ -49,10 +47,8 @@ def _project(env, frames, geom, flags, rows=False):
         r4 = np.full((xyz.shape[0], 4), np.nan, np.float32)
         r4[:, :3] = xyz
         xyz = r4
-    acc = torch.full((len(frames),), -1, dtype=torch.int32, device=env["dev"])
     xt = _to(env, xyz) if offs[-1] else torch.zeros((0, 4 if rows else 3), dtype=torch.float32, device=env["dev"])
-    ri = ops.project(xt, _to(env, offs), geom, order_flags=flags, accepted=acc)
-    return ri.cpu().numpy(), acc.cpu().numpy()
+    return ops.project(xt, _to(env, offs), geom, atomic_path=atomic_path).cpu().numpy()
 
 
 def _ring_order(f, H=64):
@@ -62,8 +58,8 @@ def _ring_order(f, H=64):
     return f[np.lexsort((np.arctan2(f[:, 1], f[:, 0]), -ring))]
 
 
-def test_stored_order_is_accepted_and_equals_the_oracle(env):
-    """The real sweep as stored (122 k points, ring by ring) and the orders a probe must tell apart."""
+def test_stored_order_equals_the_oracle(env):
+    """The real sweep as stored (122 k points, ring by ring), reversed, shuffled, its rings in random order, its halves swapped, a small piece."""
     orc = env["orc"]
     g, geom, _ = _geom(env, "Velodyne64E")
     xyz = np.load(os.path.join(HERE, "golden", "example_64E.npz"))["xyz"]
@@ -73,32 +69,23 @@ def test_stored_order_is_accepted_and_equals_the_oracle(env):
     half = xyz.shape[0] // 2
     frames = [xyz, xyz[::-1].copy(), xyz[rng.permutation(xyz.shape[0])], ringshuf, np.concatenate([xyz[half:], xyz[:half]]), xyz[:3000].copy()]
     want = [orc.project(f, g) for f in frames]
-    ri, acc = _project(env, frames, geom, PROBE)
-    assert list(acc) == [1, 1, 0, 0, 1, 0], acc        # stored, reversed: taken; shuffled, random rings: records; halves swapped: taken; small: records
+    ri = _project(env, frames, geom)
     for i in range(len(frames)):
         assert _beq(ri[i], want[i]), i
-    ri_f, acc_f = _project(env, frames, geom, FORCE)   # every frame through the window kernel, whatever its order
-    assert list(acc_f) == [1] * len(frames)
-    for i in range(len(frames)):
-        assert _beq(ri_f[i], want[i]), ("forced", i)
-    ri_n, acc_n = _project(env, frames, geom, 0)
-    assert list(acc_n) == [0] * len(frames) and _beq(ri_n, ri)
-    ri_r, acc_r = _project(env, frames, geom, PROBE, rows=True)        # the rows as a .bin stores them (16-byte loads, garbage 4th column)
-    assert list(acc_r) == list(acc) and _beq(ri_r, ri)
-    ri_rf, _ = _project(env, frames, geom, FORCE, rows=True)
-    assert _beq(ri_rf, ri)
+    ri_r = _project(env, frames, geom, rows=True)        # the rows as a .bin stores them (16-byte loads, garbage 4th column)
+    assert _beq(ri_r, ri)
 
 
-def test_window_reopens_rows_for_late_points(env):
-    """Points that come back to rows the window has already written (a second sweep appended, single stragglers far behind the front,
-    a depth-0 point, NaN / inf / huge coordinates, points on the azimuth seam): same image as the oracle's sequential loop."""
+def test_late_points_that_revisit_rows(env):
+    """Points that come back to rows the earlier points have filled (a second sweep appended, single stragglers far behind the front),
+    a depth-0 point, NaN / inf / huge coordinates, points on the azimuth seam: same image as the oracle's sequential loop."""
     orc, synth = env["orc"], env["synth"]
     gb = orc.LidarGeom(H=64, W=2048, hfov_deg=360, vmax_deg=2.0, vmin_deg=-24.9)
     geomb = env["ops"].make_geom(gb.H, gb.W, gb.horizontal_FOV, gb.vertical_max, gb.vertical_min)
     rng = np.random.default_rng(11)
     f = _ring_order(synth.make_frame(7, 64, 2048).numpy())
     f2 = _ring_order(synth.make_frame(8, 64, 2048).numpy())
-    two = np.concatenate([f, f2 * np.float32(0.97)])                   # the second sweep re-opens every row, nearer returns win
+    two = np.concatenate([f, f2 * np.float32(0.97)])                   # the second sweep revisits every row, nearer returns win
     strag = f.copy()
     idx = rng.integers(0, f.shape[0], 400)
     strag[np.sort(rng.integers(f.shape[0] // 2, f.shape[0], 400))] = f[idx] * np.float32(0.5)   # stragglers from anywhere, late
@@ -112,19 +99,16 @@ def test_window_reopens_rows_for_late_points(env):
     frames = [two, strag, special, zero, f[:5000].copy(), np.zeros((0, 3), np.float32), f[:1].copy()]
     want = [orc.project(two, gb), orc.project(strag, gb), orc.project(special[keep], gb), orc.project(zero, gb), orc.project(f[:5000], gb),
             orc.project(np.zeros((0, 3), np.float32), gb), orc.project(f[:1], gb)]
-    for flags in (PROBE, FORCE):
-        for rows in (False, True):
-            ri, acc = _project(env, frames, geomb, flags, rows=rows)
-            for i in range(len(frames)):
-                assert _beq(ri[i], want[i]), (flags, rows, i, acc)
-            if flags == FORCE:
-                assert list(acc) == [1, 1, 1, 1, 1, 0, 1]                # (a frame without a point has nothing to probe)
+    for rows in (False, True):
+        ri = _project(env, frames, geomb, rows=rows)
+        for i in range(len(frames)):
+            assert _beq(ri[i], want[i]), (rows, i)
 
 
 @pytest.mark.parametrize("gname", ["Velodyne64E", "Velodyne64E_2048", "VelodyneVLP16", "Velodyne32E"])
-def test_forced_window_kernel_on_every_shipped_geometry(env, gname):
-    """Shuffled synthetic sweeps through the window kernel (FORCE: the window thrashes, the image must not care) on the reference's lidar
-    tables: 16 rows x 1800 fits the window whole; 32 x 2250 has a width that is no multiple of four and is never probed."""
+def test_every_shipped_geometry(env, gname):
+    """Shuffled and ring-ordered synthetic sweeps on the reference's lidar tables, both point layouts: 16 rows x 1800 and 32 x 2250, a width
+    that is no multiple of four, among them."""
     orc, synth = env["orc"], env["synth"]
     gd = orc.GEOMS[gname]
     g, geom, _ = _geom(env, gname)
@@ -132,22 +116,15 @@ def test_forced_window_kernel_on_every_shipped_geometry(env, gname):
     frames[1] = _ring_order(frames[1], g.H)
     frames[3] = frames[3][:1500].copy()
     want = [orc.project(f, g) for f in frames]
-    for flags in (PROBE, FORCE):
-        ri, acc = _project(env, frames, geom, flags)
+    for rows in (False, True):
+        ri = _project(env, frames, geom, rows=rows)
         for i in range(len(frames)):
-            assert _beq(ri[i], want[i]), (flags, i)
-        if g.W % 4:
-            assert list(acc) == [0] * 5
-        elif flags == FORCE:
-            assert list(acc) == [1] * 5
-        else:
-            assert acc[1] == 1 and acc[3] == 0
+            assert _beq(ri[i], want[i]), (rows, i)
 
 
-def test_fused_batch_mixes_accepted_and_rejected_frames(env):
-    """rpcc_compress_batch on a batch that interleaves ring-ordered sweeps (window kernel), shuffled ones (records) and a frame with a
-    depth-0 point, ground fitted inside (the candidate counts and bytes the projection hands to the ground fit come from either kernel):
-    every output equals the same call without the probe, and the oracle."""
+def test_fused_batch_mixes_point_orders(env):
+    """rpcc_compress_batch on a batch that interleaves ring-ordered sweeps, shuffled ones, a frame with a depth-0 point and one with late
+    points, ground fitted inside (on the candidate counts and bytes the projection hands over): every output equals the oracle's."""
     torch, ops, orc, synth = env["torch"], env["ops"], env["orc"], env["synth"]
     gb = orc.LidarGeom(H=64, W=2048, hfov_deg=360, vmax_deg=2.0, vmin_deg=-24.9)
     geomb = ops.make_geom(gb.H, gb.W, gb.horizontal_FOV, gb.vertical_max, gb.vertical_min)
@@ -157,37 +134,30 @@ def test_fused_batch_mixes_accepted_and_rejected_frames(env):
         f = synth.make_frame(900 + i, 64, 2048).numpy()
         frames.append(_ring_order(f) if i % 3 != 1 else f)
     frames[6] = frames[6].copy(); frames[6][777] = 0
-    frames[9] = np.concatenate([frames[9], frames[9][:20000] * np.float32(0.9)])     # late points: rows re-opened, candidate counts taken back
+    frames[9] = np.concatenate([frames[9], frames[9][:20000] * np.float32(0.9)])     # late points: rows revisited, candidate counts change
     offs = np.zeros(len(frames) + 1, np.int64)
     offs[1:] = np.cumsum([f.shape[0] for f in frames])
     xyz = _to(env, np.concatenate(frames))
     fid = torch.arange(100, 100 + len(frames), dtype=torch.int64, device=env["dev"])
-    outs = []
-    for flags in (PROBE, 0, FORCE):
-        buf = ops.BatchBuffers(len(frames), geomb, 100, env["dev"])
-        gms = torch.zeros((len(frames), 4), dtype=torch.float64, device=env["dev"])
-        ops.compress_batch(xyz, _to(env, offs), _to(env, tm), gms, buf, ground_seed=3, frame_ids=fid, project_flags=flags)
-        torch.cuda.synchronize()
-        outs.append(dict(ri=buf.ri.cpu().numpy().copy(), gm=gms.cpu().numpy().copy(), seg=buf.seg.cpu().numpy().copy(), pix=buf.cen_pix.cpu().numpy().copy(),
-                         nnz=buf.nnz.cpu().numpy().copy(), q=buf.q16.cpu().numpy().copy(), model=buf.model.cpu().numpy().copy()))
-    for o in outs[1:]:
-        assert _beq(o["ri"], outs[0]["ri"]) and _beq(o["gm"], outs[0]["gm"]) and np.array_equal(o["seg"], outs[0]["seg"])
-        assert np.array_equal(o["pix"], outs[0]["pix"]) and np.array_equal(o["nnz"], outs[0]["nnz"]) and _beq(o["model"], outs[0]["model"])
-        assert all(np.array_equal(o["q"][i, :o["nnz"][i]], outs[0]["q"][i, :o["nnz"][i]]) for i in range(len(frames)))
+    buf = ops.BatchBuffers(len(frames), geomb, 100, env["dev"])
+    gms = torch.zeros((len(frames), 4), dtype=torch.float64, device=env["dev"])
+    ops.compress_batch(xyz, _to(env, offs), _to(env, tm), gms, buf, ground_seed=3, frame_ids=fid)
+    torch.cuda.synchronize()
+    out = dict(ri=buf.ri.cpu().numpy(), gm=gms.cpu().numpy(), seg=buf.seg.cpu().numpy(), nnz=buf.nnz.cpu().numpy(), q=buf.q16.cpu().numpy())
     for i in (0, 1, 6, 9):
         ri = orc.project(frames[i], gb)
         gm = orc.ground_model(ri, tm, seed=3 + 100 + i)
         o = orc.compress_frame(frames[i], gb, tm, gm)
-        assert _beq(outs[0]["ri"][i], o["range_image"]) and _beq(outs[0]["gm"][i], np.asarray(gm, np.float64)), i
-        assert np.array_equal(outs[0]["seg"][i].reshape(-1), o["seg_idx"].reshape(-1).astype(np.uint8)), i
-        assert np.array_equal(outs[0]["q"][i, :outs[0]["nnz"][i]], o["q"].astype(np.int16)), i
+        assert _beq(out["ri"][i], o["range_image"]) and _beq(out["gm"][i], np.asarray(gm, np.float64)), i
+        assert np.array_equal(out["seg"][i].reshape(-1), o["seg_idx"].reshape(-1).astype(np.uint8)), i
+        assert np.array_equal(out["q"][i, :out["nnz"][i]], o["q"].astype(np.int16)), i
 
 
 def test_random_orders_and_shapes(env):
-    """Random batches through the probe and through the forced window kernel against the record kernels: frames of 1 .. 30 000 points, sorted by
-    ring, by column, partly sorted, shuffled; duplicates; depth-0 points; four image shapes (whole image in the window, 2 and 4 windows per
-    image, 128 rows)."""
-    torch, ops, orc = env["torch"], env["ops"], env["orc"]
+    """Random batches through the record kernels against the device-atomic path (every point by the exact sequence): frames of 1 .. 30 000
+    points, sorted by ring, by column, partly sorted, shuffled; duplicates; depth-0 points; six image shapes (up to 128 rows); both point
+    layouts.  A sample also against the oracle."""
+    ops, orc = env["ops"], env["orc"]
     rng = np.random.default_rng(606)
     shapes = [(16, 1800, 15.0, -15.0), (64, 2000, 2.0, -24.9), (64, 2048, 2.0, -24.9), (128, 2048, 15.0, -25.0), (40, 1024, 10.0, -20.0), (8, 16, 10.0, -10.0)]
     for draw in range(36):
@@ -216,10 +186,9 @@ def test_random_orders_and_shapes(env):
             if n > 10 and rng.random() < 0.25:
                 a[rng.integers(0, n, 2)] = 0
             frames.append(a)
-        ref, _ = _project(env, frames, geom, 0)
-        for flags in (PROBE, FORCE):
-            ri, acc = _project(env, frames, geom, flags, rows=bool(draw & 1))
-            assert _beq(ri, ref), (draw, H, W, B, flags, acc)
+        ref = _project(env, frames, geom, atomic_path=True)
+        ri = _project(env, frames, geom, rows=bool(draw & 1))
+        assert _beq(ri, ref), (draw, H, W, B)
         if draw % 6 == 0:
             i = int(rng.integers(0, B))
-            assert _beq(ref[i], orc.project(frames[i], g)), (draw, i)
+            assert _beq(ri[i], orc.project(frames[i], g)), (draw, i)

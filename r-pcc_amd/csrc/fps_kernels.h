@@ -66,6 +66,10 @@ struct FpsLds {
 };
 static inline size_t fps_tiled_lds_bytes(int T) { return (size_t)T * 50 + 64; }
 #define FPS_TILED_MAX_TILES 3200  // 50 B/tile must fit the 160 KiB LDS of one CU
+// A frame the tile-pruned kernels take has at most FPS_TILED_MAX_TILES * FPS_TILE = 819 200 points: every point index fits the 22 bits of the
+// packed tile origin (FpsLds::cx4), every byte offset into an xyz list or a [P,3] ray table 32 bits.  The tile bound is the ONLY condition.
+static_assert(FPS_TILED_MAX_TILES * FPS_TILE <= (1 << 22) && FPS_TILED_MAX_TILES * FPS_TILE <= (1 << 30) / 3, "a tile-pruned frame's indices and offsets");
+static inline bool fps_prunable(const FpsTiling &g) { return g.T <= FPS_TILED_MAX_TILES; }
 
 // One lane's share of a tile: four consecutive points.
 struct FpsQuad {
@@ -198,6 +202,47 @@ __device__ __forceinline__ void fps_load_point(const float *__restrict__ src, co
     }
 }
 
+struct FpsTileOut { float lo[3], hi[3], wt, wx, wy, wz; uint32_t widx; };
+
+// update of one tile against centre (c0,c1,c2): returns true (wave-uniform) when its table entry changed (always with
+// with_box); the new entry comes back in `o`.  viol: an empty pixel is not what the origin class assumes (first pass only).
+template <bool RANGE, bool VEC, bool EDGE = false>
+__device__ __forceinline__ bool fps_tile_update(const FpsQuad &q, bool org_on, float t_org0, float c0, float c1, float c2,
+                                                float *__restrict__ temp, bool with_box, FpsTileOut &o, bool &viol) {
+    float x[4], y[4], z[4], nt[4];
+    uint32_t key[4];
+    bool cand[4], ch = false;
+    fps_quad_xyz(q, RANGE, x, y, z);
+    const bool lane_ok = q.nval > 0;   // VEC without EDGE: a lane's four elements are inside the frame together
+    constexpr bool QUAD = VEC && !EDGE;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        float tp = (QUAD ? lane_ok : e < q.nval) ? q.tp[e] : -1.0f;
+        if (RANGE && org_on && q.r[e] == 0.0f) {   // member of the origin class: carried by t_org
+            if (with_box) viol |= (QUAD ? lane_ok : e < q.nval) && tp != t_org0;
+            tp = -1.0f;
+        }
+        cand[e] = tp >= 0.0f;
+        const float dx = x[e] - c0, dy = y[e] - c1, dz = z[e] - c2;
+        const float d = (dx * dx + dy * dy) + dz * dz;  // sampling_gpu.cu:64, un-fused
+        nt[e] = d < tp ? d : tp;  // == fminf(d, tp): a NaN distance keeps tp, tp itself is never NaN
+        key[e] = fps_val_key(nt[e]);
+        const bool c = nt[e] != tp;
+        ch |= c;
+        if ((!VEC || (EDGE && q.nval != 4)) && c) st_f32(temp, (uint32_t)(q.p0 + e) * 4u, nt[e]);   // (c implies a valid element)
+        if (!c) nt[e] = q.tp[e];   // value to write back for an unchanged element
+    }
+    if (QUAD && ch) st_at(reinterpret_cast<float4 *>(temp), (uint32_t)q.p0 * 4u, make_float4(nt[0], nt[1], nt[2], nt[3]));
+    if (VEC && EDGE && ch && q.nval == 4) st_quad<true>(temp, (uint32_t)q.p0 * 4u, nt[0], nt[1], nt[2], nt[3]);
+    if (!with_box && __ballot(ch) == 0ull) return false;
+    // (Leaving the arg-max out when the point that holds the tile's maximum did not change -- the entry is then provably what it
+    // was -- was measured in round 3: the holder has the largest temp of the tile, so it is the FIRST point a centre in reach
+    // lowers; the test fired rarely, cost four compares per visit, and the kernel got 2 % slower.)
+    if (with_box) fps_tile_box(x, y, z, cand, o.lo, o.hi);
+    fps_tile_argmax(x, y, z, key, q.p0, o.wt, o.wx, o.wy, o.wz, o.widx);
+    return true;
+}
+
 #define FPS_THREADS 1024
 
 // Threads of the tile-pruned FPS workgroup (one workgroup per frame): FPS_TT_BATCH for batches that fill the chip
@@ -275,43 +320,19 @@ __global__ __launch_bounds__(FPS_TT) void fps_tiled_kernel(const float *__restri
             q.p0 = q.nval > 0 ? p : 0;
         }
     };
-    // distance update against the current centre, tile maximum, (optionally) bounding box and the check that the
-    // origin class is what the header says (all empty pixels candidates with one common temp)
+    // distance update against the current centre, tile maximum, (optionally) bounding box and the check that the origin class is what the
+    // header says: fps_tile_update, the routine of the register-table kernel; here the new entry goes to the LDS table.  (With VEC it keys an
+    // element's validity on the lane's nval > 0, not on e < nval.  The same thing here: VEC is only chosen with W % 4 == 0 -- N % 4 == 0 for
+    // lists --, so a lane's quad is whole or empty.)
     auto compute_tile = [&](int t, const FpsQuad &q, bool with_box) {
-        float x[4], y[4], z[4], nt[4];
-        uint32_t key[4];
-        bool cand[4], ch = false, viol = false;
-        fps_quad_xyz(q, RANGE, x, y, z);
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            float tp = e < q.nval ? q.tp[e] : -1.0f;
-            if (RANGE && org_on && q.r[e] == 0.0f) {   // member of the origin class: carried by t_org
-                if (with_box) viol |= e < q.nval && tp != t_org0;
-                tp = -1.0f;
-            }
-            cand[e] = tp >= 0.0f;
-            const float dx = x[e] - c0, dy = y[e] - c1, dz = z[e] - c2;
-            const float d = (dx * dx + dy * dy) + dz * dz;  // sampling_gpu.cu:64, un-fused
-            nt[e] = d < tp ? d : tp;  // == fminf(d, tp): a NaN distance keeps tp, tp itself is never NaN
-            key[e] = fps_val_key(nt[e]);
-            const bool c = nt[e] != tp;
-            ch |= c;
-            if (!VEC && c) st_f32(temp, (uint32_t)(q.p0 + e) * 4u, nt[e]);
-            if (!c) nt[e] = q.tp[e];   // value to write back for an unchanged element
-        }
-        if (VEC && ch) st_at(reinterpret_cast<float4 *>(temp), (uint32_t)q.p0 * 4u, make_float4(nt[0], nt[1], nt[2], nt[3]));
-        if (with_box && __ballot(viol) != 0ull && lane == 0) s_viol = 1;
+        FpsTileOut o;
+        bool viol = false;
         // nothing changed in this tile: its table entry (maximum, arg, coordinates) is still exact
-        if (!with_box && __ballot(ch) == 0ull) return;
-        if (with_box) {
-            float lo[3], hi[3];
-            fps_tile_box(x, y, z, cand, lo, hi);
-            if (lane == 0) { L.lo4[t].x = lo[0]; L.lo4[t].y = lo[1]; L.lo4[t].z = lo[2]; L.hi4[t].x = hi[0]; L.hi4[t].y = hi[1]; L.hi4[t].z = hi[2]; }
-        }
-        float wt, wx, wy, wz;
-        uint32_t widx;
-        fps_tile_argmax(x, y, z, key, q.p0, wt, wx, wy, wz, widx);
-        if (lane == 0) { L.lo4[t].w = wt; L.hi4[t].w = u2f(widx); L.cx4[t].x = wx; L.cx4[t].y = wy; L.cx4[t].z = wz; }
+        if (!fps_tile_update<RANGE, VEC>(q, org_on, t_org0, c0, c1, c2, temp, with_box, o, viol)) return;
+        if (with_box && __ballot(viol) != 0ull && lane == 0) s_viol = 1;
+        if (lane != 0) return;
+        if (with_box) { L.lo4[t].x = o.lo[0]; L.lo4[t].y = o.lo[1]; L.lo4[t].z = o.lo[2]; L.hi4[t].x = o.hi[0]; L.hi4[t].y = o.hi[1]; L.hi4[t].z = o.hi[2]; }
+        L.lo4[t].w = o.wt; L.hi4[t].w = u2f(o.widx); L.cx4[t].x = o.wx; L.cx4[t].y = o.wy; L.cx4[t].z = o.wz;
     };
     auto update_origin = [&]() {
         if (org_on) {
@@ -444,7 +465,7 @@ __global__ __launch_bounds__(FPS_TT) void fps_tiled_kernel(const float *__restri
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Register-table form (the default whenever the frame has at most 64 tiles per wavefront of the workgroup).
+// Register-table form (the default; which frames take it: fps_pick_range in rpcc_hip.hip).
 // The per-iteration chain of the kernel above is  test -> work list -> barrier -> tile loads -> update -> barrier ->
 // table scan -> barrier: three barriers and five dependent LDS round trips around ~1200 cycles of load latency.  Here
 // every tile belongs to ONE lane of ONE wavefront for the whole launch: its box, maximum, arg and coordinates live in that
@@ -455,47 +476,6 @@ __global__ __launch_bounds__(FPS_TT) void fps_tiled_kernel(const float *__restri
 // Tiles are dealt to the wavefronts round-robin in an order that is skewed from tile-row to tile-row, so the tiles around
 // a new centre (horizontal and vertical neighbours) belong to different wavefronts.  Same arithmetic, same results.
 // ------------------------------------------------------------------------------------------------------------------
-struct FpsTileOut { float lo[3], hi[3], wt, wx, wy, wz; uint32_t widx; };
-
-// update of one tile against centre (c0,c1,c2): returns true (wave-uniform) when its table entry changed (always with
-// with_box); the new entry comes back in `o`.  viol: an empty pixel is not what the origin class assumes (first pass only).
-template <bool RANGE, bool VEC, bool EDGE = false>
-__device__ __forceinline__ bool fps_tile_update(const FpsQuad &q, bool org_on, float t_org0, float c0, float c1, float c2,
-                                                float *__restrict__ temp, bool with_box, FpsTileOut &o, bool &viol) {
-    float x[4], y[4], z[4], nt[4];
-    uint32_t key[4];
-    bool cand[4], ch = false;
-    fps_quad_xyz(q, RANGE, x, y, z);
-    const bool lane_ok = q.nval > 0;   // VEC without EDGE: a lane's four elements are inside the frame together
-    constexpr bool QUAD = VEC && !EDGE;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        float tp = (QUAD ? lane_ok : e < q.nval) ? q.tp[e] : -1.0f;
-        if (RANGE && org_on && q.r[e] == 0.0f) {   // member of the origin class: carried by t_org
-            if (with_box) viol |= (QUAD ? lane_ok : e < q.nval) && tp != t_org0;
-            tp = -1.0f;
-        }
-        cand[e] = tp >= 0.0f;
-        const float dx = x[e] - c0, dy = y[e] - c1, dz = z[e] - c2;
-        const float d = (dx * dx + dy * dy) + dz * dz;  // sampling_gpu.cu:64, un-fused
-        nt[e] = d < tp ? d : tp;  // == fminf(d, tp): a NaN distance keeps tp, tp itself is never NaN
-        key[e] = fps_val_key(nt[e]);
-        const bool c = nt[e] != tp;
-        ch |= c;
-        if ((!VEC || (EDGE && q.nval != 4)) && c) st_f32(temp, (uint32_t)(q.p0 + e) * 4u, nt[e]);   // (c implies a valid element)
-        if (!c) nt[e] = q.tp[e];   // value to write back for an unchanged element
-    }
-    if (QUAD && ch) st_at(reinterpret_cast<float4 *>(temp), (uint32_t)q.p0 * 4u, make_float4(nt[0], nt[1], nt[2], nt[3]));
-    if (VEC && EDGE && ch && q.nval == 4) st_quad<true>(temp, (uint32_t)q.p0 * 4u, nt[0], nt[1], nt[2], nt[3]);
-    if (!with_box && __ballot(ch) == 0ull) return false;
-    // (Leaving the arg-max out when the point that holds the tile's maximum did not change -- the entry is then provably what it
-    // was -- was measured in round 3: the holder has the largest temp of the tile, so it is the FIRST point a centre in reach
-    // lowers; the test fired rarely, cost four compares per visit, and the kernel got 2 % slower.)
-    if (with_box) fps_tile_box(x, y, z, cand, o.lo, o.hi);
-    fps_tile_argmax(x, y, z, key, q.p0, o.wt, o.wx, o.wy, o.wz, o.widx);
-    return true;
-}
-
 // TPL: tiles per lane (1; 2 for images with more tiles than the workgroup has lanes -- 80 x 2000, 128 x 2048: slot s of lane l is position (l + 64 s) NW + wave).
 // (Round 5 ran the headline with 4 / 2 / 1 wavefronts per frame and 2 / 4 / 8 tiles per lane: every step towards fewer wavefronts is slower, profiles/HISTORY.md.)
 template <bool RANGE, bool VEC, int FPS_TT, bool SOA, bool EDGE = false, int TPL = 1>

@@ -1867,6 +1867,10 @@ __global__ __launch_bounds__(256) void ground_mask_kernel(float *__restrict__ ri
 
 // tiletab: dev float4 [B][3][T] (T = tiles of fps_tiling_range(H,W)) or NULL
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+// a range image's quads (four consecutive pixels of ri, temp and the [P,3] ray table) can be accessed 16 bytes at a time, 16-byte aligned
+static inline bool range_quads16(int W, const float *ri, const float *temp, const float *tm) {
+    return (W % 4 == 0) && aligned16(ri) && aligned16(temp) && aligned16(tm);
+}
 // What the label type decides on the host: the cluster limit of the tuned label kernels and the alignment of a 4-pixel load of seg (the VEC variants).
 template <class L>
 struct LabelTraits {
@@ -1884,7 +1888,7 @@ static int launch_ground_mask(float *ri, const float *tm, const double *ground, 
     if (tiletab) {
         const FpsTiling g = fps_tiling_range(H, W);
         const dim3 grid((g.T + MASK_WAVES * TAB_TPW - 1) / (MASK_WAVES * TAB_TPW), B);
-        const bool vec = (W % 4 == 0) && aligned16(ri) && aligned16(temp) && aligned16(tm);
+        const bool vec = range_quads16(W, ri, temp, tm);
 #define GM_LAUNCH(RAW_, EDGE_) ground_mask_tab_kernel<RAW_, true, EDGE_><<<grid, 64 * MASK_WAVES, 0, st>>>(ri, tm, ground, thr, g, temp, info, tiletab)
         // (a width that is no multiple of four, or buffers that are not 16-byte aligned: the same quad layout at 4-byte alignment)
         if (raw) { if (vec) GM_LAUNCH(true, false); else GM_LAUNCH(true, true); }
@@ -1908,7 +1912,7 @@ static inline size_t fps_tab_bound_bytes(int B, int P) { return (size_t)B * FPS_
 extern "C" int rpcc_ground_mask(const float *ri, const float *tm, const double *ground, double threshold, int B, int H,
                                 int W, float *temp, int32_t *info, void *fps_table, void *stream) {
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && ri && tm && ground && temp && info);
-    ARG_TRY(fps_table == nullptr || fps_tiling_range(H, W).T <= FPS_TILED_MAX_TILES);
+    ARG_TRY(fps_table == nullptr || fps_prunable(fps_tiling_range(H, W)));
     return launch_ground_mask(const_cast<float *>(ri), tm, ground, threshold, B, H, W, temp, info,
                               reinterpret_cast<float *>(fps_table), (hipStream_t)stream, false);
 }
@@ -2221,67 +2225,60 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_modes_kernel(const float *__r
     }
 }
 
-template <bool RANGE>
-static int launch_fps_tiled(const float *src, const float *rays, float *temp, const int32_t *info, int B, const FpsTiling &g,
-                            int M, int kflags, int32_t *idx, float *cen, const float *tiletab, bool vec, hipStream_t st,
-                            const float *rays_soa = nullptr, bool edge = false) {
-    // edge (range images only): the width is no multiple of four -- the quad kernels run with 4-byte aligned 16-byte accesses
-    const size_t sh = fps_tiled_lds_bytes(g.T);
-    // register-table form: every tile owned by one lane (at most 64 tiles per wavefront)
-#define FPS_RT_LAUNCH(VEC_, TT_) fps_regtab_kernel<RANGE, VEC_, TT_><<<B, TT_, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab)
-    {
-        const int tt = B <= 128 ? FPS_TT_SMALL : FPS_TT_BATCH;
-        if constexpr (RANGE) if (g.T <= tt && (vec || edge) && rays_soa != nullptr) {   // planar copy of the ray table (the fused batch has one)
-            if (edge) {
-                if (B <= 128) fps_regtab_planar_kernel<FPS_TT_SMALL, true><<<B, FPS_TT_SMALL, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab, rays_soa);
-                else          fps_regtab_planar_kernel<FPS_TT_BATCH, true><<<B, FPS_TT_BATCH, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab, rays_soa);
-            } else {
-                if (B <= 128) fps_regtab_planar_kernel<FPS_TT_SMALL><<<B, FPS_TT_SMALL, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab, rays_soa);
-                else          fps_regtab_planar_kernel<FPS_TT_BATCH><<<B, FPS_TT_BATCH, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab, rays_soa);
-            }
-            LAUNCH_CHECK();
-            return RPCC_OK;
-        }
-        if constexpr (RANGE) if (g.T > tt && g.T <= 2 * tt && (vec || edge) && rays_soa != nullptr) {   // two tiles per lane
-            if (edge) {
-                if (B <= 128) fps_regtab_planar2_kernel<FPS_TT_SMALL, true><<<B, FPS_TT_SMALL, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab, rays_soa);
-                else          fps_regtab_planar2_kernel<FPS_TT_BATCH, true><<<B, FPS_TT_BATCH, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab, rays_soa);
-            } else {
-                if (B <= 128) fps_regtab_planar2_kernel<FPS_TT_SMALL><<<B, FPS_TT_SMALL, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab, rays_soa);
-                else          fps_regtab_planar2_kernel<FPS_TT_BATCH><<<B, FPS_TT_BATCH, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab, rays_soa);
-            }
-            LAUNCH_CHECK();
-            return RPCC_OK;
-        }
-        if constexpr (RANGE) if (g.T <= tt && edge) {
-            if (B <= 128) fps_regtab_kernel<true, true, FPS_TT_SMALL, true><<<B, FPS_TT_SMALL, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab);
-            else          fps_regtab_kernel<true, true, FPS_TT_BATCH, true><<<B, FPS_TT_BATCH, 0, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab);
-            LAUNCH_CHECK();
-            return RPCC_OK;
-        }
-        if (g.T <= tt) {
-            if (B <= 128) { if (vec) FPS_RT_LAUNCH(true, FPS_TT_SMALL); else FPS_RT_LAUNCH(false, FPS_TT_SMALL); }
-            else          { if (vec) FPS_RT_LAUNCH(true, FPS_TT_BATCH); else FPS_RT_LAUNCH(false, FPS_TT_BATCH); }
-            LAUNCH_CHECK();
-            return RPCC_OK;
-        }
+#define RPCC_FPS_MODE_BITS (RPCC_FPS_FMA1 | RPCC_FPS_FMA2 | RPCC_FPS_TIE_CUDA)
+static inline int fps_fma_of(int flags) { return (flags & RPCC_FPS_FMA1) ? 1 : (flags & RPCC_FPS_FMA2) ? 2 : 0; }
+
+// ---- which FPS kernel a call takes (the one place that decides it; DESIGN.md "FPS") -------------------------------------------------
+//   1. a CUDA-binary mode flag                                   -> fps_modes_kernel (the reference kernel, one pass per centre)
+//   2. RPCC_FPS_BRUTEFORCE, or more than FPS_TILED_MAX_TILES tiles -> one pass per centre (fps_range_kernel / fps_xyz_kernel)
+//   3. otherwise a tile-pruned kernel -- the only case in which an FPS tile table exists (rpcc_ground_mask fills it, these kernels read it).
+//      One workgroup per frame of FPS_TT_SMALL threads when the launch has at most 128 frames (nothing to co-schedule with), else FPS_TT_BATCH;
+//      with T tiles per frame and the planar copy of the ray table at hand (the fused batch has one, the stage entries and lists do not):
+//        planar, T <= threads      -> fps_regtab_planar_kernel      (tile table in registers, one tile per lane)
+//        planar, T <= 2 * threads  -> fps_regtab_planar2_kernel     (two tiles per lane)
+//        no planar, T <= threads   -> fps_regtab_kernel
+//        more tiles                -> fps_tiled_kernel              (tile table in LDS)
+//      Accesses: 16 bytes at a time when range_quads16 holds (lists: N % 4 == 0 and aligned arrays); otherwise `unaligned`: the register-table
+//      kernels of a range image keep the quads at 4-byte alignment (EDGE), the LDS-table kernel and the lists' kernels go element by element.
+enum FpsFamily { FPS_MODES, FPS_ONE_PASS, FPS_LDS_TABLE, FPS_REG_TABLE, FPS_PLANAR, FPS_PLANAR2 };
+struct FpsPick { FpsFamily family; int threads; bool unaligned; };
+static inline bool fps_pruned(const FpsPick &k) { return k.family >= FPS_LDS_TABLE; }
+static FpsPick fps_pick_pruned(const FpsTiling &g, int frames, bool quads16, bool planar) {
+    const int tt = frames <= 128 ? FPS_TT_SMALL : FPS_TT_BATCH;
+    const FpsFamily f = g.T > (planar ? 2 : 1) * tt ? FPS_LDS_TABLE : !planar ? FPS_REG_TABLE : g.T <= tt ? FPS_PLANAR : FPS_PLANAR2;
+    return {f, tt, !quads16};
+}
+// frames: the frames that share the launch.  Whether the pick is pruned at all (rules 1 and 2) depends on H, W and the flags alone.
+static FpsPick fps_pick_range(int H, int W, int frames, int flags, bool quads16, bool planar) {
+    const FpsTiling g = fps_tiling_range(H, W);
+    if (flags & RPCC_FPS_MODE_BITS) return {FPS_MODES, FPS_THREADS, false};
+    if ((flags & RPCC_FPS_BRUTEFORCE) || !fps_prunable(g)) return {FPS_ONE_PASS, FPS_THREADS, false};
+    return fps_pick_pruned(g, frames, quads16, planar);
+}
+
+// the launch of a tile-pruned pick: each family once, thread count and access form as template arguments
+template <bool RANGE, int TT, bool VEC>
+static int launch_fps_family(FpsFamily family, const FpsGroupArgs &a, int B, int M, int kflags, hipStream_t st) {
+    if constexpr (RANGE) {   // (the register-table kernels of a range image: VEC always, EDGE when the quads are not 16-byte aligned)
+        if (family == FPS_PLANAR) fps_regtab_planar_kernel<TT, !VEC><<<B, TT, 0, st>>>(a.src, a.rays, a.temp, a.info, a.g, M, kflags, a.out_idx, a.out_cen, a.tiletab, a.rays_soa);
+        if (family == FPS_PLANAR2) fps_regtab_planar2_kernel<TT, !VEC><<<B, TT, 0, st>>>(a.src, a.rays, a.temp, a.info, a.g, M, kflags, a.out_idx, a.out_cen, a.tiletab, a.rays_soa);
     }
-#undef FPS_RT_LAUNCH
-#define FPS_LAUNCH(VEC_, TT_)                                                                                        \
-    do {                                                                                                             \
-        HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&fps_tiled_kernel<RANGE, VEC_, TT_>), (int)sh));       \
-        fps_tiled_kernel<RANGE, VEC_, TT_><<<B, TT_, sh, st>>>(src, rays, temp, info, g, M, kflags, idx, cen, tiletab); \
-    } while (0)
-    if (B <= 128) { if (vec) FPS_LAUNCH(true, FPS_TT_SMALL); else FPS_LAUNCH(false, FPS_TT_SMALL); }
-    else          { if (vec) FPS_LAUNCH(true, FPS_TT_BATCH); else FPS_LAUNCH(false, FPS_TT_BATCH); }
-#undef FPS_LAUNCH
+    if (family == FPS_REG_TABLE)
+        fps_regtab_kernel<RANGE, RANGE || VEC, TT, RANGE && !VEC><<<B, TT, 0, st>>>(a.src, a.rays, a.temp, a.info, a.g, M, kflags, a.out_idx, a.out_cen, a.tiletab);
+    if (family == FPS_LDS_TABLE) {
+        const size_t sh = fps_tiled_lds_bytes(a.g.T);
+        HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&fps_tiled_kernel<RANGE, VEC, TT>), (int)sh));
+        fps_tiled_kernel<RANGE, VEC, TT><<<B, TT, sh, st>>>(a.src, a.rays, a.temp, a.info, a.g, M, kflags, a.out_idx, a.out_cen, a.tiletab);
+    }
     LAUNCH_CHECK();
     return RPCC_OK;
 }
-
-#define FPS_SOA 1   // the fused batch hands the planar copy of the ray table to the FPS kernel
-#define RPCC_FPS_MODE_BITS (RPCC_FPS_FMA1 | RPCC_FPS_FMA2 | RPCC_FPS_TIE_CUDA)
-static inline int fps_fma_of(int flags) { return (flags & RPCC_FPS_FMA1) ? 1 : (flags & RPCC_FPS_FMA2) ? 2 : 0; }
+template <bool RANGE>
+static int launch_fps_tiled(const FpsPick &k, const FpsGroupArgs &a, int B, int M, int kflags, hipStream_t st) {
+    if (k.threads == FPS_TT_SMALL)
+        return k.unaligned ? launch_fps_family<RANGE, FPS_TT_SMALL, false>(k.family, a, B, M, kflags, st) : launch_fps_family<RANGE, FPS_TT_SMALL, true>(k.family, a, B, M, kflags, st);
+    return k.unaligned ? launch_fps_family<RANGE, FPS_TT_BATCH, false>(k.family, a, B, M, kflags, st) : launch_fps_family<RANGE, FPS_TT_BATCH, true>(k.family, a, B, M, kflags, st);
+}
 
 static int fps_xyz_impl(int B, int N, int M, const float *points, float *temp, int32_t *idx, bool brute, hipStream_t st, int flags = 0) {
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && N > 0 && M >= 0 && points && temp && idx);
@@ -2296,11 +2293,11 @@ static int fps_xyz_impl(int B, int N, int M, const float *points, float *temp, i
     const FpsTiling g = fps_tiling_list(N);
     const bool vec = (N % 4 == 0) && aligned16(points) && aligned16(temp);
     int probed = 0;
-    if (!brute && g.T <= FPS_TILED_MAX_TILES && N < (1 << 30) / 3) {
+    if (!brute && fps_prunable(g)) {
         // every list takes the kernel its order suits: the probe marks idx[b][0], the pruned kernel skips the marked lists, the streamed one the others
         fps_list_probe_kernel<<<B, 256, 0, st>>>(points, N, M, g.T, idx);
         LAUNCH_CHECK();
-        const int rc = launch_fps_tiled<false>(points, nullptr, temp, nullptr, B, g, M, FPS_FLAG_PROBED, idx, nullptr, nullptr, vec, st);
+        const int rc = launch_fps_tiled<false>(fps_pick_pruned(g, B, vec, false), {points, nullptr, temp, nullptr, g, idx, nullptr, nullptr, nullptr}, B, M, FPS_FLAG_PROBED, st);
         if (rc != RPCC_OK) return rc;
         probed = 1;
     }
@@ -2331,9 +2328,8 @@ static int launch_fps_range(const float *ri, const float *tm, float *temp, const
                             int32_t *cen_pix, float *centers, int flags, bool finalize_temp, const float *tiletab,
                             void *timer, hipStream_t st, const float *rays_soa = nullptr) {
     const int P = H * W;
-    const FpsTiling g = fps_tiling_range(H, W);
-    const bool brute = (flags & RPCC_FPS_BRUTEFORCE) != 0;
-    if (flags & RPCC_FPS_MODE_BITS) {   // CUDA-binary modes (contraction / tree tie rule): the reference kernel, one pass per centre
+    const FpsPick k = fps_pick_range(H, W, B, flags, range_quads16(W, ri, temp, tm), rays_soa != nullptr);
+    if (k.family == FPS_MODES) {   // CUDA-binary modes (contraction / tree tie rule)
         if ((flags & RPCC_FPS_FMA1) && (flags & RPCC_FPS_FMA2)) return set_err(RPCC_ERR_ARG, "fps: RPCC_FPS_FMA1 and RPCC_FPS_FMA2 exclude each other%s%s");
         if (tiletab != nullptr) return set_err(RPCC_ERR_ARG, "fps: the FPS table of rpcc_ground_mask holds un-fused first-pass distances; pass NULL with a mode flag%s%s");
         FpsTimer tmr(st, timer);
@@ -2342,15 +2338,14 @@ static int launch_fps_range(const float *ri, const float *tm, float *temp, const
         LAUNCH_CHECK();
         return RPCC_OK;
     }
-    if (!brute && g.T <= FPS_TILED_MAX_TILES && P < (1 << 22)) {
-        const bool vec = (W % 4 == 0) && aligned16(ri) && aligned16(temp) && aligned16(tm);
+    if (fps_pruned(k)) {
         FpsTimer tmr(st, timer);
-        return launch_fps_tiled<true>(ri, tm, temp, info, B, g, M, finalize_temp ? FPS_FLAG_FINALIZE_TEMP : 0, cen_pix, centers,
-                                      tiletab, vec, st, rays_soa, !vec);
+        return launch_fps_tiled<true>(k, {ri, tm, temp, info, fps_tiling_range(H, W), cen_pix, centers, tiletab, rays_soa}, B, M,
+                                      finalize_temp ? FPS_FLAG_FINALIZE_TEMP : 0, st);
     }
-    if (tiletab != nullptr && !brute)
+    if (tiletab != nullptr && !(flags & RPCC_FPS_BRUTEFORCE))
         return set_err(RPCC_ERR_ARG, "fps_range: an FPS table was produced but the tiled kernel cannot run (image too large)%s%s");
-    if (P % 4 != 0 || !aligned16(ri) || !aligned16(temp) || !aligned16(tm))
+    if (!range_quads16(P, ri, temp, tm))
         return set_err(RPCC_ERR_ARG, "fps_range brute-force path needs 16-byte aligned buffers and P %% 4 == 0%s%s");
     FpsTimer tmr(st, timer);
     fps_range_kernel<<<B, FPS_THREADS, 0, st>>>(ri, tm, temp, info, P, M, cen_pix, centers);
@@ -3623,7 +3618,7 @@ extern "C" int rpcc_plane_model_wide(const float *ri, const float *tm, const uin
 struct BatchPlan : BatchLayout {
     const rpcc_batch_io *io;
     int Bs, M, P; int64_t npts; rpcc_geom g; double ground_threshold; float acc; char *ws;
-    bool fit_ground, brute, tiled;
+    bool fit_ground, tiled;   // tiled: the FPS is tile-pruned, so the mask kernel fills the tile table
     int32_t *zcnt;
     BatchInit bi;
 };
@@ -3642,8 +3637,7 @@ static int plan_batch(BatchPlan &p, const rpcc_batch_io *io, int Bs, int64_t npt
     p.bi.z1 = {reinterpret_cast<uint32_t *>(p.L.sums), (int)(((char *)p.L.hist - (char *)p.L.sums) / 4)};
     if (!io->nonuniform) { p.label_acc = nullptr; p.kpn = nullptr; }
     p.bi.z2 = {reinterpret_cast<uint32_t *>(p.kpn), p.kpn ? Bs * (M + 2) : 0};  // key points per label
-    p.brute = (io->flags & (RPCC_FPS_BRUTEFORCE | RPCC_FPS_MODE_BITS)) != 0;   // a mode flag selects the reference kernel too
-    p.tiled = !p.brute && fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES;
+    p.tiled = fps_pruned(fps_pick_range(g.H, g.W, Bs, io->flags, range_quads16(g.W, io->ri, p.temp, io->tm), true));
     return RPCC_OK;
 }
 // The launches of a batch in order, as stages: the three marked (*) are the kernels with one workgroup per frame or per label, which
@@ -3667,7 +3661,7 @@ static int run_stage(const BatchPlan &p, int stage, hipStream_t st) {
                                   p.tiled ? p.tiletab : nullptr, st, false, true);
     case ST_FPS:
         return launch_fps_range(io->ri, io->tm, p.temp, io->info, Bs, p.g.H, p.g.W, M, io->cen_pix, io->centers, io->flags, false,
-                                p.tiled ? p.tiletab : nullptr, io->timer, st, FPS_SOA ? p.rays_soa : nullptr);
+                                p.tiled ? p.tiletab : nullptr, io->timer, st, p.rays_soa);
     case ST_ASSIGN_LABELS:
         // (the FPS state is the un-fused minimum the assignment's bound needs; a CUDA-binary mode contracts it)
         if ((rc = launch_assign(io->ri, io->tm, io->ground, io->centers, Bs, p.g.H, p.g.W, M, seg, st,
@@ -3707,8 +3701,8 @@ static int check_batch_io(const rpcc_batch_io *io, int B, rpcc_geom g, int M, co
     const int P = g.H * g.W;
     if (wide)
         ARG_TRY(!(io->flags & RPCC_FPS_MODE_BITS));
-    else   // only the brute-force FPS kernel (16-byte loads at frame bases) needs P % 4 == 0; the tile-pruned one does not
-        ARG_TRY(P % 4 == 0 || (io->flags & RPCC_FPS_MODE_BITS) || (!(io->flags & RPCC_FPS_BRUTEFORCE) && fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES));
+    else   // only the brute-force FPS kernel (16-byte loads at frame bases) needs P % 4 == 0 (alignment and the planar table do not decide that pick)
+        ARG_TRY(P % 4 == 0 || fps_pick_range(g.H, g.W, B, io->flags, true, true).family != FPS_ONE_PASS);
     ARG_TRY(io->model_method == 0 || io->model_method == 1);
     ARG_TRY(point_floats(io->point_stride_bytes) > 0 && (io->point_stride_bytes != 16 || (reinterpret_cast<uintptr_t>(io->xyz) & 15u) == 0));
     if (io->nonuniform) {
@@ -3765,24 +3759,20 @@ static int mixed_ground(const BatchPlan *pl, int G, hipStream_t st) {
     return launch_ground_ransac_multi(m, st);
 }
 static int mixed_fps(const BatchPlan *pl, int G, hipStream_t st) {
-    int rc, total = 0;
-    bool common[RPCC_MAX_GROUPS], edge[RPCC_MAX_GROUPS];
-    for (int i = 0; i < G; i++) {   // the planar register-table kernel (launch_fps_tiled's first branch)
-        const BatchPlan &p = pl[i];
-        const bool vec = (p.g.W % 4 == 0) && aligned16(p.io->ri) && aligned16(p.temp) && aligned16(p.io->tm);
-        edge[i] = !vec;
-        common[i] = p.tiled && p.P < (1 << 22) && FPS_SOA && p.io->timer == nullptr;
-        if (common[i]) total += p.Bs;
-    }
-    const int tt = total <= 128 ? FPS_TT_SMALL : FPS_TT_BATCH;
-    for (int i = 0; i < G; i++) common[i] = common[i] && fps_tiling_range(pl[i].g.H, pl[i].g.W).T <= tt;
+    int rc, total = 0, tt = FPS_TT_SMALL;
+    for (int i = 0; i < G; i++)   // the frames that can share the launch: tile-pruned, untimed
+        if (pl[i].tiled && pl[i].io->timer == nullptr) total += pl[i].Bs;
+    bool common[RPCC_MAX_GROUPS];
     FpsMulti m;
     m.n = 0; m.first[0] = 0;
-    for (int i = 0; i < G; i++) {
-        if (!common[i]) continue;
+    for (int i = 0; i < G; i++) {   // of those, the groups whose pick for a launch of `total` frames is the planar register-table kernel
         const BatchPlan &p = pl[i];
+        const FpsPick k = fps_pick_range(p.g.H, p.g.W, total, p.io->flags, range_quads16(p.g.W, p.io->ri, p.temp, p.io->tm), true);
+        common[i] = k.family == FPS_PLANAR && p.io->timer == nullptr;
+        if (!common[i]) continue;
+        tt = k.threads;
         m.a[m.n] = {p.io->ri, p.io->tm, p.temp, p.io->info, fps_tiling_range(p.g.H, p.g.W), p.io->cen_pix, p.io->centers, p.tiletab, p.rays_soa};
-        m.edge[m.n] = edge[i] ? 1 : 0;
+        m.edge[m.n] = k.unaligned ? 1 : 0;
         m.first[m.n + 1] = m.first[m.n] + p.Bs;
         m.n++;
     }
@@ -3923,9 +3913,8 @@ extern "C" int rpcc_compress_batch_mixed(const rpcc_batch_io *ios, const int *Bs
 // wide_kernels.h (89 k frames/s at 300 clusters against 367 k at 100: a 4 x cliff at 254 -> 255).  Such a batch is the fused batch's own plan and
 // stages (run_batch<uint16_t>); ws is laid out as for rpcc_compress_batch (rpcc_wide_workspace_bytes covers rpcc_workspace_bytes_general for these counts).
 static bool mid_clusters_ok(const rpcc_batch_io *io, rpcc_geom g, int M) {
-    const int P = g.H * g.W;
     (void)io;
-    return M <= RPCC_MAX_CLUSTERS_MID && P < (1 << 22) && fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES;
+    return M <= RPCC_MAX_CLUSTERS_MID && fps_prunable(fps_tiling_range(g.H, g.W));
 }
 
 // carve-up of a wide workspace: [ keys, vals (in / out) u32 4 x [B,P] | pos i32 [B,P] | order u32 [B,P] | pts4 float4 [B,P] | sums u64 [B,K] |
@@ -3986,7 +3975,7 @@ extern "C" int rpcc_compress_batch_wide(const rpcc_batch_io *io, int B, rpcc_geo
     if ((rc = check_batch_io(io, B, g, M, ws, true))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int P = g.H * g.W, K = M + 2;
-    ARG_TRY(fps_tiling_range(g.H, g.W).T <= FPS_TILED_MAX_TILES && P < (1 << 22));
+    ARG_TRY(fps_prunable(fps_tiling_range(g.H, g.W)));
     if (mid_clusters_ok(io, g, M)) return run_batch<uint16_t>(io, B, g, M, ground_threshold, acc, ws, (1 << ST_COUNT) - 1, st);
     const WideWs w = wide_layout(ws, B, P, M, io->total);
     uint16_t *seg = reinterpret_cast<uint16_t *>(io->seg);

@@ -613,11 +613,18 @@ def test_fps_cuda_binary_modes_equal_the_oracle(env, fma, cuda_tie):
 
 def test_fps_tiled_equals_bruteforce(env):
     """The tile-pruned FPS kernels are exact: same indices, same centres AND the same final temp array
-    (bit for bit) as the brute-force kernels, on range images and on explicit point lists."""
+    (bit for bit) as the brute-force kernels, on range images and on explicit point lists.  The four sensors' images keep their
+    tile table in registers; the two 128-row images have more tiles (2048, 2064) than that table holds and take the LDS-table
+    kernel, with 16-byte loads (128 x 4096) and element by element (128 x 4098: the width is no multiple of four)."""
     torch, ops, orc, synth = env["torch"], env["ops"], env["orc"], env["synth"]
-    for name, ids in (("Velodyne64E_2048", (5, 6)), ("Velodyne64E", (7,)), ("Velodyne32E", (8,)), ("VelodyneVLP16", (9,))):
-        g, geom, tm = _geom(env, name)
-        gd = orc.GEOMS[name]
+    big = {"128x%d" % W: dict(H=128, W=W, hfov_deg=360, vmax_deg=15.0, vmin_deg=-25.0) for W in (4096, 4098)}
+    for name, ids in (("Velodyne64E_2048", (5, 6)), ("Velodyne64E", (7,)), ("Velodyne32E", (8,)), ("VelodyneVLP16", (9,)),
+                      ("128x4096", (42,)), ("128x4098", (43,))):
+        gd = big[name] if name in big else orc.GEOMS[name]
+        g = orc.LidarGeom(**gd)
+        geom = ops.make_geom(g.H, g.W, g.horizontal_FOV, g.vertical_max, g.vertical_min)
+        tm = ops.transform_map(g.H, g.W, g.horizontal_FOV, g.vertical_max, g.vertical_min)
+        assert np.array_equal(tm, orc.transform_map(g))
         frames = [synth.make_frame(i, g.H, g.W, vmax_deg=gd["vmax_deg"], vmin_deg=gd["vmin_deg"]).numpy() for i in ids]
         offs = np.zeros(len(frames) + 1, np.int64)
         offs[1:] = np.cumsum([f.shape[0] for f in frames])
@@ -669,6 +676,26 @@ def test_fps_tiled_equals_bruteforce(env):
         assert _beq(out[True][0], out[False][0]) and _beq(out[True][1], out[False][1]), (B, N, M)
         if N <= 30000:
             assert np.array_equal(out[False][0][0], orc.fps(pts[0], M))
+    # a list with locality and more tiles than the register table holds (N > 262 144): the non-empty pixels of a 128 x 4096 image
+    # in row-major order go to the LDS-table kernel (probe mark 0), with 16-byte loads (N % 4 == 0) and element by element.
+    # (Frame 45: the probe's measure is 0.014 against its limit of 0.07.  The sparse rows above the horizon stretch the tiles of
+    # some frames past it -- frame 44: 0.084 -- and those lists take the one-pass kernel, which is not what this case is for.)
+    g = orc.LidarGeom(**big["128x4096"])
+    tm = ops.transform_map(g.H, g.W, g.horizontal_FOV, g.vertical_max, g.vertical_min)
+    ri = orc.project(synth.make_frame(45, g.H, g.W, vmax_deg=15.0, vmin_deg=-25.0).numpy(), g)
+    rowmajor = orc.backproject(ri, tm).reshape(-1, 3)[ri.reshape(-1) != 0].astype(np.float32)
+    for cut in (0, 3):
+        n = (rowmajor.shape[0] // 4) * 4 - cut
+        assert n > 262144
+        pts = rowmajor[None, :n]
+        assert list(ops.fps_xyz_probe(_to(env, pts)).cpu().numpy()) == [0], cut
+        out = {}
+        for mode in (True, False):
+            temp = torch.full((1, n), 1e10, dtype=torch.float32, device=env["dev"])
+            idx = ops.fps_xyz(_to(env, pts), 100, temp=temp, bruteforce=mode)
+            out[mode] = (idx.cpu().numpy(), temp.cpu().numpy())
+        assert _beq(out[True][0], out[False][0]) and _beq(out[True][1], out[False][1]), cut
+        assert np.array_equal(out[False][0][0], orc.fps(pts[0], 100)), cut
 
 
 def test_ground_ransac_matches_specification(env):

@@ -11,18 +11,21 @@ HOST_SRC = os.path.join(_HERE, "csrc", "rpcc_host.c")
 HOST_LIB = os.path.join(_HERE, "lib", "librpcc_host.so")
 
 
-def _side_library(subdir, src, header, lib):
-    """(src, deps, lib) of a HIP library of its own beside librpcc_hip.so: its directory, its public header and csrc_tile/ (the
-    tile preparation it shares with the other side library), so that neither DEPS nor source_digest() -- the compression
-    library's identity -- changes with it."""
-    deps = [os.path.join(_HERE, d, f) for d in (subdir, "csrc_tile") for f in sorted(os.listdir(os.path.join(_HERE, d)))]
+def _side_library(subdir, src, header, lib, shared=("csrc_tile",)):
+    """(src, deps, lib) of a HIP library of its own beside librpcc_hip.so: its directory, its public header and the directories
+    of headers it shares with other side libraries (csrc_tile/: error state and tile preparation; csrc_lzmatch/: the match
+    finder of the two entropy coders), so that neither DEPS nor source_digest() -- the compression library's identity --
+    changes with it, and an edit of a shared header rebuilds every library that includes it."""
+    deps = [os.path.join(_HERE, d, f) for d in (subdir,) + tuple(shared) for f in sorted(os.listdir(os.path.join(_HERE, d)))]
     return (os.path.join(_HERE, subdir, src), deps + [os.path.join(os.path.dirname(_HERE), "include", header)],
             os.path.join(_HERE, "lib", lib))
 
 
 EVAL_SRC, EVAL_DEPS, EVAL_LIB = _side_library("csrc_eval", "eval_kernels.hip", "rpcc_eval.h", "librpcc_eval.so")   # reconstruction metrics
 SEG_SRC, SEG_DEPS, SEG_LIB = _side_library("csrc_seg", "dbscan_kernels.hip", "rpcc_seg.h", "librpcc_seg.so")     # DBSCAN segmentation
-LZ4_SRC, LZ4_DEPS, LZ4_LIB = _side_library("csrc_lz4", "lz4_kernels.hip", "rpcc_lz4.h", "librpcc_lz4.so")        # LZ4 entropy back-end
+_LZ = ("csrc_tile", "csrc_lzmatch")
+LZ4_SRC, LZ4_DEPS, LZ4_LIB = _side_library("csrc_lz4", "lz4_kernels.hip", "rpcc_lz4.h", "librpcc_lz4.so", _LZ)   # LZ4 entropy back-end
+DEFLATE_SRC, DEFLATE_DEPS, DEFLATE_LIB = _side_library("csrc_deflate", "deflate_kernels.hip", "rpcc_deflate.h", "librpcc_deflate.so", _LZ)   # gzip back-end
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -83,6 +86,11 @@ def build_lz4(force=False, verbose=False):
     return _hipcc(LZ4_SRC, LZ4_LIB, LZ4_DEPS, force, verbose)
 
 
+def build_deflate(force=False, verbose=False):
+    """librpcc_deflate.so: the gzip / deflate encoder kernels (csrc_deflate/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(DEFLATE_SRC, DEFLATE_LIB, DEFLATE_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -91,6 +99,7 @@ def build(force=False, verbose=False):
     build_eval(force, verbose)
     build_seg(force, verbose)
     build_lz4(force, verbose)
+    build_deflate(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

@@ -132,9 +132,9 @@ def pack_frames(basic_compressor, frames, uniform=True):
             host = _lib.host_lib()     # not built / not loadable / stale: remembered by _lib, the Python path below gives the same bytes
         except _lib.RpccError:
             host = None
-    if basic_compressor.lz4_batched() and frames:   # every array of the chunk in one dumps_many (one launch)
+    if basic_compressor.batch_codec() and frames:   # every array of the chunk in one dumps_many / compress_many
         keys = (() if uniform else ("salience_level",)) + _ORDER
-        blobs = basic_compressor._lz4().dumps_many([np.ascontiguousarray(od[k]) for od in frames for k in keys])
+        blobs = basic_compressor.batch_codec()[1]([np.ascontiguousarray(od[k]) for od in frames for k in keys])
         na = len(keys)
         return [b"".join(struct.pack("i", len(b)) + b for b in blobs[i * na: (i + 1) * na]) for i in range(len(frames))]
     if host is None:
@@ -197,12 +197,15 @@ def decompress_point_cloud(compressed_data, basic_compressor, model_num, H, W):
 
 class BasicCompressor:
     """utils/compress_utils.py:232-310.  bzip2 / deflate are stdlib; lz4 is the lz4 package (lz4==0.7.0 API in the reference)
-    where it is installed, else rpcc_amd.lz4_codec (the same dumps / loads forms, coded on the GPU)."""
+    where it is installed, else rpcc_amd.lz4_codec (the same dumps / loads forms, coded on the GPU).  device_entropy=True
+    (opt-in) sends 'deflate' / 'gzip' through rpcc_amd.deflate_codec: gzip members coded on the GPU, other bytes than
+    gzip.compress's, read by the same gzip.decompress."""
 
     METHODS = ["lz4", "bzip2", "gzip", "deflate"]
 
-    def __init__(self, compressor_yaml=None, method_name=None):
+    def __init__(self, compressor_yaml=None, method_name=None, device_entropy=False):
         self.method_name = None
+        self.device_entropy = bool(device_entropy)
         if compressor_yaml is not None:
             self.method_name = load_yaml(compressor_yaml)["basic_compressor"]
         if method_name is not None:
@@ -221,9 +224,22 @@ class BasicCompressor:
         from . import lz4_codec
         return self._lz4() is lz4_codec
 
-    def compress_dict(self, data_dict):
+    def deflate_batched(self):
+        """True when 'deflate' / 'gzip' runs through rpcc_amd.deflate_codec (device_entropy), which codes a list of arrays at once."""
+        return self.device_entropy and self.method_name in ("gzip", "deflate")
+
+    def batch_codec(self):
+        """(module, its list encoder) of the back-end that codes a list of arrays on the device at once, or None."""
         if self.lz4_batched():
-            return dict(zip(data_dict, self._lz4().dumps_many([np.ascontiguousarray(v) for v in data_dict.values()])))
+            return self._lz4(), self._lz4().dumps_many
+        if self.deflate_batched():
+            from . import deflate_codec
+            return deflate_codec, deflate_codec.compress_many
+        return None
+
+    def compress_dict(self, data_dict):
+        if self.batch_codec():
+            return dict(zip(data_dict, self.batch_codec()[1]([np.ascontiguousarray(v) for v in data_dict.values()])))
         return {k: self.compress(v) for k, v in data_dict.items()}
 
     def decompress_dict(self, data_dict):
@@ -235,6 +251,8 @@ class BasicCompressor:
         buf = np.ascontiguousarray(np_array)
         if self.method_name == "bzip2":
             return bz2.compress(buf)
+        if self.deflate_batched():
+            return self.batch_codec()[1]([buf])[0]
         if self.method_name in ("gzip", "deflate"):
             return gzip.compress(buf)
         if self.method_name == "lz4":

@@ -1,30 +1,20 @@
 // lz4_kernels.hip -- librpcc_lz4.so (include/rpcc_lz4.h): LZ4 block encode / decode and .rpcc container compaction for
 // gfx950.  The encoder follows DESIGN.md section 11 bit for bit; tests/lz4_ref.py is its numpy statement.
 //
-// Encoder: one 256-thread workgroup per stream, which walks the stream in tiles of 1024 positions and keeps the 16384-entry
-// last-position table in LDS across tiles.  Per tile: the hash of every position; an LDS bitonic sort of (hash, position) gives
-// each position its in-tile predecessor of the same hash, or the table's entry where it has none; the accept test runs for all
-// positions and is stored as 64-bit ballots; the table takes each hash's last position of the tile.  Wave 0 then walks the
-// greedy parse over the ballots, extending a match 256 bytes per step with a wave-wide compare, and the tile's sequences
-// (at most 256: each consumes >= 4 positions of the tile) are sized, scanned and written by the whole workgroup.
+// Encoder: one 256-thread workgroup per stream.  The shared match finder (csrc_lzmatch/lz_match.h) walks the stream in tiles of
+// 1024 positions and leaves each tile's sequences in LDS; they are sized, scanned and written by the whole workgroup.
 //
 // Decoder: one wavefront per stream.  The token stream is read through a 2 KB LDS window; literals are copied by all lanes
 // from global memory; the last 64 KB of output are kept in an LDS ring, from which matches are served, so no lane reads back
 // through global memory what the wave has just stored.  Every read is checked against the stream's length and every write
 // against the header's size, which is checked against the capacity first.
 #include "../../include/rpcc_lz4.h"
+#include "../csrc_lzmatch/lz_match.h"
 #include "../csrc_tile/tiles.h"
 
 static_assert(RPCC_LZ4_ERR_ARG == TILE_ERR_ARG && RPCC_LZ4_ERR_HIP == TILE_ERR_HIP, "rpcc_lz4.h and tiles.h disagree");
 
-#define ENC_THREADS 256
-#define ENC_TILE 1024                // positions per tile (local position: 10 bits of the sort key)
-#define ENC_SEQ (ENC_TILE / 4)       // sequences starting in one tile
-#define HASH_LOG 14
-#define NONE 0xFFFFFFFFu
 #define MAX_OFFSET 65535
-#define MFLIMIT 12                   // a match starts at p <= n - 12
-#define LAST_LITERALS 5              // the last 5 bytes are literals
 #define DEC_WINDOW 2048              // bytes of the decoder's token window
 #define RING 65536                   // the decoder's history ring (> MAX_OFFSET)
 
@@ -36,14 +26,6 @@ __host__ __device__ static inline int64_t lz4_bound(int64_t n) { return 4 + n + 
 // ------------------------------------------------------------------------------------------------
 // encoder
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t hash5(uint64_t v) {   // v: the little-endian 40-bit value of src[p..p+5)
-    return (uint32_t)(((v << 24) * 889523592379ull) >> (64 - HASH_LOG));
-}
-
-__device__ __forceinline__ uint32_t ld4(const uint8_t *p) {
-    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
-
 // Bytes of a length's continuation: lengths >= 15 continue in 255-bytes and a final byte < 255.
 __device__ __forceinline__ uint32_t ext_bytes(uint32_t v) { return v >= 15 ? (v - 15) / 255 + 1 : 0; }
 
@@ -55,36 +37,10 @@ __device__ __forceinline__ uint32_t put_ext(uint8_t *o, uint32_t v) {   // -> by
     return k;
 }
 
-// Exclusive scan of one value per thread of a 256-thread block; *total gets the sum.  Ends with a barrier.
-__device__ uint32_t block_scan256(uint32_t v, uint32_t *wsum, uint32_t *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t x = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int k = 0; k < ENC_THREADS / 64; ++k) {
-        before += k < w ? wsum[k] : 0;
-        all += wsum[k];
-    }
-    *total = all;
-    __syncthreads();
-    return before + x - v;
-}
-
 struct EncShared {
-    uint32_t table[1 << HASH_LOG];   // last position of each hash before the tile (NONE: none)
-    uint32_t keys[ENC_TILE];         // hash << 10 | local position, sorted
-    uint32_t cand[ENC_TILE];         // c(p) by local position
-    uint64_t acc[ENC_TILE / 64];     // accept bits
-    uint4 seq[ENC_SEQ];              // literal start, literal length, offset, L
+    MatchShared m;
     uint32_t lit_out[ENC_SEQ];       // where each sequence's literals go
-    uint8_t bytes[ENC_TILE + 4];     // src[t0 .. t0 + cnt + 4)
     uint32_t wsum[ENC_THREADS / 64];
-    uint32_t i, anchor, nseq;
 };
 
 __global__ __launch_bounds__(ENC_THREADS) void encode_kernel(const uint64_t *__restrict__ src_ptr, const int64_t *__restrict__ src_len,
@@ -103,107 +59,17 @@ __global__ __launch_bounds__(ENC_THREADS) void encode_kernel(const uint64_t *__r
     uint8_t *__restrict__ out = dst + dst_off[s];
     if (tid < 4) out[tid] = (uint8_t)(n >> (8 * tid));
     uint32_t op = 4;                                    // output position in the slot
-    const uint32_t m = n >= MFLIMIT ? n - MFLIMIT + 1 : 0;   // positions that may start a match: 0 .. n - 12
-    for (int k = tid; k < (1 << HASH_LOG); k += ENC_THREADS) S.table[k] = NONE;
-    if (tid == 0) S.i = S.anchor = 0;
-    __syncthreads();
+    const uint32_t m = match_positions(n);
+    match_init(S.m);
 
     for (uint32_t t0 = 0; t0 < m; t0 += ENC_TILE) {
-        const uint32_t cnt = min((uint32_t)ENC_TILE, m - t0);
-        for (uint32_t k = tid; k < cnt + 4; k += ENC_THREADS) S.bytes[k] = src[t0 + k];   // t0 + cnt + 3 <= n - 9
-        __syncthreads();
-        for (uint32_t lp = tid; lp < ENC_TILE; lp += ENC_THREADS) {
-            uint32_t key = NONE;
-            if (lp < cnt) {
-                const uint64_t v = (uint64_t)ld4(S.bytes + lp) | (uint64_t)S.bytes[lp + 4] << 32;
-                key = hash5(v) << 10 | lp;
-            }
-            S.keys[lp] = key;
-        }
-        __syncthreads();
-        // bitonic sort of keys[0 .. ENC_TILE), ascending: equal hashes end up adjacent, in position order
-        for (uint32_t k = 2; k <= ENC_TILE; k <<= 1) {
-            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-                for (uint32_t q = tid; q < ENC_TILE / 2; q += ENC_THREADS) {
-                    const uint32_t a = 2 * j * (q / j) + (q % j), b = a + j;
-                    const uint32_t ka = S.keys[a], kb = S.keys[b];
-                    if ((ka > kb) == ((a & k) == 0)) {
-                        S.keys[a] = kb;
-                        S.keys[b] = ka;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        // c(p): the previous position of the same hash inside the tile, else the table's last one before the tile
-        for (uint32_t e = tid; e < cnt; e += ENC_THREADS) {
-            const uint32_t key = S.keys[e], h = key >> 10, lp = key & 1023;
-            const uint32_t prev = e > 0 ? S.keys[e - 1] : NONE;
-            S.cand[lp] = (e > 0 && (prev >> 10) == h) ? t0 + (prev & 1023) : S.table[h];
-        }
-        __syncthreads();
-        for (uint32_t e = tid; e < cnt; e += ENC_THREADS) {
-            const uint32_t key = S.keys[e], h = key >> 10;
-            if (e + 1 == cnt || (S.keys[e + 1] >> 10) != h) S.table[h] = t0 + (key & 1023);
-        }
-        // accept: c exists, p - c <= 65535, src[c..c+4) == src[p..p+4)
-        for (uint32_t lp = tid; lp < ENC_TILE; lp += ENC_THREADS) {
-            bool a = false;
-            if (lp < cnt) {
-                const uint32_t c = S.cand[lp];
-                a = c != NONE && t0 + lp - c <= MAX_OFFSET && ld4(src + c) == ld4(S.bytes + lp);
-            }
-            const uint64_t bits = __ballot(a);
-            if (lane == 0) S.acc[lp >> 6] = bits;
-        }
-        __syncthreads();
-        // greedy walk over the accept bits (wave 0; every lane holds the same state)
-        if (wave == 0) {
-            uint32_t i = S.i, anchor = S.anchor, nseq = 0;
-            const uint32_t end = t0 + cnt;
-            while (i < end) {
-                uint32_t w = (i - t0) >> 6;
-                uint64_t bits = S.acc[w] & (~0ull << ((i - t0) & 63));
-                while (bits == 0 && ++w < ENC_TILE / 64) bits = S.acc[w];
-                if (bits == 0) {
-                    i = end;
-                    break;
-                }
-                const uint32_t p = t0 + w * 64 + (__ffsll((unsigned long long)bits) - 1);   // < end: bits past cnt are 0
-                const uint32_t c = S.cand[p - t0];
-                const uint32_t lim = n - LAST_LITERALS - p;   // L <= lim (>= 7)
-                uint32_t L = 4;
-                while (L < lim) {
-                    const uint32_t x0 = L + lane * 4;
-                    uint32_t mm = 4;
-                    for (int k = 3; k >= 0; --k)
-                        if (x0 + k < lim && src[c + x0 + k] != src[p + x0 + k]) mm = k;
-                    const uint64_t miss = __ballot(mm < 4);
-                    if (miss) {
-                        const int l = __ffsll((unsigned long long)miss) - 1;
-                        L += l * 4 + __shfl(mm, l);
-                        break;
-                    }
-                    L = min(lim, L + 256);
-                }
-                if (lane == 0) S.seq[nseq] = make_uint4(anchor, p - anchor, p - c, L);
-                ++nseq;
-                i = p + L;
-                anchor = i;
-            }
-            if (lane == 0) {
-                S.i = i;
-                S.anchor = anchor;
-                S.nseq = nseq;
-            }
-        }
-        __syncthreads();
-        const uint32_t nseq = S.nseq;
+        match_tile<MAX_OFFSET>(S.m, src, n, t0, min((uint32_t)ENC_TILE, m - t0));
+        const uint32_t nseq = S.m.nseq;
         if (nseq) {   // the tile's sequences: sizes, scan, headers by one thread each, literals by one wave each
             uint4 q = make_uint4(0, 0, 0, 0);
             uint32_t size = 0;
             if ((uint32_t)tid < nseq) {
-                q = S.seq[tid];
+                q = S.m.seq[tid];
                 size = 1 + ext_bytes(q.y) + q.y + 2 + ext_bytes(q.w - 4);
             }
             uint32_t total;
@@ -221,7 +87,7 @@ __global__ __launch_bounds__(ENC_THREADS) void encode_kernel(const uint64_t *__r
             }
             __syncthreads();
             for (uint32_t e = wave; e < nseq; e += ENC_THREADS / 64) {
-                const uint4 r = S.seq[e];
+                const uint4 r = S.m.seq[e];
                 uint8_t *o = out + S.lit_out[e];
                 for (uint32_t x = lane; x < r.y; x += 64) o[x] = src[r.x + x];
             }
@@ -230,7 +96,7 @@ __global__ __launch_bounds__(ENC_THREADS) void encode_kernel(const uint64_t *__r
         __syncthreads();   // bytes / keys / seq are rewritten by the next tile
     }
     // the last literals src[anchor .. n)
-    const uint32_t anchor = S.anchor, ll = n - anchor;
+    const uint32_t anchor = S.m.anchor, ll = n - anchor;
     const uint32_t hdr = 1 + ext_bytes(ll);
     if (tid == 0) {
         out[op] = (uint8_t)(min(ll, 15u) << 4);

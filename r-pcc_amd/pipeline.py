@@ -13,7 +13,8 @@ class BatchCompressor:
     SLOTS = 4      # batches in flight one instance supports (submit() without collect()): every one owns its output buffers
 
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
-                 model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0):
+                 model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
+                 device_entropy=False):
         self.M = ops.check_cluster_num(cluster_num)   # (above 254: uint16 labels through the rpcc_*_wide entries; above 65533: refused by name)
         self.T = transformer
         self.device = torch.device(device) if device is not None else transformer.device
@@ -22,7 +23,7 @@ class BatchCompressor:
         self.uniform = uniform
         self.model_method = model_method
         self.cfg = compressor_cfg or {}
-        self.bc = BasicCompressor(method_name=basic_compressor)
+        self.bc = BasicCompressor(method_name=basic_compressor, device_entropy=device_entropy)
         self.seed = int(seed)
         self._buf = None        # the buffers of the most recent call (tests read them after compress())
         self._codec_ws = None
@@ -91,13 +92,16 @@ class BatchCompressor:
         buf.in_flight = True    # until collect() has read it (_buffers)
         ctx = dict(n=n, buf=buf, bits=bits, nseq=nseq, sal=sal, qp=qp, qtot=qtot, sp=sp, stot=stot,
                    stream=torch.cuda.current_stream(self.device), keep=(xyz, g, seq))
-        if self.bc.lz4_batched():
-            ctx["lz4"] = self._lz4_containers(n, buf, bits, nseq, sal, qp, sp)
+        codec = self.bc.batch_codec()
+        if codec:
+            ctx["lz4"] = self._device_containers(codec[0], n, buf, bits, nseq, sal, qp, sp)
         return ctx
 
-    def _lz4_containers(self, B, buf, bits, nseq, sal, qp, sp):
-        """basic_compressor 'lz4' without the lz4 package: the batch's .rpcc containers are built in HBM (rpcc_lz4_encode over the
-        arrays where they lie, then rpcc_lz4_pack_containers) on the current stream.  -> (containers, frame offsets / lengths)."""
+    def _device_containers(self, codec, B, buf, bits, nseq, sal, qp, sp):
+        """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), or 'deflate' / 'gzip' with device_entropy (deflate_codec):
+        the batch's .rpcc containers are built in HBM (the codec's encode_descriptors over the arrays where they lie, then
+        rpcc_lz4_pack_containers, which asks nothing of the streams' format) on the current stream.
+        -> (containers, frame offsets / lengths)."""
         from . import lz4_codec
         dev, K, P = self.device, buf.counts.shape[1], self.T.H * self.T.W
         i64 = dict(dtype=torch.int64, device=dev)
@@ -115,7 +119,7 @@ class BatchCompressor:
             cols.insert(0, (sal.data_ptr() + rows * K, nrow, K))
         addr = torch.stack([c[0] for c in cols], 1).reshape(-1)
         lens = torch.stack([c[1] for c in cols], 1).reshape(-1)
-        slots, dst_off, dst_len, _ = lz4_codec.encode_descriptors(addr, lens, [c[2] for c in cols] * B)
+        slots, dst_off, dst_len, _ = codec.encode_descriptors(addr, lens, [c[2] for c in cols] * B)
         cap = int(slots.numel()) + 4 * len(cols) * B
         out, frame = lz4_codec.pack_containers(slots, dst_off, dst_len, B, len(cols), cap)
         return out, frame, (addr, lens, slots, dst_off, dst_len)
@@ -161,7 +165,7 @@ class BatchCompressor:
         return [blob for part in parts for blob in part]
 
     def _collect_lz4(self, ctx):
-        """The containers _lz4_containers built: the frames' places, then the containers in one copy."""
+        """The containers _device_containers built: the frames' places, then the containers in one copy."""
         out, frame, _ = ctx["lz4"]
         try:
             ctx["stream"].synchronize()

@@ -47,6 +47,8 @@ def make_parser(datalist=False):
     p.add_argument("--lidar", help="lidar type of this point cloud collection.")
     p.add_argument("--compressor_yaml", default=os.path.join(PKG, "cfgs/compressor.yaml"))
     p.add_argument("--basic_compressor", type=str, default=None, help="for manual setting.")
+    p.add_argument("--device_entropy", action="store_true",
+                   help="basic_compressor deflate / gzip: code the gzip members on the GPU (this build; other bytes, the same decoder).")
     p.add_argument("--accuracy", type=float, default=None, help="for manual setting.")
     p.add_argument("--segment_method", type=str, default=None, help="for manual setting.")
     p.add_argument("--cluster_num", type=int, default=None, help="for manual setting.")
@@ -82,7 +84,7 @@ def resolve_cfg(args):
     segment_cfg = {"segment_method": cfg["segment_method"], "ground_vertical_threshold": cfg["ground_threshold"],
                    "cluster_num": cfg["cluster_num"], "DBSCAN_eps": cfg["DBSCAN_eps"]}
     model_cfg = {"model_method": cfg["modeling_method"], "angle_threshold": cfg["plane_angle_threshold"]}
-    bc = BasicCompressor(compressor_yaml=args.compressor_yaml)
+    bc = BasicCompressor(compressor_yaml=args.compressor_yaml, device_entropy=getattr(args, "device_entropy", False))
     if args.basic_compressor is not None:
         bc.set_method(args.basic_compressor)
     if args.accuracy is not None:
@@ -125,7 +127,8 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
     frame = dataset.load_data(args.input)
     bc = BatchCompressor(dataset.PCTransformer, cluster_num=segment_cfg["cluster_num"], accuracy=accuracy / 2,
                          ground_threshold=segment_cfg["ground_vertical_threshold"], uniform=uniform, model_method=model_cfg["model_method"],
-                         compressor_cfg=dict(cfg), basic_compressor=basic_compressor.method_name, seed=args.seed)
+                         compressor_cfg=dict(cfg), basic_compressor=basic_compressor.method_name, seed=args.seed,
+                         device_entropy=basic_compressor.device_entropy)
     blob = bc.compress([frame], frame_ids=[frame_identity(args.input)])[0]
     with open(args.output, "wb") as f:
         f.write(blob)

@@ -103,7 +103,8 @@ def compress(args, streaming_factory=None):
     bc = BatchCompressor(dataset.PCTransformer, cluster_num=segment_cfg["cluster_num"], accuracy=accuracy / 2,
                          ground_threshold=segment_cfg["ground_vertical_threshold"], uniform=uniform,
                          model_method=model_cfg["model_method"], compressor_cfg=dict(cfg),
-                         basic_compressor=basic_compressor.method_name, seed=args.seed)
+                         basic_compressor=basic_compressor.method_name, seed=args.seed,
+                         device_entropy=basic_compressor.device_entropy)
     mine = shard_indices(len(dataset), rank, world)
     # the ingest mode follows from the WHOLE datalist -- the same decision on every rank, also on one whose shard is empty -- and is
     # settled before the process group forms, so that a datalist --ingest rows cannot take fails on all ranks together

@@ -43,6 +43,10 @@ size_t rpcc_deflate_bound(int64_t n);
 /* Bytes of the work buffer rpcc_deflate_encode takes for nstreams streams of total_len input bytes in all (an upper bound of
  * the sum of src_len is enough); 0 for an invalid count or total. */
 size_t rpcc_deflate_workspace_bytes(int64_t nstreams, int64_t total_len);
+/* Caller's buffers: ws needs no initialisation (it may hold anything, an earlier call's contents under other arguments included), nothing
+ * outside the size above is touched and its contents are undefined on return; align it to 8 bytes (the tests use 256, and base + 8 once).  dst is written
+ * only where a member lands: dst[dst_off[s] .. + dst_len[s]) -- the rest of a slot, the gaps between slots and a refused stream's slot
+ * are left as they are; dst_len is written for every stream. */
 
 /* Encode nstreams streams as gzip members.  src_ptr (dev, uint64 [nstreams]) device addresses, src_len (dev, int64) their
  * lengths; stream s is written at dst + dst_off[s] (dev, int64), which must have room for dst_cap[s] (dev, int64) >=

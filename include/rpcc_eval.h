@@ -40,6 +40,11 @@ const char *rpcc_eval_last_error(void);
 
 /* Bytes of the work buffer every entry below takes for a batch of B frames of H x W (0 for an invalid shape). */
 size_t rpcc_eval_workspace_bytes(int B, int H, int W);
+/* Caller's buffers: ws needs no initialisation -- it may hold anything, e.g. what another entry of this header or a call of another shape
+ * left there (one ws serves rpcc_eval_nn, rpcc_eval_normals and rpcc_eval_metrics in turn) --, nothing outside the size above is touched
+ * and its contents are undefined on return.  Align it to 16 bytes (its point tables hold 16-byte elements); the tests use 256, and base + 16 once.
+ * dist1 / idx1 / dist2 / idx2 and normals are indexed by rank: they are written for the n valid points of their cloud and left as they are
+ * behind them; n and sums are written completely.  Everything written repeats bit for bit. */
 
 /* Exact nearest neighbours in both directions -- the chamfer_3DDist call of calc_chamfer_distance
  * (utils/evaluate_metrics.py:9-19).  dev outputs, [B,P] by rank: dist1[i] = squared distance from cloud-1 point i

@@ -42,6 +42,26 @@ extern "C" {
  * on different streams with different buffers (the reference's ThreadPoolExecutor front-end,
  * tools/compress_datalist.py:202-206).  The one developer hook that is process-wide is rpcc_debug_stamps. */
 
+/* Caller's buffers (held by tests/test_gpu_buffers.py: exact sizes, hostile contents, guard bytes around them).
+ * Work buffers -- `ws`, `scratch`, `fps_table`, sized by rpcc_workspace_bytes[_general], rpcc_wide_workspace_bytes,
+ * rpcc_project_scratch_bytes, rpcc_fps_table_bytes, rpcc_plane_workspace_bytes, rpcc_codec_workspace_bytes -- need NO initialisation: they
+ * may hold anything, including what an earlier call left there under other arguments (another B, P, M, point count or entry point), and a
+ * buffer larger than asked for may be handed to calls of different shapes in turn.  Every entry clears or overwrites what it reads; the
+ * fused batch compares its per-frame projection flags with a mark kept inside ws, and a stale word that happens to equal the mark only
+ * sends that frame through the exact input-order projection (slower, same result).  Their contents are undefined on return, except where a
+ * stage hands them to the next (the stages of rpcc_compress_batch_stages on one ws; fps_table from rpcc_ground_mask to rpcc_fps_range).
+ * No entry reads or writes a byte outside the size it asked for.  Alignment: the base must be aligned to 16 bytes (the layouts place their
+ * parts at offsets that are multiples of 4 .. 256 bytes RELATIVE to the base and read some with 16-byte loads); 256 bytes -- what
+ * hipMalloc and torch give -- is what the tests use, but for one run of every kind of work buffer at base + 16.
+ * Outputs are written completely by every call, whatever they held before, and identically when the call is repeated, except:
+ *   q16 / q32 [b, nnz[b]:]            entries past a frame's count are left as they are (the caller need not zero them)
+ *   idx_sequence [b, nseq[b]:]        likewise (rpcc_contour_encode)
+ *   packed [total:]                   likewise (rpcc_pack_payload)
+ *   pc_rec, pred, inliers, q16 / q32  where NULL is allowed, NULL means not written
+ *   salience, key_point_map           not touched in the uniform framework (rpcc_batch_io.nonuniform == NULL); complete otherwise
+ * In particular every row of model / counts (labels without pixels too), all RPCC_INFO_INTS ints of info and the pad bits of the last
+ * byte of contour_bits are written. */
+
 /* Interface version: changes whenever the layout of a struct below or the meaning of an argument changes (the structs carry no size
  * field).  A binding compares rpcc_version() with the RPCC_ABI_VERSION of the header it was built against before it calls anything else
  * (r-pcc_amd/_lib.py does).  100: round 3.  101: rpcc_batch_io.point_stride_bytes.  102: the uint16-label entries (rpcc_*_wide), rpcc_compress_batch_stages.

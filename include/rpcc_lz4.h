@@ -47,6 +47,10 @@ size_t rpcc_lz4_bound(int64_t n);
 
 /* Bytes of the work buffer rpcc_lz4_pack_containers takes for nstreams streams (0 for an invalid count). */
 size_t rpcc_lz4_workspace_bytes(int64_t nstreams);
+/* Caller's buffers: ws needs no initialisation (it may hold anything, an earlier call's contents included), nothing outside the size above
+ * is touched and its contents are undefined on return; align it to 8 bytes (the tests use 256, and base + 8 once).  dst / out are written only where a stream
+ * or container lands: dst[dst_off[s] .. + dst_len[s]) -- the rest of a slot, the gaps between slots and a refused stream's slot are left
+ * as they are.  dst_len, status, frame_off and frame_len are written for every stream / frame. */
 
 /* Encode nstreams streams into dumps form.  src_ptr (dev, uint64 [nstreams]) device addresses, src_len (dev, int64) their
  * lengths; stream s is written at dst + dst_off[s] (dev, int64), which must have room for dst_cap[s] (dev, int64) >=

@@ -46,6 +46,11 @@ size_t rpcc_seg_workspace_bytes(int B, int H, int W);
  * pixel 1.  max_label (dev, int32 [B]): the largest label of each frame, RPCC_SEG_CAPPED if the frame's union-find hit
  * its iteration cap.  stats (dev, int64 [B,2], may be NULL): pair tests and tiles visited per frame.
  * flags: RPCC_SEG_BRUTEFORCE. */
+/* Caller's buffers: ws needs no initialisation -- it may hold anything, a previous call's contents under another shape included --, nothing
+ * outside rpcc_seg_workspace_bytes(B, H, W) bytes of it is touched and its contents are undefined on return.  Align it to 16 bytes (the
+ * point table at its start holds 16-byte elements); the tests use 256, and base + 16 once.  seg and max_label are written completely and repeat bit for bit.
+ * stats are written for every frame too, but they count work, and how much a workgroup does depends on the order in which its lanes list
+ * the tiles: they may differ from run to run (the labels do not). */
 int rpcc_seg_dbscan(const float *ri, const float *tm, const double *ground, int B, int H, int W, double eps, int min_points,
                     int flags, int32_t *seg, int32_t *max_label, int64_t *stats, void *ws, void *stream);
 

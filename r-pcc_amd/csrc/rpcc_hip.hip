@@ -3546,6 +3546,9 @@ extern "C" size_t rpcc_plane_workspace_bytes(int B, int P, int M) { return B > 0
 template <class L>
 static int launch_label_scan(const L *seg, int B, int P, int M, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared) {
     const WsLayout lay = ws_layout(ws, B, P, M);
+    // (Not a requirement of this scan: without ri and model neither kernel below adds to or reads sums / flags -- the results are the same
+    // with the clear left out, tests/test_gpu_buffers.py::test_plane_model_workspace runs it on hostile contents.  It only keeps the block in
+    // the state launch_hist_scan's comment asks for; launch_point_model's clear is the one that matters.)
     if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
     return launch_hist_scan(nullptr, seg, nullptr, B, P, M, lay, nullptr, counts, nnz, st);
 }

@@ -7,11 +7,12 @@ from . import _seg_lib as S
 from ._lib import RpccError, ptr, stream
 
 
-def dbscan_segment(ri, tm, ground, eps, min_points=10, brute_force=False, stats=False):
+def dbscan_segment(ri, tm, ground, eps, min_points=10, brute_force=False, stats=False, ws=None):
     """ri f32 [B,H,W], tm f32 [H,W,3], ground f64 [B,4] (device tensors) -> (seg int32 [B,H,W], max_label int32 [B]) in the
     reference's final labels: ground 0, ri == 0 pixels 1, noise 2, cluster k -> k + 3.  stats=True adds an int64 [B,2]
     tensor: pair tests and tiles visited per frame.  brute_force: every candidate tested in fp64, no pruning (the tests'
-    reference).  Raises RpccError if a frame's union-find hit its iteration cap (this synchronises the stream)."""
+    reference).  ws: the caller's work buffer of rpcc_seg_workspace_bytes(B, H, W) bytes (uint8; allocated here when None).
+    Raises RpccError if a frame's union-find hit its iteration cap (this synchronises the stream)."""
     if ri.dim() != 3:
         raise ValueError("ri must be [B,H,W], got %s" % (tuple(ri.shape),))
     B, H, W = ri.shape
@@ -20,7 +21,8 @@ def dbscan_segment(ri, tm, ground, eps, min_points=10, brute_force=False, stats=
     if ri.dtype != torch.float32 or tm.dtype != torch.float32 or ground.dtype != torch.float64:
         raise ValueError("ri and tm are float32, ground float64")
     dev = ri.device
-    ws = torch.empty(max(S.lib().rpcc_seg_workspace_bytes(B, H, W), 1), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty(max(S.lib().rpcc_seg_workspace_bytes(B, H, W), 1), dtype=torch.uint8, device=dev)
     seg = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     mx = torch.empty((B,), dtype=torch.int32, device=dev)
     st = torch.empty((B, S.NSTATS), dtype=torch.int64, device=dev) if stats else None

@@ -17,11 +17,12 @@ def bound(n):
     return 18 + n + 5 * max(1, -(-n // 65535))
 
 
-def encode_descriptors(addr, lens, caps):
+def encode_descriptors(addr, lens, caps, ws=None):
     """Device form of compress over descriptors: addr, lens (i64 GPU tensors [n]) the streams' device addresses and byte counts,
     caps (host ints) an upper bound of each length.  Enqueued on the current stream, nothing waited for.  -> (slots u8, dst_off i64,
     dst_len i64 GPU tensors, dst_off as numpy): stream s as a gzip member at slots[dst_off[s]:][:dst_len[s]], dst_len[s] < 0 when
-    its length was out of range or above its cap."""
+    its length was out of range or above its cap.  ws: the caller's work buffer of rpcc_deflate_workspace_bytes(n, sum of caps) bytes
+    (allocated here when None)."""
     dev = addr.device
     cap = np.array([bound(int(c)) for c in caps], np.int64)
     off = np.zeros(len(cap), np.int64)
@@ -31,13 +32,14 @@ def encode_descriptors(addr, lens, caps):
     dst_len = torch.empty(len(cap), dtype=torch.int64, device=dev)
     if len(cap):
         total = int(sum(int(c) for c in caps))
-        ws = torch.empty(max(L.lib().rpcc_deflate_workspace_bytes(len(cap), total), 8) // 8 + 1, dtype=torch.int64, device=dev)
+        if ws is None:
+            ws = torch.empty(max(L.lib().rpcc_deflate_workspace_bytes(len(cap), total), 8) // 8 + 1, dtype=torch.int64, device=dev)
         L.check(L.lib().rpcc_deflate_encode(ptr(addr), ptr(lens), len(cap), total, ptr(slots), ptr(meta[0]), ptr(meta[1]), ptr(dst_len),
                                             ptr(ws), stream()))
     return slots, meta[0], dst_len, off
 
 
-def compress_many(buffers, device=None):
+def compress_many(buffers, device=None, ws=None):
     """[bytes-like or numpy array] -> [gzip member bytes]: one H2D copy, the launches, one D2H copy."""
     if not buffers:
         return []
@@ -47,7 +49,7 @@ def compress_many(buffers, device=None):
         data, offs = _upload(arrays, dev)
         sizes = [a.size for a in arrays]
         desc = torch.tensor([[data.data_ptr() + int(o) for o in offs], sizes], dtype=torch.int64).to(dev, non_blocking=True)
-        slots, _, dst_len, off = encode_descriptors(desc[0], desc[1], sizes)
+        slots, _, dst_len, off = encode_descriptors(desc[0], desc[1], sizes, ws=ws)
         # [dst_len as bytes | slots] leave in one copy
         both = torch.cat([dst_len.view(torch.uint8), slots]).cpu().numpy()
         torch.cuda.current_stream(dev).synchronize()

@@ -71,13 +71,15 @@ def encode_tensors(srcs):
     return encode_descriptors(desc[0], desc[1], nbytes)
 
 
-def pack_containers(slots, dst_off, dst_len, nframes, per_frame, out_cap):
+def pack_containers(slots, dst_off, dst_len, nframes, per_frame, out_cap, ws=None):
     """The .rpcc containers of nframes frames of per_frame streams (encode_tensors' output, frame-major) back to back on the device.
+    ws: the caller's work buffer of rpcc_lz4_workspace_bytes(nframes * per_frame) bytes (allocated here when None).
     -> (out u8, frame i64 [2, nframes]: offsets and lengths, -1 for a frame that failed)."""
     dev = slots.device
     out = torch.empty(max(int(out_cap), 1), dtype=torch.uint8, device=dev)
     frame = torch.empty((2, max(nframes, 1)), dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.lib().rpcc_lz4_workspace_bytes(nframes * per_frame), 8), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty(max(L.lib().rpcc_lz4_workspace_bytes(nframes * per_frame), 8), dtype=torch.uint8, device=dev)
     L.check(L.lib().rpcc_lz4_pack_containers(ptr(slots), ptr(dst_off), ptr(dst_len), nframes, per_frame, ptr(out), int(out_cap),
                                              ptr(frame[0]), ptr(frame[1]), ptr(ws), stream()))
     return out, frame

@@ -101,18 +101,18 @@ def ground_ransac(ri, tm, seed=0, frame_ids=None):
     return ground, inl
 
 
-def ground_mask(ri, tm, ground, threshold, fps_table=False):
+def ground_mask(ri, tm, ground, threshold, fps_table=False, table=None):
     """a3+a5.  -> (temp f32 [B,P], info i32 [B,8] = n_left, first candidate pixel, nnz, table flag, first empty
     candidate pixel, 3 spare).
     fps_table=True: the kernel also runs the first FPS pass and returns the tile table as third value
-    (hand it to fps_range); results are identical either way."""
+    (hand it to fps_range); results are identical either way.  table: the caller's buffer of rpcc_fps_table_bytes(B, H, W) bytes for it."""
     B, H, W = ri.shape
     P = H * W
     temp = torch.empty((B, P), dtype=torch.float32, device=_dev(ri))
     info = torch.empty((B, _lib.INFO_INTS), dtype=torch.int32, device=_dev(ri))
     tab = None
     if fps_table:
-        tab = torch.empty(_lib.lib().rpcc_fps_table_bytes(B, H, W) // 4, dtype=torch.float32, device=_dev(ri))
+        tab = torch.empty(_lib.lib().rpcc_fps_table_bytes(B, H, W) // 4, dtype=torch.float32, device=_dev(ri)) if table is None else table
     check(_lib.lib().rpcc_ground_mask(ptr(ri), ptr(tm), ptr(ground), float(threshold), B, H, W, ptr(temp), ptr(info),
                                       ptr(tab), stream()))
     return (temp, info, tab) if fps_table else (temp, info)
@@ -203,7 +203,9 @@ def predict_quantize(ri, tm, seg, model, acc, M, want_pred=False, int16=False, w
                      residual=None, q_out=None, nnz_out=None):
     """a10+a11(+a13).  label_acc f32 [B,K]: per-label steps (non-uniform); residual f32 [B,P]: use this
     residual instead of ri - pred.  -> (q [B,P] label-ordered, nnz [B], pred or None).  q_out / nnz_out: write into
-    these buffers (entries of q past nnz are left as they are) instead of fresh zero-filled ones."""
+    these buffers (entries of q past nnz are left as they are) instead of fresh ones.  The fresh q is zero-filled
+    for the caller's sake only (a defined tail behind nnz): the library neither reads q nor needs it cleared
+    (include/rpcc_hip.h "Caller's buffers")."""
     B = ri.shape[0]
     P = ri[0].numel()
     ws = workspace(B, P, M, _dev(ri)) if ws is None else ws
@@ -378,6 +380,9 @@ class BatchBuffers:
         self.max_points = int(max_points) if max_points is not None else B * P
         self.general = bool(general)
         self.ws = workspace(B, P, M, device, self.max_points, general=self.general)
+        # (zeros, not empty: the library writes every level in the non-uniform framework and does not touch the tensor
+        # in the uniform one, where consumers that copy it whole -- loader.StreamingCompressor's pinned copy, bench.py's
+        # output dump -- then read defined bytes)
         self.salience = torch.zeros((B, K), dtype=torch.uint8, device=device) if general else None
         self.key_point_map = torch.empty((B, geom.H, geom.W), dtype=torch.uint8, device=device) if general else None
 
@@ -522,13 +527,13 @@ def angle_cos_cut(angle_threshold_deg):
     return float(lo)
 
 
-def plane_model(ri, tm, seg, M, angle_threshold=75, seed=0, ground=None, want_counts=False, frame_ids=None, inject=None):
+def plane_model(ri, tm, seg, M, angle_threshold=75, seed=0, ground=None, want_counts=False, frame_ids=None, inject=None, ws=None):
     """a9 -> model f32 [B,K,4] (and counts i32 [B,K]).  Label k of frame b draws with hash(seed, frame_ids[b], k).
     inject f64 [B,K,4] (test hook): planes used instead of the RANSAC results."""
     B = ri.shape[0]
     P = ri[0].numel()
     K = M + 2
-    ws = torch.empty(_lib.lib().rpcc_plane_workspace_bytes(B, P, M), dtype=torch.uint8, device=_dev(ri))
+    ws = torch.empty(_lib.lib().rpcc_plane_workspace_bytes(B, P, M), dtype=torch.uint8, device=_dev(ri)) if ws is None else ws
     model = torch.empty((B, K, 4), dtype=torch.float32, device=_dev(ri))
     counts = torch.empty((B, K), dtype=torch.int32, device=_dev(ri))
     fid = _frame_ids(frame_ids, B, _dev(ri))

@@ -165,16 +165,11 @@ __global__ __launch_bounds__(256) void recover_map_kernel(const uint8_t *__restr
 }
 
 // ------------------------------------------------------------------------------------------------
-// f3: decoder body.  For every pixel: pred (intra_predict), residual = (float)((double)q * step) read
-// from the label-ordered stream at tile offset + segment prefix + ballot rank (the inverse of the
-// encoder's ordered scatter), rec = pred + residual (fp32), optional point cloud rec * tm.
-// step: one double (uniform) or per-label through salience (non-uniform).
+// f3: decoder body.  For every pixel: pred (intra_pred), residual = dequant of the integer read from the
+// label-ordered stream at its slot (segment_slot: the inverse of the encoder's ordered scatter),
+// rec = pred + residual (fp32), optional point cloud rec * tm.
+// steps (DecodeSteps, ref_rules.h): one double (uniform) or per-label through salience (non-uniform).
 // ------------------------------------------------------------------------------------------------
-struct DecodeSteps {
-    double acc[8];  // acc[level]; uniform: acc[0]
-    int levels;     // 0 = uniform
-};
-
 __global__ __launch_bounds__(256) void decode_kernel(const uint8_t *__restrict__ seg, const int16_t *__restrict__ q16,
                                                      const float *__restrict__ model, const float *__restrict__ tm,
                                                      const uint32_t *__restrict__ hist, const uint8_t *__restrict__ salience,
@@ -186,7 +181,6 @@ __global__ __launch_bounds__(256) void decode_kernel(const uint8_t *__restrict__
     const int SEGP = KP + 1;
     uint32_t *soff = segcnt + 16 * SEGP;                                 // [KP] this tile's input offsets per label
     const int b = blockIdx.y, t = blockIdx.x, K = M + 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // per-frame bases (wave-uniform) + byte offsets; all loads of the tile are issued first (unconditional, clamped)
     seg += (int64_t)b * P;
     q16 += (int64_t)b * P;
@@ -208,43 +202,21 @@ __global__ __launch_bounds__(256) void decode_kernel(const uint8_t *__restrict__
     for (int j = 0; j < 4; j++) {
         const int p = t * TILE + j * 256 + threadIdx.x;
         lab[j] = (p < P && lraw[j] != 1) ? lraw[j] : -1;
-        rank[j] = 0;
-        int todo = lab[j];
-        while (true) {
-            const unsigned long long pending = __ballot(todo >= 0);
-            if (!pending) break;
-            const int leader = (int)__ffsll((long long)pending) - 1;
-            const int cur = __builtin_amdgcn_readlane(todo, leader);
-            const unsigned long long same = __ballot(todo == cur);
-            if (todo == cur) {
-                rank[j] = __popcll(same & ((1ull << lane) - 1ull));
-                if (lane == leader) segcnt[(j * 4 + wave) * SEGP + cur] = (uint32_t)__popcll(same);
-                todo = -1;
-            }
-        }
+        rank[j] = segment_rank(j, lab[j], segcnt, SEGP);
     }
-    __syncthreads();
-    segment_prefix(segcnt, SEGP, soff, K);
-    __syncthreads();
+    segment_offsets(segcnt, SEGP, soff, K);
     int16_t qv[4];
 #pragma unroll
     for (int j = 0; j < 4; j++)  // gather of the label-ordered integers (clamped: unused for label 1 / outside)
-        qv[j] = ld_at(q16, (lab[j] >= 0 ? segcnt[(j * 4 + wave) * SEGP + lab[j]] + (uint32_t)rank[j] : 0u) * 2u);
+        qv[j] = ld_at(q16, (lab[j] >= 0 ? segment_slot(j, lab[j], rank[j], segcnt, SEGP) : 0u) * 2u);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int p = t * TILE + j * 256 + threadIdx.x;
         if (p >= P) continue;
         const int l = lraw[j];
-        const float p0 = smodel[4 * l], p1 = smodel[4 * l + 1], p2 = smodel[4 * l + 2], p3 = smodel[4 * l + 3];
-        float pr;
-        if (p0 + p1 + p2 == 0.0f) pr = p3;
-        else pr = -p3 / (p0 * ray[j].x + p1 * ray[j].y + p2 * ray[j].z);
+        const float pr = intra_pred(smodel[4 * l], smodel[4 * l + 1], smodel[4 * l + 2], smodel[4 * l + 3], ray[j].x, ray[j].y, ray[j].z);
         float res = 0.0f;  // label 1 keeps the zero of np.zeros_like (compress_utils.py:115)
-        if (lab[j] >= 0) {
-            // (a level beyond the configured ones -- a corrupt stream; tools/decompress.py rejects it -- is clamped, never read past acc[])
-            const double st = steps.levels ? steps.acc[min((int)salience[(int64_t)b * K + l], steps.levels - 1)] : steps.acc[0];
-            res = (float)((double)qv[j] * st);  // int16 * python float -> float64 -> stored into a float32 array
-        }
+        if (lab[j] >= 0) res = dequant(qv[j], dequant_step(steps, salience, (int64_t)b * K + l));
         const float rec = pr + res;          // tools/decompress.py:104
         st_at(ri_rec, (uint32_t)p * 4u, rec);
         if (pc_rec) {
@@ -254,6 +226,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const uint8_t *__restrict__
         }
     }
 }
+// its LDS: smodel f32 [KP*4] | the segments'
+static inline size_t decode_lds_bytes(int KP) { return (size_t)KP * 4 * 4 + segment_lds_bytes(KP); }
 
 // a3 as its own entry: pc = ri[...,None] * transform_map  (dataset/transformer.py:94-101)
 __global__ __launch_bounds__(256) void backproject_kernel(const float *__restrict__ ri, const float *__restrict__ tm, int P,

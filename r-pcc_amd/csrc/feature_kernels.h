@@ -421,13 +421,7 @@ __global__ __launch_bounds__(FEAT_THREADS) void features_kernel(const float *__r
 
 
 // a13 (salience): per label p_num (pixels, label 1 excluded by the caller's quantiser anyway) and kp_num
-// (key points > 0); level: label 0 -> ground_level, label 1 -> L-1, p_num < 30 -> L-1, else the first
-// level l with kp_num >= level_kp_num[l] (cpp_modules.cpp:388-403).  One workgroup per frame.
-struct SalienceParams {
-    int level_kp_num[8];
-    float level_acc[8];
-    int levels, ground_level;
-};
+// (key points > 0), then the label's level (salience_level, ref_rules.h) and its step.  One workgroup per frame.
 
 #define SAL_THREADS 1024  // one workgroup per frame: 16 wavefronts hide the latency of the frame-long scan
 // L: label type, KMAX: most labels (256 for byte labels, 1024 for uint16 ones up to RPCC_MAX_CLUSTERS_MID clusters)
@@ -469,13 +463,7 @@ __global__ __launch_bounds__(SAL_THREADS) void salience_kernel(const L *__restri
     __syncthreads();
     const int k = threadIdx.x;
     if (k < K) {
-        int lv = 0;
-        if (k == 0) lv = sp.ground_level;
-        else if (k == 1) lv = sp.levels - 1;
-        else if (pn[k] < 30) lv = sp.levels - 1;
-        else
-            for (int l = 0; l < sp.levels; l++)
-                if (kpn[k] >= sp.level_kp_num[l]) { lv = l; break; }
+        const int lv = salience_level(k, pn[k], kpn[k], sp);
         salience[(int64_t)b * K + k] = (uint8_t)lv;
         label_acc[(int64_t)b * K + k] = sp.level_acc[lv];
     }
@@ -489,13 +477,7 @@ __device__ __forceinline__ void salience_levels_body(const int32_t *__restrict__
     const int K = M + 2, k = threadIdx.x;
     if (k >= K) return;
     const int pn = counts[(int64_t)b * K + k], kn = kpn[(int64_t)b * K + k];
-    int lv = 0;
-    if (k == 0) lv = sp.ground_level;
-    else if (k == 1) lv = sp.levels - 1;
-    else if (pn < 30) lv = sp.levels - 1;
-    else
-        for (int l = 0; l < sp.levels; l++)
-            if (kn >= sp.level_kp_num[l]) { lv = l; break; }
+    const int lv = salience_level(k, pn, kn, sp);
     salience[(int64_t)b * K + k] = (uint8_t)lv;
     label_acc[(int64_t)b * K + k] = sp.level_acc[lv];
 }
@@ -510,13 +492,7 @@ __global__ __launch_bounds__(256) void wide_salience_levels_kernel(const int32_t
     const int b = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
     if (k >= K) return;
     const int pn = counts[(int64_t)b * K + k], kn = kpn[(int64_t)b * K + k];
-    int lv = 0;
-    if (k == 0) lv = sp.ground_level;
-    else if (k == 1) lv = sp.levels - 1;
-    else if (pn < 30) lv = sp.levels - 1;
-    else
-        for (int l = 0; l < sp.levels; l++)
-            if (kn >= sp.level_kp_num[l]) { lv = l; break; }
+    const int lv = salience_level(k, pn, kn, sp);
     salience[(int64_t)b * K + k] = (uint8_t)lv;
     label_acc[(int64_t)b * K + k] = sp.level_acc[lv];
 }
@@ -541,9 +517,5 @@ __global__ __launch_bounds__(256) void intra_predict_kernel(const L *__restrict_
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
     const float *m = model + ((int64_t)b * K + seg[(int64_t)b * P + p]) * 4;
-    const float p0 = m[0], p1 = m[1], p2 = m[2], p3 = m[3];
-    float pr;
-    if (p0 + p1 + p2 == 0.0f) pr = p3;
-    else pr = -p3 / (p0 * tm[3 * p] + p1 * tm[3 * p + 1] + p2 * tm[3 * p + 2]);
-    pred[(int64_t)b * P + p] = pr;
+    pred[(int64_t)b * P + p] = intra_pred(m[0], m[1], m[2], m[3], tm[3 * p], tm[3 * p + 1], tm[3 * p + 2]);
 }

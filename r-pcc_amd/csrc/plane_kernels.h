@@ -28,7 +28,6 @@ __device__ __forceinline__ void label_order_body(const L *__restrict__ seg, cons
     const int SEGP = KP + 1;
     uint32_t *soff = segcnt + 16 * SEGP;                        // [KP] this tile's offsets per label
     const int K = M + 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // per-frame bases + byte offsets; all loads of the tile first (unconditional, clamped)
     seg += (int64_t)b * P;
     order += (int64_t)b * P;
@@ -50,33 +49,19 @@ __device__ __forceinline__ void label_order_body(const L *__restrict__ seg, cons
     for (int j = 0; j < 4; j++) {
         const int p = t * TILE + j * 256 + threadIdx.x;
         lab[j] = (p < P && lraw[j] > 1) ? lraw[j] : -1;
-        rank[j] = 0;
-        int todo = lab[j];
-        while (true) {
-            const unsigned long long pending = __ballot(todo >= 0);
-            if (!pending) break;
-            const int leader = (int)__ffsll((long long)pending) - 1;
-            const int cur = __builtin_amdgcn_readlane(todo, leader);
-            const unsigned long long same = __ballot(todo == cur);
-            if (todo == cur) {
-                rank[j] = __popcll(same & ((1ull << lane) - 1ull));
-                if (lane == leader) segcnt[(j * 4 + wave) * SEGP + cur] = (uint32_t)__popcll(same);
-                todo = -1;
-            }
-        }
+        rank[j] = segment_rank(j, lab[j], segcnt, SEGP);
     }
-    __syncthreads();
-    segment_prefix(segcnt, SEGP, soff, K);
-    __syncthreads();
+    segment_offsets(segcnt, SEGP, soff, K);
 #pragma unroll
     for (int j = 0; j < 4; j++)
         if (lab[j] >= 0) {
-            const int p = t * TILE + j * 256 + threadIdx.x;
-            const uint32_t o = segcnt[(j * 4 + wave) * SEGP + lab[j]] + (uint32_t)rank[j];
-            order[o] = (uint32_t)p;
-            if (pts4) pts4[o] = make_float4(rr[j] * ray[j].x, rr[j] * ray[j].y, rr[j] * ray[j].z, rr[j]);  // transformer.py:94-101
+            const uint32_t o = segment_slot(j, lab[j], rank[j], segcnt, SEGP);
+            order[o] = (uint32_t)(t * TILE + j * 256 + threadIdx.x);
+            if (pts4) pts4[o] = label_point(rr[j], ray[j].x, ray[j].y, ray[j].z);
         }
 }
+// its LDS: the segments' alone
+static inline size_t label_order_lds_bytes(int KP) { return segment_lds_bytes(KP); }
 template <class L = uint8_t>
 __global__ __launch_bounds__(256) void label_order_kernel(const L *__restrict__ seg, const uint32_t *__restrict__ hist,
                                                           int P, int M, int KP, int T, uint32_t *__restrict__ order,

@@ -19,6 +19,7 @@
 #include <vector>
 #include "../../include/rpcc_hip.h"
 #include "rpcc_device.h"
+#include "ref_rules.h"
 
 using namespace rpcc;
 
@@ -2826,31 +2827,8 @@ __device__ __forceinline__ void model_scan_body(const ScanArgs &A, const int b) 
         }
         if (counts && grp == 0) counts[(int64_t)b * K + k] = (int32_t)total;
     }
-    if (k < K && grp == 0 && model != nullptr) {
-        float *row = model + ((int64_t)b * K + k) * 4;
-        if (k == 0) {
-            row[0] = (float)ground[4 * b]; row[1] = (float)ground[4 * b + 1];
-            row[2] = (float)ground[4 * b + 2]; row[3] = (float)ground[4 * b + 3];
-        } else if (k == 1) {
-            row[0] = row[1] = row[2] = row[3] = 0.0f;
-        } else {
-            double s;
-            if (flags[4 * b]) {
-                // exact sequential double accumulation in row-major order (cpp_modules.cpp:514) for frames
-                // whose ranges fall outside the fixed-point window; one thread per label, rare.
-                s = 0.0;
-                const uint8_t *sg = seg + (int64_t)b * P;
-                const float *rr = ri + (int64_t)b * P;
-                for (int p = 0; p < P; p++)
-                    if (sg[p] == k) s += (double)rr[p];
-            } else {
-                s = (double)sums[(int64_t)b * KP + k] * (1.0 / 268435456.0);  // exact: sum < 2^53 units
-            }
-            const double n = (double)total;
-            row[0] = row[1] = row[2] = 0.0f;
-            row[3] = (total == 0) ? u2f(0xFFC00000u) : (float)(s / n);  // 0.0/0 on x86 = default NaN
-        }
-    }
+    if (k < K && grp == 0 && model != nullptr)
+        point_model_row(model, ground, flags, seg, ri, P, K, b, k, (long long)sums[(int64_t)b * KP + k], total);
 }
 __global__ __launch_bounds__(SCAN_THREADS) void model_scan_kernel(const ScanArgs A) { model_scan_body(A, blockIdx.x); }
 // (the frames of several geometry groups in one launch, rpcc_compress_batch_mixed: one workgroup per frame, per[] = 1)
@@ -2897,25 +2875,8 @@ __global__ __launch_bounds__(SCANW_THREADS) void model_scan_wide_kernel(const fl
             if (t0 + j < T) { st_at(gh, (uint32_t)(t0 + j) * kp4 + k4, run); run += d[j]; }
     }
     if (counts) counts[(int64_t)b * K + k] = (int32_t)total;
-    if (model != nullptr) {
-        float *row = model + ((int64_t)b * K + k) * 4;
-        if (k == 0) {
-            row[0] = (float)ground[4 * b]; row[1] = (float)ground[4 * b + 1]; row[2] = (float)ground[4 * b + 2]; row[3] = (float)ground[4 * b + 3];
-        } else if (k == 1) {
-            row[0] = row[1] = row[2] = row[3] = 0.0f;
-        } else {
-            double sm;
-            if (flags[4 * b]) {   // sequential double accumulation in row-major order (cpp_modules.cpp:514): ranges outside the fixed-point window, rare
-                sm = 0.0;
-                for (int p = 0; p < P; p++)
-                    if (seg[(int64_t)b * P + p] == (L)k) sm += (double)ri[(int64_t)b * P + p];
-            } else {
-                sm = (double)sums[(int64_t)b * KP + k] * (1.0 / 268435456.0);
-            }
-            row[0] = row[1] = row[2] = 0.0f;
-            row[3] = total == 0 ? u2f(0xFFC00000u) : (float)(sm / (double)total);
-        }
-    }
+    if (model != nullptr)
+        point_model_row(model, ground, flags, seg, ri, P, K, b, k, (long long)sums[(int64_t)b * KP + k], total);
 }
 // A lane owns FOUR CONSECUTIVE pixels of the tile (VEC: one 4-byte load of labels, one 16-byte load of ranges), a wavefront
 // 256 consecutive pixels.  Labels are spatially coherent, so the pixels that carry the label of the wavefront's first pixel
@@ -2923,6 +2884,26 @@ __global__ __launch_bounds__(SCANW_THREADS) void model_scan_wide_kernel(const fl
 // sums for the range total), the others add themselves to LDS directly: integer sums, any order.  The fixed-point value of a
 // range r in [2^-5, 2^8) is read off its bit pattern: r * 2^28 = mantissa << (exponent + 5), an integer below 2^36, kept as
 // an 18-bit low part and a high part whose sums over a wavefront stay below 2^32.
+//
+// Two steps are shared with the quantiser (predict_quantize_body: same pixels per lane, same rounds): the labels of the four consecutive
+// pixels from pixel q on in one 4- or 8-byte load (q % 4 == 0 and seg aligned for it: hist_vec / quantise_vec),
+template <class L>
+__device__ __forceinline__ void load_labels4(const L *seg, uint32_t q, int (&lab)[4]) {
+    if (sizeof(L) == 1) {
+        const uint32_t l4 = ld_at(reinterpret_cast<const uint32_t *>(seg), q);
+        lab[0] = (int)(l4 & 255u); lab[1] = (int)((l4 >> 8) & 255u); lab[2] = (int)((l4 >> 16) & 255u); lab[3] = (int)(l4 >> 24);
+    } else {
+        const uint2 l8 = ld_at(reinterpret_cast<const uint2 *>(seg), q * 2u);
+        lab[0] = (int)(l8.x & 0xFFFFu); lab[1] = (int)(l8.x >> 16); lab[2] = (int)(l8.y & 0xFFFFu); lab[3] = (int)(l8.y >> 16);
+    }
+}
+// and a round's label: that of the first pending pixel of the lowest pending slot (pend[e]: the lanes whose pixel e is pending; not all empty).
+__device__ __forceinline__ int round_label(const int (&lab)[4], const unsigned long long (&pend)[4]) {
+    if (pend[0]) return __builtin_amdgcn_readlane(lab[0], (int)__ffsll((long long)pend[0]) - 1);
+    if (pend[1]) return __builtin_amdgcn_readlane(lab[1], (int)__ffsll((long long)pend[1]) - 1);
+    if (pend[2]) return __builtin_amdgcn_readlane(lab[2], (int)__ffsll((long long)pend[2]) - 1);
+    return __builtin_amdgcn_readlane(lab[3], (int)__ffsll((long long)pend[3]) - 1);
+}
 template <bool VEC, class L = uint8_t>
 __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, const L *__restrict__ seg,
                                                 int P, int KP, int T, int64_t *__restrict__ sums,
@@ -2941,13 +2922,7 @@ __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, co
     // all loads first (unconditional, clamped)
     if (VEC) {
         const uint32_t q = (uint32_t)(nval > 0 ? p0 : 0);
-        if (sizeof(L) == 1) {
-            const uint32_t l4 = ld_at(reinterpret_cast<const uint32_t *>(seg_b), q);
-            lab[0] = (int)(l4 & 255u); lab[1] = (int)((l4 >> 8) & 255u); lab[2] = (int)((l4 >> 16) & 255u); lab[3] = (int)(l4 >> 24);
-        } else {   // four 16-bit labels: one 8-byte load
-            const uint2 l8 = ld_at(reinterpret_cast<const uint2 *>(seg_b), q * 2u);
-            lab[0] = (int)(l8.x & 0xFFFFu); lab[1] = (int)(l8.x >> 16); lab[2] = (int)(l8.y & 0xFFFFu); lab[3] = (int)(l8.y >> 16);
-        }
+        load_labels4(seg_b, q, lab);
         if (want_sum) {
             const uint4 r4 = ld_at(reinterpret_cast<const uint4 *>(ri_b), q * 4u);
             rb[0] = r4.x; rb[1] = r4.y; rb[2] = r4.z; rb[3] = r4.w;
@@ -2991,11 +2966,7 @@ __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, co
     for (int e = 0; e < 4; e++) pend[e] = __ballot(todo[e] >= 0);
 #pragma unroll 1
     for (int round = 0; round < HIST_ROUNDS && (pend[0] | pend[1] | pend[2] | pend[3]) != 0ull; round++) {
-        int cur;
-        if (pend[0])      cur = __builtin_amdgcn_readlane(todo[0], (int)__ffsll((long long)pend[0]) - 1);
-        else if (pend[1]) cur = __builtin_amdgcn_readlane(todo[1], (int)__ffsll((long long)pend[1]) - 1);
-        else if (pend[2]) cur = __builtin_amdgcn_readlane(todo[2], (int)__ffsll((long long)pend[2]) - 1);
-        else              cur = __builtin_amdgcn_readlane(todo[3], (int)__ffsll((long long)pend[3]) - 1);
+        const int cur = round_label(todo, pend);
         int ctot = 0;
         uint32_t slo = 0u, shi = 0u;
 #pragma unroll
@@ -3048,6 +3019,11 @@ __global__ __launch_bounds__(256) void model_hist_multi_kernel(const MultiArgs<H
     if (a.vec) model_hist_body<true>(a.ri, a.seg, a.P, KP, a.T, a.sums, a.flags, a.hist, b, t);
     else       model_hist_body<false>(a.ri, a.seg, a.P, KP, a.T, a.sums, a.flags, a.hist, b, t);
 }
+// model_hist_body's LDS (ssum u64 [KP] | scnt u32 [KP]) and whether a group may take its VEC form: the 4-pixel loads of seg and -- when the
+// range sums are wanted -- of ri are aligned and never straddle the frame's end
+static inline size_t hist_lds_bytes(int KP) { return (size_t)KP * 8 + (size_t)KP * 4; }
+template <class L>
+static inline bool hist_vec(int P, const L *seg, const float *ri) { return (P & 3) == 0 && seg4_aligned(seg) && (ri == nullptr || aligned16(ri)); }
 static inline int scan_kp2(int M) { int v = 1; while (v < M + 2) v <<= 1; return v; }   // labels rounded up to a power of two (<= 256)
 // histogram + scan: tile x label counts (and the labels' range sums when ri is given), then the offsets of the ordered scatter, counts, nnz and
 // -- with `model` -- the point model's rows.  The sums / flags block must be zero (memset or BatchInit).
@@ -3055,11 +3031,11 @@ template <class L>
 static int launch_hist_scan(const float *ri, const L *seg, const double *ground, int B, int P, int M, const WsLayout &lay, float *model,
                             int32_t *counts, int32_t *nnz, hipStream_t st) {
     const int KP = kpad(M), T = ntiles(P);
-    const bool vec = (P & 3) == 0 && seg4_aligned(seg) && (ri == nullptr || aligned16(ri));
+    const size_t sh = hist_lds_bytes(KP);
     // (The scan as the tail of the histogram kernel -- the frame's last workgroup to finish runs it -- was measured in round 4: a workgroup must
     // release its rows device-wide before it draws its ticket, and an agent-scope fence writes the XCD's L2 back: 62 us -> 2.9 ms.)
-    if (vec) model_hist_kernel<true, L><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
-    else     model_hist_kernel<false, L><<<dim3(T, B), 256, (size_t)KP * 12, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
+    if (hist_vec(P, seg, ri)) model_hist_kernel<true, L><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
+    else                      model_hist_kernel<false, L><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
     LAUNCH_CHECK();
     if constexpr (sizeof(L) == 1) {
         const ScanArgs sa = {ri, seg, ground, P, M, KP, T, scan_kp2(M), lay.sums, lay.flags, lay.hist, model, counts, nnz};
@@ -3099,6 +3075,10 @@ extern "C" int rpcc_point_model_wide(const float *ri, const uint16_t *seg, const
 // a10 + a11  intra-prediction, residual, uniform quantisation, ordered scatter
 //            (cpp_modules.cpp:248-285, tools/compress.py:106, cpp_modules.cpp:288-334)
 // ================================================================================================
+// The 16-segment tile layout.  The quantiser left it in round 3 (predict_quantize_body below); the decoder (decode_kernel,
+// codec_kernels.h) and the label-ordered lists (label_order_body, plane_kernels.h) keep it -- their stores and gathers are
+// lane-consecutive in it, see launch_label_order -- and share the functions below, so that the decoder's gather stays the
+// inverse of the encoder's scatter.
 // A 256-thread workgroup owns one 1024-pixel tile as 16 segments (4 passes x 4 waves) of 64
 // consecutive pixels.  Rank of a pixel inside its label = tile offset (model_scan_kernel) + pixels of
 // that label in earlier segments + earlier lanes of its own segment (ballot + popcount).
@@ -3119,6 +3099,39 @@ __device__ __forceinline__ void segment_prefix(uint32_t *segcnt, int SEGP, const
         if (ok) segcnt[sgi * SEGP + k] = tile_off[k] + v - c;
     }
 }
+// Position in the frame's label-ordered stream of the thread's pixel of pass j (the tile's pixel j * 256 + threadIdx.x), which carries label
+// lab, or -1 for none.  segment_rank (every pass; all 256 threads; segcnt [16][SEGP] zero behind a barrier) counts the segment's labels into
+// segcnt and returns the pixel's rank among its label in its segment; segment_offsets (once, after the four passes; tile_off [K], the tile's
+// offsets per label, staged) turns segcnt into first positions, between barriers; segment_slot is then the pixel's position (lab >= 0 only).
+// (Three functions, not one over the thread's four pixels, to keep the parent's machine code: the ranks stay the caller's scalars, and each
+// caller reads segcnt where it uses the position: profiles/HISTORY.md, "Reference rules stated once".)
+__device__ __forceinline__ int segment_rank(int j, int lab, uint32_t *segcnt, int SEGP) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int rank = 0, todo = lab;
+    while (true) {
+        const unsigned long long pending = __ballot(todo >= 0);
+        if (!pending) break;
+        const int leader = (int)__ffsll((long long)pending) - 1;
+        const int cur = __builtin_amdgcn_readlane(todo, leader);
+        const unsigned long long same = __ballot(todo == cur);
+        if (todo == cur) {
+            rank = __popcll(same & ((1ull << lane) - 1ull));
+            if (lane == leader) segcnt[(j * 4 + wave) * SEGP + cur] = (uint32_t)__popcll(same);
+            todo = -1;
+        }
+    }
+    return rank;
+}
+__device__ __forceinline__ void segment_offsets(uint32_t *segcnt, int SEGP, const uint32_t *tile_off, int K) {
+    __syncthreads();
+    segment_prefix(segcnt, SEGP, tile_off, K);
+    __syncthreads();
+}
+__device__ __forceinline__ uint32_t segment_slot(int j, int lab, int rank, const uint32_t *segcnt, int SEGP) {
+    return segcnt[(j * 4 + (int)(threadIdx.x >> 6)) * SEGP + lab] + (uint32_t)rank;
+}
+// their LDS: segcnt u32 [16][KP + 1] | tile_off u32 [KP]
+static inline size_t segment_lds_bytes(int KP) { return (size_t)16 * (KP + 1) * 4 + (size_t)KP * 4; }
 
 // RESIDUAL_ONLY: the quantiser's own seam (uniform_quantize(seg_idx, residual, acc)): no prediction, so ri, tm and
 // model are not read at all (they may be NULL).
@@ -3165,13 +3178,7 @@ __device__ __forceinline__ void predict_quantize_body(const float *__restrict__ 
     float rv[4], ray[12], rin[4];
     if (VEC) {
         const uint32_t q = (uint32_t)(nval > 0 ? p0 : 0);
-        if (sizeof(L) == 1) {
-            const uint32_t l4 = ld_at(reinterpret_cast<const uint32_t *>(seg), q);
-            lab[0] = (int)(l4 & 255u); lab[1] = (int)((l4 >> 8) & 255u); lab[2] = (int)((l4 >> 16) & 255u); lab[3] = (int)(l4 >> 24);
-        } else {   // four 16-bit labels: one 8-byte load
-            const uint2 l8 = ld_at(reinterpret_cast<const uint2 *>(seg), q * 2u);
-            lab[0] = (int)(l8.x & 0xFFFFu); lab[1] = (int)(l8.x >> 16); lab[2] = (int)(l8.y & 0xFFFFu); lab[3] = (int)(l8.y >> 16);
-        }
+        load_labels4(seg, q, lab);
         if (RESIDUAL_ONLY) {
 #pragma unroll
             for (int e = 0; e < 4; e++) rv[e] = 0.0f;
@@ -3220,13 +3227,10 @@ __device__ __forceinline__ void predict_quantize_body(const float *__restrict__ 
         rank[e] = 0;
         if (e < nval) {
             const float4 pm = smodel[l];
-            float pr;
-            if (pm.x + pm.y + pm.z == 0.0f) pr = pm.w;                                          // cpp_modules.cpp:271-272
-            else pr = -pm.w / (pm.x * ray[3 * e] + pm.y * ray[3 * e + 1] + pm.z * ray[3 * e + 2]);  // :275-277
+            const float pr = intra_pred(pm.x, pm.y, pm.z, pm.w, ray[3 * e], ray[3 * e + 1], ray[3 * e + 2]);
             if (!RESIDUAL_ONLY && pred_out) st_at(pred_out, (uint32_t)(p0 + e) * 4u, pr);
             const float res = (RESIDUAL_ONLY || residual_in) ? rin[e] : rv[e] - pr;            // compress.py:106
-            const float step = label_acc ? sacc[l] : acc;                                      // cpp_modules.cpp:404,419
-            qv[e] = (int)roundf(res / step);                                                    // cpp_modules.cpp:315
+            qv[e] = quantise(res, label_acc ? sacc[l] : acc);
             keep = (l == 1) ? -1 : l;                                                           // label 1 is skipped (:314)
         }
         lab[e] = keep;
@@ -3240,11 +3244,7 @@ __device__ __forceinline__ void predict_quantize_body(const float *__restrict__ 
 #pragma unroll
     for (int e = 0; e < 4; e++) pend[e] = __ballot(lab[e] >= 0);
     while ((pend[0] | pend[1] | pend[2] | pend[3]) != 0ull) {
-        int cur;
-        if (pend[0])      cur = __builtin_amdgcn_readlane(lab[0], (int)__ffsll((long long)pend[0]) - 1);
-        else if (pend[1]) cur = __builtin_amdgcn_readlane(lab[1], (int)__ffsll((long long)pend[1]) - 1);
-        else if (pend[2]) cur = __builtin_amdgcn_readlane(lab[2], (int)__ffsll((long long)pend[2]) - 1);
-        else              cur = __builtin_amdgcn_readlane(lab[3], (int)__ffsll((long long)pend[3]) - 1);
+        const int cur = round_label(lab, pend);
         unsigned long long m[4];
         int below = 0, total = 0;
 #pragma unroll
@@ -3306,6 +3306,14 @@ __global__ __launch_bounds__(256) void predict_quantize_multi_kernel(const Multi
     if (a.vec) predict_quantize_body<false, true>(a.ri, a.tm, a.seg, a.model, a.hist, acc, a.label_acc, nullptr, a.P, M, KP, a.T, a.q16, nullptr, nullptr, a.epoch_inc, b, t);
     else       predict_quantize_body<false, false>(a.ri, a.tm, a.seg, a.model, a.hist, acc, a.label_acc, nullptr, a.P, M, KP, a.T, a.q16, nullptr, nullptr, a.epoch_inc, b, t);
 }
+// predict_quantize_body's LDS (smodel float4 [KP] | wcnt u32 [4][KP] | soff u32 [KP] | sacc f32 [KP]) and whether a group may take its VEC form:
+// every 4-pixel load it issues (seg; ri and the rays unless the residual is handed in without a prediction; residual_in if given) is aligned and
+// never straddles the frame's end (resid: that case, RESIDUAL_ONLY).  The fused batch hands no residual in: quantise_vec(P, seg, ri, tm, nullptr, false).
+static inline size_t quantise_lds_bytes(int KP) { return (size_t)KP * 16 + (size_t)4 * KP * 4 + (size_t)KP * 4 + (size_t)KP * 4; }
+template <class L>
+static inline bool quantise_vec(int P, const L *seg, const float *ri, const float *tm, const float *residual_in, bool resid) {
+    return (P & 3) == 0 && seg4_aligned(seg) && (resid || (aligned16(ri) && aligned16(tm))) && (!residual_in || aligned16(residual_in));
+}
 
 template <class L>
 static int launch_predict_quantize(const float *ri, const float *tm, const L *seg, const float *model, float acc,
@@ -3313,10 +3321,8 @@ static int launch_predict_quantize(const float *ri, const float *tm, const L *se
                                    int32_t *q32, float *pred, void *ws, hipStream_t st, int32_t *epoch_inc = nullptr) {
     const int KP = kpad(M), T = ntiles(P);
     const WsLayout lay = ws_layout(ws, B, P, M);
-    const size_t sh = (size_t)KP * 16 + (size_t)4 * KP * 4 + (size_t)KP * 4 + (size_t)KP * 4;
-    const bool resid = residual_in && !pred;
-    const bool vec = (P & 3) == 0 && seg4_aligned(seg) && (resid || (aligned16(ri) && aligned16(tm))) &&
-                     (!residual_in || aligned16(residual_in));
+    const size_t sh = quantise_lds_bytes(KP);
+    const bool resid = residual_in && !pred, vec = quantise_vec(P, seg, ri, tm, residual_in, resid);
 #define PQ_LAUNCH(R_, V_) predict_quantize_kernel<R_, V_, L><<<dim3(T, B), 256, sh, st>>>(ri, tm, seg, model, lay.hist, acc, label_acc, residual_in, P, M, KP, T, q16, q32, pred, epoch_inc)
     if (resid) { if (vec) PQ_LAUNCH(true, true); else PQ_LAUNCH(true, false); }
     else       { if (vec) PQ_LAUNCH(false, true); else PQ_LAUNCH(false, false); }
@@ -3403,8 +3409,7 @@ extern "C" int rpcc_decode(const uint8_t *seg, const int16_t *q16, const float *
     DecodeSteps steps;
     steps.levels = levels;
     for (int i = 0; i < 8; i++) steps.acc[i] = i < (levels ? levels : 1) ? level_acc[i] : 0.0;
-    const size_t sh = (size_t)KP * 4 * 4 + (size_t)16 * (KP + 1) * 4 + (size_t)KP * 4;
-    decode_kernel<<<dim3(T, B), 256, sh, st>>>(seg, q16, model, tm, L.hist, salience, steps, P, M, KP, T, ri_rec, pc_rec);
+    decode_kernel<<<dim3(T, B), 256, decode_lds_bytes(KP), st>>>(seg, q16, model, tm, L.hist, salience, steps, P, M, KP, T, ri_rec, pc_rec);
     LAUNCH_CHECK();
     return RPCC_OK;
 }
@@ -3558,7 +3563,7 @@ template <class L>
 static int launch_label_order(const float *ri, const float *tm, const L *seg, int B, int P, int M, void *ws, void *extra, hipStream_t st) {
     const int KP = kpad(M), T = ntiles(P);
     const WsLayout lay = ws_layout(ws, B, P, M);
-    const size_t sh = (size_t)16 * (KP + 1) * 4 + (size_t)KP * 4;
+    const size_t sh = label_order_lds_bytes(KP);
     // (the quantiser's round-3 layout -- four consecutive pixels per lane -- was tried here as well: 121 us against 97 us, because a
     // lane's four 16-byte point stores then lie 64 bytes apart from the next lane's; this kernel is bound by its 255 MB of stores)
     if constexpr (sizeof(L) == 2) HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&label_order_kernel<L>), (int)sh));   // above 64 KB
@@ -3833,19 +3838,18 @@ static int mixed_labels(const BatchPlan *pl, int G, hipStream_t st) {
         const int T = ntiles(p.P);
         const bool point = io->model_method == 0;
         const float *ri = point ? io->ri : nullptr;   // (the plane model needs no range sums)
-        const bool vec = (p.P & 3) == 0 && seg4_aligned(io->seg) && (ri == nullptr || aligned16(ri));
-        multi_add(mh, HistGroup{ri, io->seg, p.P, T, vec ? 1 : 0, p.L.sums, p.L.flags, p.L.hist}, p.Bs, T);
+        multi_add(mh, HistGroup{ri, io->seg, p.P, T, hist_vec(p.P, io->seg, ri) ? 1 : 0, p.L.sums, p.L.flags, p.L.hist}, p.Bs, T);
         multi_add(ms, ScanArgs{ri, io->seg, point ? io->ground : nullptr, p.P, M, KP, T, scan_kp2(M), p.L.sums, p.L.flags, p.L.hist,
                                point ? io->model : nullptr, io->counts, io->nnz}, p.Bs, 1);
         const PlaneLayout pa = plane_layout(p.extra, p.Bs, p.P);
         if (!point) multi_add(mo, OrderGroup{io->seg, p.L.hist, p.P, T, pa.order, io->ri, io->tm, pa.pts4}, p.Bs, T);
     }
-    model_hist_multi_kernel<<<mh.first[mh.n], 256, (size_t)KP * 12, st>>>(mh, KP);
+    model_hist_multi_kernel<<<mh.first[mh.n], 256, hist_lds_bytes(KP), st>>>(mh, KP);
     LAUNCH_CHECK();
     model_scan_multi_kernel<<<ms.first[ms.n], SCAN_THREADS, 0, st>>>(ms);
     LAUNCH_CHECK();
     if (mo.n > 0) {
-        label_order_multi_kernel<<<mo.first[mo.n], 256, (size_t)16 * (KP + 1) * 4 + (size_t)KP * 4, st>>>(mo, M, KP);
+        label_order_multi_kernel<<<mo.first[mo.n], 256, label_order_lds_bytes(KP), st>>>(mo, M, KP);
         LAUNCH_CHECK();
     }
     return RPCC_OK;
@@ -3868,7 +3872,7 @@ static int mixed_quantise(const BatchPlan *pl, int G, hipStream_t st) {
                                           p.label_acc}, p.Bs, 1);
         }
         const int T = ntiles(p.P);
-        const bool vec = (p.P & 3) == 0 && seg4_aligned(io->seg) && aligned16(io->ri) && aligned16(io->tm);
+        const bool vec = quantise_vec(p.P, io->seg, io->ri, io->tm, nullptr, false);
         // (every group's kernel advances its own workspace's epoch: its frame 0 / tile 0 workgroup)
         multi_add(mq, QuantGroup{io->ri, io->tm, io->model, p.label_acc, io->seg, p.L.hist, p.P, T, vec ? 1 : 0, io->q16, p.epoch}, p.Bs, T);
     }
@@ -3876,8 +3880,7 @@ static int mixed_quantise(const BatchPlan *pl, int G, hipStream_t st) {
         salience_levels_multi_kernel<<<msal.first[msal.n], 256, 0, st>>>(msal, M);
         LAUNCH_CHECK();
     }
-    const size_t sh = (size_t)KP * 16 + (size_t)4 * KP * 4 + (size_t)KP * 4 + (size_t)KP * 4;
-    predict_quantize_multi_kernel<<<mq.first[mq.n], 256, sh, st>>>(mq, pl[0].acc, M, KP);
+    predict_quantize_multi_kernel<<<mq.first[mq.n], 256, quantise_lds_bytes(KP), st>>>(mq, pl[0].acc, M, KP);
     LAUNCH_CHECK();
     return RPCC_OK;
 }

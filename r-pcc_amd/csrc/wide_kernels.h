@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void wide_positions_kernel(const uint32_t *__r
         order[(int64_t)b * P + o] = p;
         if (pts4) {
             const float r = ri[(int64_t)b * P + p];
-            pts4[(int64_t)b * P + o] = make_float4(r * tm[3 * p], r * tm[3 * p + 1], r * tm[3 * p + 2], r);  // transformer.py:94-101
+            pts4[(int64_t)b * P + o] = label_point(r, tm[3 * p], tm[3 * p + 1], tm[3 * p + 2]);
         }
     }
 }
@@ -185,24 +185,8 @@ __global__ __launch_bounds__(256) void wide_point_model_kernel(const float *__re
                                                                const int32_t *__restrict__ flags, int P, int K, float *__restrict__ model) {
     const int b = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
     if (k >= K) return;
-    float *row = model + ((int64_t)b * K + k) * 4;
-    if (k == 0) {
-        row[0] = (float)ground[4 * b]; row[1] = (float)ground[4 * b + 1]; row[2] = (float)ground[4 * b + 2]; row[3] = (float)ground[4 * b + 3];
-    } else if (k == 1) {
-        row[0] = row[1] = row[2] = row[3] = 0.0f;
-    } else {
-        const int total = counts[(int64_t)b * K + k];
-        double s;
-        if (flags[4 * b]) {   // sequential double accumulation in row-major order (cpp_modules.cpp:514)
-            s = 0.0;
-            for (int p = 0; p < P; p++)
-                if (seg[(int64_t)b * P + p] == (L)k) s += (double)ri[(int64_t)b * P + p];
-        } else {
-            s = (double)(long long)sums[(int64_t)b * K + k] * (1.0 / 268435456.0);
-        }
-        row[0] = row[1] = row[2] = 0.0f;
-        row[3] = total == 0 ? u2f(0xFFC00000u) : (float)(s / (double)total);
-    }
+    // (the sums are unsigned here: below 2^63, so through long long as the byte-label scan's int64 ones)
+    point_model_row(model, ground, flags, seg, ri, P, K, b, k, (long long)sums[(int64_t)b * K + k], counts[(int64_t)b * K + k]);
 }
 // a10 + a11 / a13: prediction, residual, quantisation, the integer to its position (cpp_modules.cpp:248-285,288-334, compress.py:106)
 template <class L>
@@ -216,13 +200,8 @@ __global__ __launch_bounds__(256) void wide_quantise_kernel(const float *__restr
     if (o < 0) return;
     const int l = seg[g];
     const float *m = model + ((int64_t)b * K + l) * 4;
-    const float p0 = m[0], p1 = m[1], p2 = m[2], p3 = m[3];
-    float pr;
-    if (p0 + p1 + p2 == 0.0f) pr = p3;
-    else pr = -p3 / (p0 * tm[3 * p] + p1 * tm[3 * p + 1] + p2 * tm[3 * p + 2]);
-    const float res = ri[g] - pr;
-    const float step = label_acc ? label_acc[(int64_t)b * K + l] : acc;
-    q16[(int64_t)b * P + o] = (int16_t)(int)roundf(res / step);   // astype(np.int16): two's-complement truncation
+    const float res = ri[g] - intra_pred(m[0], m[1], m[2], m[3], tm[3 * p], tm[3 * p + 1], tm[3 * p + 2]);
+    q16[(int64_t)b * P + o] = (int16_t)quantise(res, label_acc ? label_acc[(int64_t)b * K + l] : acc);   // astype(np.int16): two's-complement truncation
 }
 // f3: the decoder's body on the positions (decode_kernel for any K)
 template <class L>
@@ -236,13 +215,11 @@ __global__ __launch_bounds__(256) void wide_decode_kernel(const L *__restrict__ 
     const float *m = model + ((int64_t)b * K + l) * 4;
     const float p0 = m[0], p1 = m[1], p2 = m[2], p3 = m[3];
     const float tx = tm[3 * p], ty = tm[3 * p + 1], tz = tm[3 * p + 2];
-    float pr;
-    if (p0 + p1 + p2 == 0.0f) pr = p3;
-    else pr = -p3 / (p0 * tx + p1 * ty + p2 * tz);
+    const float pr = intra_pred(p0, p1, p2, p3, tx, ty, tz);
     float res = 0.0f;
     if (o >= 0) {
-        const double st = steps.levels ? steps.acc[min((int)salience[(int64_t)b * K + l], steps.levels - 1)] : steps.acc[0];
-        res = (float)((double)q16[(int64_t)b * P + o] * st);
+        const double st = dequant_step(steps, salience, (int64_t)b * K + l);
+        res = dequant(q16[(int64_t)b * P + o], st);
     }
     const float rec = pr + res;
     ri_rec[g] = rec;

@@ -347,26 +347,33 @@ def test_fps_xyz_takes_the_kernel_the_point_order_suits(env):
 
 
 def test_point_model_sequential_fallback(env):
-    """Ranges outside the fixed-point window [2^-5, 2^8) take the exact sequential fp64 path."""
+    """Ranges outside the fixed-point window [2^-5, 2^8) take the exact sequential fp64 path: byte labels (model_scan_kernel) and, at
+    cluster_num = 300, the uint16 stage entry (rpcc_point_model_wide: model_scan_wide_kernel).  16 x 1800: P is no multiple of the tile."""
     torch, ops, orc = env["torch"], env["ops"], env["orc"]
     rng = np.random.default_rng(9)
     H, W = 16, 1800
     seg = np.repeat(rng.integers(0, 102, (H, W // 8)), 8, axis=1).astype(np.uint8)
     seg[seg == 60] = 61                                            # an empty label -> NaN row
-    ri = rng.uniform(0.5, 80, (H, W)).astype(np.float32)
-    ri2 = ri.copy()
-    ri2[3, 5:50] = rng.uniform(1e-4, 0.02, 45)                     # < 2^-5
-    ri2[9, 100:140] = rng.uniform(300, 5000, 40)                   # >= 2^8
+    base = rng.uniform(0.5, 80, (H, W)).astype(np.float32)
+    low, high = rng.uniform(1e-4, 0.02, 45), rng.uniform(300, 5000, 40)   # < 2^-5, >= 2^8
+    seg16 = np.repeat(rng.integers(0, 302, (H, W // 8)), 8, axis=1).astype(np.uint16)
+    seg16[seg16 == 260] = 261
     gm = np.array([[0.01, -0.02, -0.999, -1.7]] * 2)
-    for arr in (ri, ri2):
-        arr[seg == 1] = 0
-    model, counts = ops.point_model(_to(env, np.stack([ri, ri2])), _to(env, np.stack([seg, seg])), _to(env, gm), 100)
-    for i, arr in enumerate((ri, ri2)):
-        exp = orc.point_modeling(arr, seg.astype(np.int32))
-        got = model[i].cpu().numpy()
-        assert _beq(got[2:exp.shape[0], 3], exp[2:])
-        assert got.view(np.uint32)[60, 3] == 0xFFC00000
-        assert _beq(got[0], gm[i].astype(np.float32)) and not got[1].any()
+    for sg, M, empty in ((seg, 100, 60), (seg16, 300, 260)):
+        ri, ri2 = base.copy(), base.copy()
+        ri2[3, 5:50] = low
+        ri2[9, 100:140] = high
+        for arr in (ri, ri2):
+            arr[sg == 1] = 0
+        assert int(sg.max()) == M + 1 and (sg[3, 5:50] >= 2).any() and (sg[9, 100:140] >= 2).any()
+        model, counts = ops.point_model(_to(env, np.stack([ri, ri2])), _to(env, np.stack([sg, sg])), _to(env, gm), M)
+        for i, arr in enumerate((ri, ri2)):
+            exp = orc.point_modeling(arr, sg.astype(np.int32))
+            got = model[i].cpu().numpy()
+            assert exp.shape[0] == M + 2 and _beq(got[2:, 3], exp[2:]), (M, i)
+            assert got.view(np.uint32)[empty, 3] == 0xFFC00000, (M, i)
+            assert _beq(got[0], gm[i].astype(np.float32)) and not got[1].any() and not got[2:, :3].any(), (M, i)
+            assert np.array_equal(counts[i].cpu().numpy(), np.bincount(sg.reshape(-1), minlength=M + 2)), (M, i)
 
 
 def test_predict_quantize_with_plane_rows(env):

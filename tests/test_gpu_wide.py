@@ -73,6 +73,37 @@ def test_wide_batch_vs_oracle(env, M, uniform, method):
             assert np.array_equal(buf.salience[i, :o["salience"].shape[0]].cpu().numpy(), o["salience"].astype(np.uint8)), tag
 
 
+def test_wide_point_model_sequential_fallback(env):
+    """cluster_num = 1100 (the radix-sort kernels): frames with ranges outside the point model's fixed-point window [2^-5, 2^8) take the sequential
+    fp64 loop of wide_point_model_kernel.  The rows are compared with the oracle's point model of the batch's OWN range image and labels, so the
+    case pins this branch alone, whatever centres the FPS chose."""
+    torch, ops, orc, dev = env["torch"], env["ops"], env["orc"], env["dev"]
+    gd, g, geom, tm = _geom(env, "VelodyneVLP16")
+    ids, M = [7400, 7401], 1100
+    frames, _, _ = _batch(env, gd, g, ids)
+    rng = np.random.default_rng(12)
+    for f in frames:                                                  # same directions, ranges beyond 256 m and below 2^-5 m
+        pick = rng.choice(f.shape[0], 400, replace=False)
+        new_r = np.concatenate([rng.uniform(300, 2000, 300), rng.uniform(1e-3, 0.02, 100)])
+        f[pick] = (f[pick] * (new_r / np.linalg.norm(f[pick].astype(np.float64), axis=1))[:, None]).astype(np.float32)
+    offs = np.zeros(len(frames) + 1, np.int64)
+    offs[1:] = np.cumsum([f.shape[0] for f in frames])
+    ground = np.array([[0.01, -0.02, -0.9997, -1.72], [-0.01, 0.005, -0.9999, -1.75]])
+    buf = ops.BatchBuffers(len(ids), geom, M, dev)
+    ops.compress_batch(torch.from_numpy(np.concatenate(frames)).to(dev), torch.from_numpy(offs).to(dev), torch.from_numpy(tm).to(dev),
+                       torch.from_numpy(ground).to(dev), buf)
+    torch.cuda.synchronize()
+    ri, seg, model = buf.ri.cpu().numpy(), buf.seg.cpu().numpy().astype(np.int32), buf.model.cpu().numpy()
+    for i in range(len(ids)):
+        r = ri[i][seg[i] >= 2]
+        assert ((r < 2.0 ** -5) | (r >= 256.0)).any(), "frame %d must take the fallback" % i
+        exp = orc.point_modeling(ri[i], seg[i])
+        n = exp.shape[0]
+        assert np.array_equal(model[i, 2:n, 3].view(np.uint32), exp[2:].view(np.uint32)), i
+        assert (model[i, n:, 3].view(np.uint32) == 0xFFC00000).all() and not model[i, 2:, :3].any(), i     # labels no pixel carries
+        assert np.array_equal(model[i, 0].view(np.uint32), ground[i].astype(np.float32).view(np.uint32)) and not model[i, 1].any(), i
+
+
 def test_mid_cluster_counts_with_the_bruteforce_fps_and_groundless_frames(env):
     """cluster_num = 300 through the fused plan (run_batch<uint16_t>): the one-pass-per-centre FPS (RPCC_FPS_BRUTEFORCE) gives the same centres, labels
     and integers as the pruned one, and a batch that holds a sweep without ground returns (whole-cloud fit, scored chip-wide) equals the oracle."""

@@ -1,7 +1,7 @@
 /*
  * rpcc_deflate.h -- C ABI of librpcc_deflate.so: the gzip / deflate entropy back-end on the MI355X (gfx950), the device
  * counterpart of the reference's basic_compressor 'deflate' / 'gzip' (utils/compress_utils.py:232-310, gzip.compress).  A
- * library of its own, apart from librpcc_hip.so.  There is no device decoder: any inflate reads the streams.
+ * library of its own, apart from librpcc_hip.so.  Any inflate reads the streams; the device decoder is librpcc_inflate.so (rpcc_inflate.h).
  *
  * Conventions as in rpcc_lz4.h: plain pointers and sizes; every pointer marked "dev" is a device pointer; kernels are
  * enqueued on the caller's hipStream_t (passed as void*) and nothing synchronises; the library allocates nothing; 0 = OK,

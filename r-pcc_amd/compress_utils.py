@@ -199,7 +199,7 @@ class BasicCompressor:
     """utils/compress_utils.py:232-310.  bzip2 / deflate are stdlib; lz4 is the lz4 package (lz4==0.7.0 API in the reference)
     where it is installed, else rpcc_amd.lz4_codec (the same dumps / loads forms, coded on the GPU).  device_entropy=True
     (opt-in) sends 'deflate' / 'gzip' through rpcc_amd.deflate_codec: gzip members coded on the GPU, other bytes than
-    gzip.compress's, read by the same gzip.decompress."""
+    gzip.compress's, read by the same gzip.decompress -- and, under the same flag, by rpcc_amd.inflate_codec on the GPU."""
 
     METHODS = ["lz4", "bzip2", "gzip", "deflate"]
 
@@ -242,10 +242,27 @@ class BasicCompressor:
             return dict(zip(data_dict, self.batch_codec()[1]([np.ascontiguousarray(v) for v in data_dict.values()])))
         return {k: self.compress(v) for k, v in data_dict.items()}
 
-    def decompress_dict(self, data_dict):
+    def batch_decoder(self):
+        """The list decoder of the back-end that decodes a list of streams on the device at once, or None."""
         if self.lz4_batched():
-            return dict(zip(data_dict, self._lz4().loads_many(list(data_dict.values()))))
+            return self._lz4().loads_many
+        if self.deflate_batched():
+            from . import inflate_codec
+            return inflate_codec.decompress_many
+        return None
+
+    def decompress_dict(self, data_dict):
+        if self.batch_decoder():
+            return dict(zip(data_dict, self.batch_decoder()(list(data_dict.values()))))
         return {k: self.decompress(v) for k, v in data_dict.items()}
+
+    def decompress_dicts(self, data_dicts):
+        """decompress_dict over the frames of a chunk: every array of the chunk in one call where batch_decoder() exists."""
+        data_dicts = list(data_dicts)
+        if not self.batch_decoder() or not data_dicts:
+            return [self.decompress_dict(d) for d in data_dicts]
+        outs = iter(self.batch_decoder()([v for d in data_dicts for v in d.values()]))
+        return [{k: next(outs) for k in d} for d in data_dicts]
 
     def compress(self, np_array):
         buf = np.ascontiguousarray(np_array)
@@ -262,6 +279,8 @@ class BasicCompressor:
     def decompress(self, bitstream):
         if self.method_name == "bzip2":
             return bz2.decompress(bitstream)
+        if self.deflate_batched():
+            return self.batch_decoder()([bitstream])[0]
         if self.method_name in ("gzip", "deflate"):
             return gzip.decompress(bitstream)
         if self.method_name == "lz4":

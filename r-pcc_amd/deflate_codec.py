@@ -1,7 +1,7 @@
 """The gzip back-end of basic_compressor 'deflate' / 'gzip' on the device (librpcc_deflate.so).
 
 compress() gives one gzip member, as gzip.compress does: other bytes (the parse and the code lengths are the build's own), the
-same format, so gzip.decompress -- the reference's decoder -- reads it.  There is no device decoder.  compress_many codes a
+same format, so gzip.decompress -- the reference's decoder -- reads it, and so does inflate_codec on the device.  compress_many codes a
 list with one copy to the device, the launches and one copy back; encode_descriptors is the device form the batch pipeline
 uses, and lz4_codec.pack_containers compacts its output into .rpcc containers."""
 import numpy as np

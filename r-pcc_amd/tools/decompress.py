@@ -26,11 +26,12 @@ def stream_cluster_num(segment_cfg):
     return None if segment_cfg["segment_method"] == "DBSCAN" else segment_cfg["cluster_num"]
 
 
-def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy, level_acc, uniform, want_points=True):
+def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy, level_acc, uniform, want_points=True, decoded=None):
     """decompress_point_cloud + dequantise + predict + back-project (tools/decompress.py:79-112).  cluster_num None
-    (DBSCAN, stream_cluster_num): the labels 0 .. rows - 1 of the stream's model rows."""
+    (DBSCAN, stream_cluster_num): the labels 0 .. rows - 1 of the stream's model rows.  decoded: blob_dict's arrays with the entropy
+    stage already undone (basic_compressor.decompress_dicts over a chunk of frames)."""
     H, W = transformer.H, transformer.W
-    d = basic_compressor.decompress_dict(blob_dict)
+    d = basic_compressor.decompress_dict(blob_dict) if decoded is None else decoded
     # The .rpcc file stores no configuration (as in the reference): a wrong --lidar / cluster_num / framework shows up as
     # payload sizes that do not fit.  Check them here instead of letting the kernels index past their buffers.
     if len(d["plane_param"]) % 16 != 0:

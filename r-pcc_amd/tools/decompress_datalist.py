@@ -18,6 +18,9 @@ from rpcc_amd.tools.compress import make_parser, resolve_cfg  # noqa: E402
 from rpcc_amd.tools.decompress import decode_frame, stream_cluster_num  # noqa: E402
 
 
+CHUNK = 32   # .rpcc files read and entropy-decoded together
+
+
 def decompress(args):
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -25,18 +28,20 @@ def decompress(args):
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
     dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device)
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
-    for i in shard_indices(len(dataset), rank, world):
-        name = dataset.data_list[i]
-        cd = read_compressed_bitstream(name, uniform=uniform)
-        rec, pc, _ = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
-                                  level_acc, uniform)
-        rel = name[1:] if name.startswith("/") else name
-        out = os.path.join(args.output_dir, rel)
-        out = out.replace(out.split(".")[-1], "bin")
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3))
-        if args.output:
-            print("%s -> %s (%d points)" % (name, out, int((rec != 0).sum())))
+    mine = list(shard_indices(len(dataset), rank, world))
+    for c0 in range(0, len(mine), CHUNK):
+        names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
+        cds = [read_compressed_bitstream(name, uniform=uniform) for name in names]
+        for name, cd, d in zip(names, cds, basic_compressor.decompress_dicts(cds)):   # the chunk's entropy stage in one call where the back-end has one
+            rec, pc, _ = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
+                                      level_acc, uniform, decoded=d)
+            rel = name[1:] if name.startswith("/") else name
+            out = os.path.join(args.output_dir, rel)
+            out = out.replace(out.split(".")[-1], "bin")
+            os.makedirs(os.path.dirname(out), exist_ok=True)
+            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3))
+            if args.output:
+                print("%s -> %s (%d points)" % (name, out, int((rec != 0).sum())))
 
 
 if __name__ == "__main__":

@@ -199,13 +199,16 @@ class BasicCompressor:
     """utils/compress_utils.py:232-310.  bzip2 / deflate are stdlib; lz4 is the lz4 package (lz4==0.7.0 API in the reference)
     where it is installed, else rpcc_amd.lz4_codec (the same dumps / loads forms, coded on the GPU).  device_entropy=True
     (opt-in) sends 'deflate' / 'gzip' through rpcc_amd.deflate_codec: gzip members coded on the GPU, other bytes than
-    gzip.compress's, read by the same gzip.decompress -- and, under the same flag, by rpcc_amd.inflate_codec on the GPU."""
+    gzip.compress's, read by the same gzip.decompress -- and, under the same flag, by rpcc_amd.inflate_codec on the GPU.
+    device_bunzip2=True (opt-in, a flag of its own) decodes 'bzip2' streams through rpcc_amd.bunzip2_codec on the GPU, with
+    bz2.decompress's bytes; 'bzip2' is compressed by bz2.compress under every flag."""
 
     METHODS = ["lz4", "bzip2", "gzip", "deflate"]
 
-    def __init__(self, compressor_yaml=None, method_name=None, device_entropy=False):
+    def __init__(self, compressor_yaml=None, method_name=None, device_entropy=False, device_bunzip2=False):
         self.method_name = None
         self.device_entropy = bool(device_entropy)
+        self.device_bunzip2 = bool(device_bunzip2)
         if compressor_yaml is not None:
             self.method_name = load_yaml(compressor_yaml)["basic_compressor"]
         if method_name is not None:
@@ -249,6 +252,9 @@ class BasicCompressor:
         if self.deflate_batched():
             from . import inflate_codec
             return inflate_codec.decompress_many
+        if self.device_bunzip2 and self.method_name == "bzip2":
+            from . import bunzip2_codec
+            return bunzip2_codec.decompress_many
         return None
 
     def decompress_dict(self, data_dict):
@@ -278,7 +284,7 @@ class BasicCompressor:
 
     def decompress(self, bitstream):
         if self.method_name == "bzip2":
-            return bz2.decompress(bitstream)
+            return self.batch_decoder()([bitstream])[0] if self.device_bunzip2 else bz2.decompress(bitstream)
         if self.deflate_batched():
             return self.batch_decoder()([bitstream])[0]
         if self.method_name in ("gzip", "deflate"):

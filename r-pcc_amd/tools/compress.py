@@ -49,6 +49,8 @@ def make_parser(datalist=False):
     p.add_argument("--basic_compressor", type=str, default=None, help="for manual setting.")
     p.add_argument("--device_entropy", action="store_true",
                    help="basic_compressor deflate / gzip: code the gzip members on the GPU (this build; other bytes, the same decoder).")
+    p.add_argument("--device_bunzip2", action="store_true",
+                   help="decompress tools, basic_compressor bzip2: decode the bzip2 streams on the GPU (this build; bz2.decompress's bytes).")
     p.add_argument("--accuracy", type=float, default=None, help="for manual setting.")
     p.add_argument("--segment_method", type=str, default=None, help="for manual setting.")
     p.add_argument("--cluster_num", type=int, default=None, help="for manual setting.")
@@ -84,7 +86,8 @@ def resolve_cfg(args):
     segment_cfg = {"segment_method": cfg["segment_method"], "ground_vertical_threshold": cfg["ground_threshold"],
                    "cluster_num": cfg["cluster_num"], "DBSCAN_eps": cfg["DBSCAN_eps"]}
     model_cfg = {"model_method": cfg["modeling_method"], "angle_threshold": cfg["plane_angle_threshold"]}
-    bc = BasicCompressor(compressor_yaml=args.compressor_yaml, device_entropy=getattr(args, "device_entropy", False))
+    bc = BasicCompressor(compressor_yaml=args.compressor_yaml, device_entropy=getattr(args, "device_entropy", False),
+                         device_bunzip2=getattr(args, "device_bunzip2", False))
     if args.basic_compressor is not None:
         bc.set_method(args.basic_compressor)
     if args.accuracy is not None:

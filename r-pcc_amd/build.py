@@ -28,6 +28,7 @@ LZ4_SRC, LZ4_DEPS, LZ4_LIB = _side_library("csrc_lz4", "lz4_kernels.hip", "rpcc_
 DEFLATE_SRC, DEFLATE_DEPS, DEFLATE_LIB = _side_library("csrc_deflate", "deflate_kernels.hip", "rpcc_deflate.h", "librpcc_deflate.so", _LZ)   # gzip back-end
 INFLATE_SRC, INFLATE_DEPS, INFLATE_LIB = _side_library("csrc_inflate", "inflate_kernels.hip", "rpcc_inflate.h", "librpcc_inflate.so")   # gzip decoder
 BUNZIP2_SRC, BUNZIP2_DEPS, BUNZIP2_LIB = _side_library("csrc_bunzip2", "bunzip2_kernels.hip", "rpcc_bunzip2.h", "librpcc_bunzip2.so")   # bzip2 decoder
+BZIP2_SRC, BZIP2_DEPS, BZIP2_LIB = _side_library("csrc_bzip2", "bzip2_kernels.hip", "rpcc_bzip2.h", "librpcc_bzip2.so")   # bzip2 encoder
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -103,6 +104,11 @@ def build_bunzip2(force=False, verbose=False):
     return _hipcc(BUNZIP2_SRC, BUNZIP2_LIB, BUNZIP2_DEPS, force, verbose)
 
 
+def build_bzip2(force=False, verbose=False):
+    """librpcc_bzip2.so: the bzip2 encoder kernels (csrc_bzip2/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(BZIP2_SRC, BZIP2_LIB, BZIP2_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -114,6 +120,7 @@ def build(force=False, verbose=False):
     build_deflate(force, verbose)
     build_inflate(force, verbose)
     build_bunzip2(force, verbose)
+    build_bzip2(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

@@ -201,14 +201,17 @@ class BasicCompressor:
     (opt-in) sends 'deflate' / 'gzip' through rpcc_amd.deflate_codec: gzip members coded on the GPU, other bytes than
     gzip.compress's, read by the same gzip.decompress -- and, under the same flag, by rpcc_amd.inflate_codec on the GPU.
     device_bunzip2=True (opt-in, a flag of its own) decodes 'bzip2' streams through rpcc_amd.bunzip2_codec on the GPU, with
-    bz2.decompress's bytes; 'bzip2' is compressed by bz2.compress under every flag."""
+    bz2.decompress's bytes.  device_bzip2=True (opt-in, a flag of its own) encodes 'bzip2' through rpcc_amd.bzip2_codec on the GPU:
+    valid bzip2 streams of the build's own bytes, read by the same bz2.decompress.  Without that flag 'bzip2' is
+    compressed by bz2.compress (or librpcc_host.so for a chunk of frames)."""
 
     METHODS = ["lz4", "bzip2", "gzip", "deflate"]
 
-    def __init__(self, compressor_yaml=None, method_name=None, device_entropy=False, device_bunzip2=False):
+    def __init__(self, compressor_yaml=None, method_name=None, device_entropy=False, device_bunzip2=False, device_bzip2=False):
         self.method_name = None
         self.device_entropy = bool(device_entropy)
         self.device_bunzip2 = bool(device_bunzip2)
+        self.device_bzip2 = bool(device_bzip2)
         if compressor_yaml is not None:
             self.method_name = load_yaml(compressor_yaml)["basic_compressor"]
         if method_name is not None:
@@ -231,6 +234,10 @@ class BasicCompressor:
         """True when 'deflate' / 'gzip' runs through rpcc_amd.deflate_codec (device_entropy), which codes a list of arrays at once."""
         return self.device_entropy and self.method_name in ("gzip", "deflate")
 
+    def bzip2_batched(self):
+        """True when 'bzip2' is encoded through rpcc_amd.bzip2_codec (device_bzip2), which codes a list of arrays at once."""
+        return self.device_bzip2 and self.method_name == "bzip2"
+
     def batch_codec(self):
         """(module, its list encoder) of the back-end that codes a list of arrays on the device at once, or None."""
         if self.lz4_batched():
@@ -238,6 +245,9 @@ class BasicCompressor:
         if self.deflate_batched():
             from . import deflate_codec
             return deflate_codec, deflate_codec.compress_many
+        if self.bzip2_batched():
+            from . import bzip2_codec
+            return bzip2_codec, bzip2_codec.compress_many
         return None
 
     def compress_dict(self, data_dict):
@@ -272,6 +282,8 @@ class BasicCompressor:
 
     def compress(self, np_array):
         buf = np.ascontiguousarray(np_array)
+        if self.bzip2_batched():
+            return self.batch_codec()[1]([buf])[0]
         if self.method_name == "bzip2":
             return bz2.compress(buf)
         if self.deflate_batched():

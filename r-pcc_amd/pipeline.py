@@ -14,7 +14,7 @@ class BatchCompressor:
 
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
                  model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
-                 device_entropy=False):
+                 device_entropy=False, device_bzip2=False):
         self.M = ops.check_cluster_num(cluster_num)   # (above 254: uint16 labels through the rpcc_*_wide entries; above 65533: refused by name)
         self.T = transformer
         self.device = torch.device(device) if device is not None else transformer.device
@@ -23,7 +23,7 @@ class BatchCompressor:
         self.uniform = uniform
         self.model_method = model_method
         self.cfg = compressor_cfg or {}
-        self.bc = BasicCompressor(method_name=basic_compressor, device_entropy=device_entropy)
+        self.bc = BasicCompressor(method_name=basic_compressor, device_entropy=device_entropy, device_bzip2=device_bzip2)
         self.seed = int(seed)
         self._buf = None        # the buffers of the most recent call (tests read them after compress())
         self._codec_ws = None
@@ -98,7 +98,8 @@ class BatchCompressor:
         return ctx
 
     def _device_containers(self, codec, B, buf, bits, nseq, sal, qp, sp):
-        """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), or 'deflate' / 'gzip' with device_entropy (deflate_codec):
+        """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), 'deflate' / 'gzip' with device_entropy (deflate_codec), or
+        'bzip2' with device_bzip2 (bzip2_codec):
         the batch's .rpcc containers are built in HBM (the codec's encode_descriptors over the arrays where they lie, then
         rpcc_lz4_pack_containers, which asks nothing of the streams' format) on the current stream.
         -> (containers, frame offsets / lengths)."""

@@ -105,6 +105,15 @@ def main():
             out["feature_sweep"][",".join(str(v) for v in params)] = {"in": ins(seg=seg, ri=ri), "f_written": T.sha(f_r[f_o != 0]),
                                                                       "k": T.sha(k_r)}
 
+        out["feature_classes"] = {}
+        for W, params in T.fc.FEATURE_PIN_DRAWS:
+            seg, ri = T._feature_class_inputs(W, params)
+            f_r, k_r = run_ref(tmp, "features", seg=seg, ri=ri, params=np.array(params))
+            f_o, k_o = orc.extract_features_with_segment(ri, seg, *params)
+            f_r, k_r = like(f_r, f_o), like(k_r, k_o)
+            out["feature_classes"]["%d:%s" % (W, ",".join(str(v) for v in params))] = {"in": ins(seg=seg, ri=ri), "f_written": T.sha(f_r[f_o != 0]),
+                                                                                      "k": T.sha(k_r)}
+
         seg = T._contour_inputs()
         cm_r, sq_r = run_ref(tmp, "contour", seg=seg)
         cm_o, sq_o = orc.extract_contour(seg)

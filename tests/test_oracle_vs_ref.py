@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import feature_cases as fc
 from oracle import oracle as orc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -206,6 +207,27 @@ def test_features_parameter_sweep_matches(man, params):
     wrote = f_o != 0
     assert sha(f_o[wrote]) == rec["f_written"], params
     assert sha(k_o) == rec["k"], params
+
+
+def _feature_class_inputs(W, params):
+    """The key-point image of a launch-variant case (tests/launch_variants.py), 96 rows high: outputs of at least 395 KB, which a fresh
+    process gets as zero pages (see test_features_parameter_sweep_matches; at 197 KB it does not)."""
+    return fc.feature_image(W, params, H=96)
+
+
+@pytest.mark.parametrize("W,params", fc.FEATURE_PIN_DRAWS, ids=["%d-%s" % (w, "-".join(str(v) for v in p)) for w, p in fc.FEATURE_PIN_DRAWS])
+def test_features_kernel_class_settings_match(man, W, params):
+    """The settings at which tests/test_gpu_launch_variants.py holds the key-point kernels to the restatement -- more than 32 segments,
+    flat_num 10, chunk lengths on both sides of 128, 256, 384 and 512, widths up to 4096 -- against the reference's C++, so that the
+    restatement is not its own witness there."""
+    rec = man["feature_classes"]["%d:%s" % (W, ",".join(str(v) for v in params))]
+    seg, ri = _feature_class_inputs(W, params)
+    check_inputs(rec, seg=seg, ri=ri)
+    f_o, k_o = orc.extract_features_with_segment(ri, seg, *params)
+    wrote = f_o != 0
+    assert k_o.max() >= 1
+    assert sha(f_o[wrote]) == rec["f_written"], (W, params)
+    assert sha(k_o) == rec["k"], (W, params)
 
 
 def _contour_inputs():

@@ -44,7 +44,7 @@ extern "C" {
 
 /* Caller's buffers (held by tests/test_gpu_buffers.py: exact sizes, hostile contents, guard bytes around them).
  * Work buffers -- `ws`, `scratch`, `fps_table`, sized by rpcc_workspace_bytes[_general], rpcc_wide_workspace_bytes,
- * rpcc_project_scratch_bytes, rpcc_fps_table_bytes, rpcc_plane_workspace_bytes, rpcc_codec_workspace_bytes -- need NO initialisation: they
+ * rpcc_project_scratch_bytes, rpcc_fps_table_bytes, rpcc_plane_workspace_bytes, rpcc_codec_workspace_bytes, rpcc_decompress_workspace_bytes -- need NO initialisation: they
  * may hold anything, including what an earlier call left there under other arguments (another B, P, M, point count or entry point), and a
  * buffer larger than asked for may be handed to calls of different shapes in turn.  Every entry clears or overwrites what it reads; the
  * fused batch compares its per-frame projection flags with a mark kept inside ws, and a stale word that happens to equal the mark only
@@ -66,8 +66,9 @@ extern "C" {
  * field).  A binding compares rpcc_version() with the RPCC_ABI_VERSION of the header it was built against before it calls anything else
  * (r-pcc_amd/_lib.py does).  100: round 3.  101: rpcc_batch_io.point_stride_bytes.  102: the uint16-label entries (rpcc_*_wide), rpcc_compress_batch_stages.
  * 103: the scanner-order window projection entry, the RPCC_PROJECT_* bits of rpcc_batch_io.flags, the uint16 stage entries (rpcc_assign_wide ...).
- * 104: the window projection entry and the RPCC_PROJECT_* bits removed (rpcc_batch_io.flags takes the FPS bits only). */
-#define RPCC_ABI_VERSION 104
+ * 104: the window projection entry and the RPCC_PROJECT_* bits removed (rpcc_batch_io.flags takes the FPS bits only).
+ * 105: rpcc_decompress_batch, rpcc_decompress_batch_wide, rpcc_decompress_workspace_bytes and the RPCC_STREAM_* status codes. */
+#define RPCC_ABI_VERSION 105
 int rpcc_version(void);
 const char *rpcc_last_error(void);
 
@@ -394,6 +395,55 @@ int rpcc_contour_encode_wide(const uint16_t *seg, int B, int H, int W, uint8_t *
 int rpcc_contour_decode_wide(const uint8_t *contour_bits, const uint16_t *idx_sequence, int B, int H, int W, uint16_t *seg, void *ws, void *stream);
 int rpcc_decode_wide(const uint16_t *seg, const int16_t *q16, const float *model, const float *tm, const double *level_acc, int levels,
                      const uint8_t *salience, int B, int P, int M, float *ri_rec, float *pc_rec, void *ws, void *stream);
+
+/* ---- f3 for a batch of streams: the decoding counterpart of rpcc_compress_batch ------------------------------------------------ *
+ * Takes the decoded payloads of B frames where the entropy decoders left them -- every row padded to the geometry's maximum -- and gives label maps,
+ * range images and points: the host checks of tools/decompress.py:decode_frame as one status per frame, then rpcc_contour_decode and rpcc_decode
+ * for the frames that pass.  Everything is queued on `stream`; nothing synchronises.
+ *   contour_bits   dev u8  [B, ceil(P/8)]
+ *   idx_sequence   dev u16 [B,P]
+ *   model          dev f32 [B,K,4]
+ *   q16            dev i16 [B,P]
+ *   salience       dev u8  [B,K]          (NULL in the uniform framework: levels == 0)
+ *   payload_len    dev i64 [B,5]          decoded byte counts in container order: salience_level, contour_map, idx_sequence, plane_param,
+ *                                         residual_quantized (the salience column is ignored in the uniform framework)
+ *   entropy_status dev i32 [B,5]          the entropy decoders' statuses in the same order, 0 = sound (salience column: likewise ignored)
+ *   tm, level_acc (HOST f64), levels, M   as in rpcc_decode;  H, W as in rpcc_contour_decode
+ *   status         dev i32 [B]     out    RPCC_STREAM_OK or RPCC_STREAM_E_*
+ *   seg            dev u8  [B,P]   out    (rpcc_decompress_batch_wide: u16 [B,P], 255 <= M <= RPCC_MAX_CLUSTERS_WIDE)
+ *   ri_rec         dev f32 [B,P]   out ;  pc_rec dev f32 [B,P,3] out (may be NULL)
+ *   ws             dev, rpcc_decompress_workspace_bytes(B, P, M) bytes (M above RPCC_MAX_CLUSTERS: the uint16 entry's layout)
+ * Whatever lies past a payload's stated length, in any input row, is not read as data: it may hold anything.  No byte outside a row is read.
+ * A model row or salience entry the stream does not hold counts as zero, as decode_frame pads them.
+ * The status of a frame is the first of these that applies, in decode_frame's order; rows = payload_len[plane_param] / 16:
+ *   E_ENTROPY   one of the frame's entropy statuses is not 0
+ *   E_PLANE     the plane payload is not a multiple of 16 bytes, or rows > K
+ *   E_CONTOUR   the contour payload is not ceil(P/8) bytes
+ *   E_WIDTH     the idx or the residual payload has an odd byte count
+ *   E_NSEQ      the number of idx entries is not the popcount of the first P contour bits (the pad bits of the last byte do not count)
+ *   E_LABEL     an idx entry is >= rows
+ *   E_SALIENCE  (non-uniform) the payload is longer than K, shorter than rows, or holds a level >= levels
+ *   E_RESIDUAL  the number of residual values is not the number of pixels whose recovered label is not 1
+ * (a negative length fails the check of its payload).  Outputs are written completely for every frame: a refused frame's seg, ri_rec and pc_rec
+ * rows are all zero bytes, and none of its payloads is used as an index.  RPCC_STREAM_E_CONTAINER is not produced here: callers that parse
+ * the containers (pipeline.BatchDecompressor) give it to a frame whose length prefixes do not fit its bytes. */
+#define RPCC_STREAM_OK 0
+#define RPCC_STREAM_E_ENTROPY 1
+#define RPCC_STREAM_E_PLANE 2
+#define RPCC_STREAM_E_CONTOUR 3
+#define RPCC_STREAM_E_WIDTH 4
+#define RPCC_STREAM_E_NSEQ 5
+#define RPCC_STREAM_E_LABEL 6
+#define RPCC_STREAM_E_SALIENCE 7
+#define RPCC_STREAM_E_RESIDUAL 8
+#define RPCC_STREAM_E_CONTAINER 9
+size_t rpcc_decompress_workspace_bytes(int B, int P, int M);
+int rpcc_decompress_batch(const uint8_t *contour_bits, const uint16_t *idx_sequence, const float *model, const int16_t *q16, const uint8_t *salience,
+                          const int64_t *payload_len, const int32_t *entropy_status, const float *tm, const double *level_acc, int levels, int B,
+                          int H, int W, int M, int32_t *status, uint8_t *seg, float *ri_rec, float *pc_rec, void *ws, void *stream);
+int rpcc_decompress_batch_wide(const uint8_t *contour_bits, const uint16_t *idx_sequence, const float *model, const int16_t *q16, const uint8_t *salience,
+                               const int64_t *payload_len, const int32_t *entropy_status, const float *tm, const double *level_acc, int levels, int B,
+                               int H, int W, int M, int32_t *status, uint16_t *seg, float *ri_rec, float *pc_rec, void *ws, void *stream);
 
 /* Developer hook (libraries built with -DRPCC_DEVTRACE only; the shipped one returns RPCC_ERR_ARG for a non-NULL buffer):
  * register a device int64 buffer of at least RPCC_DEBUG_STAMPS_WORDS words; instrumented kernels store the shader clock at

@@ -40,7 +40,9 @@ FPS_FMA1, FPS_FMA2, FPS_TIE_CUDA = 2, 4, 8   # RPCC_FPS_FMA1 / RPCC_FPS_FMA2 / R
 MAX_CLUSTERS = 254     # RPCC_MAX_CLUSTERS: labels 0 .. cluster_num + 1 are stored as uint8 on the device
 MAX_CLUSTERS_WIDE = 65533   # RPCC_MAX_CLUSTERS_WIDE: the uint16-label entries (rpcc_*_wide)
 MAX_CLUSTERS_MID = 1022     # RPCC_MAX_CLUSTERS_MID: the tuned kernels on uint16 labels; the uint16 STAGE entries (rpcc_assign_wide ...)
-ABI_VERSION = 104      # RPCC_ABI_VERSION: the layout of rpcc_batch_io / rpcc_geom this binding was written for
+STREAM_OK, STREAM_E_ENTROPY, STREAM_E_PLANE, STREAM_E_CONTOUR, STREAM_E_WIDTH = 0, 1, 2, 3, 4     # RPCC_STREAM_* (rpcc_decompress_batch)
+STREAM_E_NSEQ, STREAM_E_LABEL, STREAM_E_SALIENCE, STREAM_E_RESIDUAL, STREAM_E_CONTAINER = 5, 6, 7, 8, 9
+ABI_VERSION = 105      # RPCC_ABI_VERSION: the layout of rpcc_batch_io / rpcc_geom this binding was written for
 
 
 def fps_mode_flags(fma=0, cuda_tie=False):
@@ -105,6 +107,9 @@ _SIGS = {
     "rpcc_contour_encode_wide": (C.c_int, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "rpcc_contour_decode_wide": (C.c_int, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
     "rpcc_decode_wide": (C.c_int, [_VP, _VP, _VP, _VP, C.POINTER(C.c_double), _I, _VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "rpcc_decompress_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "rpcc_decompress_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_double), _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rpcc_decompress_batch_wide": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_double), _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rpcc_debug_stamps": (C.c_int, [_VP]),
     "rpcc_timer_create": (_VP, []),
     "rpcc_timer_destroy": (None, [_VP]),

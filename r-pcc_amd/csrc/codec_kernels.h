@@ -37,11 +37,8 @@ __global__ __launch_bounds__(256) void contour_count_kernel(const L *__restrict_
     if (threadIdx.x == 0) tile_cnt[(int64_t)b * T + t] = (uint32_t)(s[0] + s[1] + s[2] + s[3]);
 }
 
-// exclusive scan of the per-tile counts of one frame (T <= 4096 handled in chunks of 256), total -> nseq
-__global__ __launch_bounds__(256) void tile_scan_kernel(uint32_t *__restrict__ tile_cnt, int T, int32_t *__restrict__ total) {
-    __shared__ uint32_t sh[256];
-    const int b = blockIdx.x;
-    uint32_t *c = tile_cnt + (int64_t)b * T;
+// exclusive scan of the per-tile counts of one frame (T <= 4096 handled in chunks of 256) -> the frame's total, in every thread
+__device__ __forceinline__ uint32_t tile_scan_body(uint32_t *__restrict__ c, int T, uint32_t *sh) {
     uint32_t run = 0;
     for (int base = 0; base < T; base += 256) {
         const int i = base + threadIdx.x;
@@ -58,6 +55,13 @@ __global__ __launch_bounds__(256) void tile_scan_kernel(uint32_t *__restrict__ t
         run += sh[255];
         __syncthreads();
     }
+    return run;
+}
+// ... of every frame of a batch, total -> nseq
+__global__ __launch_bounds__(256) void tile_scan_kernel(uint32_t *__restrict__ tile_cnt, int T, int32_t *__restrict__ total) {
+    __shared__ uint32_t sh[256];
+    const int b = blockIdx.x;
+    const uint32_t run = tile_scan_body(tile_cnt + (int64_t)b * T, T, sh);
     if (threadIdx.x == 0 && total) total[b] = (int32_t)run;
 }
 
@@ -104,6 +108,93 @@ __global__ __launch_bounds__(256) void contour_write_kernel(const L *__restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// f3, batched streams (rpcc_decompress_batch): the checks tools/decompress.py:decode_frame makes on the host before it lets the kernels index
+// with a stream's contents, as a status per frame (RPCC_STREAM_*, rpcc_hip.h: the first check that fails, in decode_frame's order).
+// Checks 1..4 follow from the lengths and the entropy statuses alone (stream_length_status: every workgroup evaluates them for itself);
+// a frame that fails one is not read at all.  stream_check_kernel: per frame x tile, the popcount of the tile's contour bits (the pad bits of
+// the last byte do not count) -- the tile counts recover_map scans --, the largest idx entry of the tile's share of the stream's
+// entries and (tile 0) the largest salience level.  stream_status_kernel: per frame, the scan of the tile counts, whose total is the
+// popcount, and the status of checks 1..7.  Check 8 needs the label map: decode_body<true>.
+// Nothing past a payload's stated length is read.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int stream_length_status(const int64_t *__restrict__ len, const int32_t *__restrict__ est, bool nonuniform, int P, int K) {
+    for (int c = nonuniform ? 0 : 1; c < 5; c++)
+        if (est[c] != 0) return RPCC_STREAM_E_ENTROPY;
+    const int64_t plane = len[3];
+    if (plane < 0 || (plane & 15) != 0 || (plane >> 4) > K) return RPCC_STREAM_E_PLANE;
+    if (len[1] != (int64_t)((P + 7) >> 3)) return RPCC_STREAM_E_CONTOUR;
+    if (len[2] < 0 || (len[2] & 1) != 0 || len[4] < 0 || (len[4] & 1) != 0) return RPCC_STREAM_E_WIDTH;
+    return RPCC_STREAM_OK;
+}
+__global__ __launch_bounds__(256) void stream_check_kernel(const uint8_t *__restrict__ bits, const uint16_t *__restrict__ seq,
+                                                           const uint8_t *__restrict__ salience, const int64_t *__restrict__ payload_len,
+                                                           const int32_t *__restrict__ entropy_status, int nonuniform, int P, int K, int T,
+                                                           uint32_t *__restrict__ tile_cnt, uint32_t *__restrict__ tile_max,
+                                                           uint32_t *__restrict__ sal_max) {
+    __shared__ uint32_t s[3][4];
+    const int b = blockIdx.y, t = blockIdx.x;
+    const int64_t *len = payload_len + 5 * (int64_t)b;
+    const bool sound = stream_length_status(len, entropy_status + 5 * (int64_t)b, nonuniform != 0, P, K) == RPCC_STREAM_OK;
+    uint32_t cnt = 0u, imax = 0u, smax = 0u;
+    if (sound) {
+        const int nbytes = (P + 7) >> 3;
+        // a tile = 1024 pixels = 128 bytes; threads 0..127 take one byte each
+        const int byte_idx = t * (TILE / 8) + threadIdx.x;
+        if (threadIdx.x < TILE / 8 && byte_idx < nbytes) {
+            uint32_t v = bits[(int64_t)b * nbytes + byte_idx];
+            const int valid = P - byte_idx * 8;  // pixels of this byte inside the image
+            if (valid < 8) v &= 0xFFu << (8 - valid);
+            cnt = (uint32_t)__popc(v);
+        }
+        const int nidx = (int)min(len[2] >> 1, (int64_t)P);   // (more entries than pixels: refused by the count, whatever they hold)
+#pragma unroll
+        for (int j = 0; j < TILE / 256; j++) {
+            const int p = t * TILE + j * 256 + threadIdx.x;
+            if (p < nidx) imax = max(imax, (uint32_t)seq[(int64_t)b * P + p]);
+        }
+        if (nonuniform && t == 0) {
+            const int nsal = (int)min(max(len[0], (int64_t)0), (int64_t)K);
+            for (int i = threadIdx.x; i < nsal; i += 256) smax = max(smax, (uint32_t)salience[(int64_t)b * K + i]);
+        }
+    }
+    cnt = dpp_sum_u32(cnt);
+    imax = dpp_max_u32(imax);
+    smax = dpp_max_u32(smax);
+    if ((threadIdx.x & 63) == 0) { s[0][threadIdx.x >> 6] = cnt; s[1][threadIdx.x >> 6] = imax; s[2][threadIdx.x >> 6] = smax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        tile_cnt[(int64_t)b * T + t] = s[0][0] + s[0][1] + s[0][2] + s[0][3];
+        tile_max[(int64_t)b * T + t] = max(max(s[1][0], s[1][1]), max(s[1][2], s[1][3]));
+        if (t == 0) sal_max[b] = max(max(s[2][0], s[2][1]), max(s[2][2], s[2][3]));
+    }
+}
+__global__ __launch_bounds__(256) void stream_status_kernel(uint32_t *__restrict__ tile_cnt, const uint32_t *__restrict__ tile_max,
+                                                            const uint32_t *__restrict__ sal_max, const int64_t *__restrict__ payload_len,
+                                                            const int32_t *__restrict__ entropy_status, int levels, int P, int K, int T,
+                                                            int32_t *__restrict__ pre_status) {
+    __shared__ uint32_t sh[256];
+    __shared__ uint32_t smx[4];
+    const int b = blockIdx.x;
+    const uint32_t nbits = tile_scan_body(tile_cnt + (int64_t)b * T, T, sh);
+    uint32_t imax = 0u;
+    for (int i = threadIdx.x; i < T; i += 256) imax = max(imax, tile_max[(int64_t)b * T + i]);
+    imax = dpp_max_u32(imax);
+    if ((threadIdx.x & 63) == 0) smx[threadIdx.x >> 6] = imax;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    imax = max(max(smx[0], smx[1]), max(smx[2], smx[3]));
+    const int64_t *len = payload_len + 5 * (int64_t)b;
+    int st = stream_length_status(len, entropy_status + 5 * (int64_t)b, levels != 0, P, K);
+    if (st == RPCC_STREAM_OK) {
+        const int64_t nidx = len[2] >> 1, rows = len[3] >> 4;
+        if (nidx != (int64_t)nbits) st = RPCC_STREAM_E_NSEQ;
+        else if (nidx > 0 && (int64_t)imax >= rows) st = RPCC_STREAM_E_LABEL;
+        else if (levels != 0 && (len[0] > K || len[0] < rows || (len[0] > 0 && (int)sal_max[b] >= levels))) st = RPCC_STREAM_E_SALIENCE;
+    }
+    pre_status[b] = st;
+}
+
 // f3: recover_map.  Label of pixel p = seq[(number of contour bits at positions <= p) - 1].
 __global__ __launch_bounds__(256) void contour_bits_count_kernel(const uint8_t *__restrict__ bits, int P, int T,
                                                                  uint32_t *__restrict__ tile_cnt) {
@@ -128,12 +219,23 @@ __global__ __launch_bounds__(256) void contour_bits_count_kernel(const uint8_t *
     if (threadIdx.x == 0) tile_cnt[(int64_t)b * T + t] = (uint32_t)(s[0] + s[1] + s[2] + s[3]);
 }
 
-template <class L>
-__global__ __launch_bounds__(256) void recover_map_kernel(const uint8_t *__restrict__ bits, const uint16_t *__restrict__ seq,
-                                                          int P, int T, const uint32_t *__restrict__ tile_off,
-                                                          L *__restrict__ seg) {
+// GATED (rpcc_decompress_batch): gate[b] != 0 -- a frame the stream check refused: its workgroups read nothing and write the zeros themselves.
+template <class L, bool GATED>
+__device__ __forceinline__ void recover_map_body(const uint8_t *__restrict__ bits, const uint16_t *__restrict__ seq,
+                                                 int P, int T, const uint32_t *__restrict__ tile_off, const int32_t *__restrict__ gate,
+                                                 L *__restrict__ seg) {
     __shared__ uint32_t segcnt[16];
     const int b = blockIdx.y, t = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if constexpr (GATED) {
+        if (gate[b] != 0) {   // (the same for the whole workgroup)
+#pragma unroll
+            for (int j = 0; j < TILE / 256; j++) {
+                const int p = t * TILE + j * 256 + threadIdx.x;
+                if (p < P) seg[(int64_t)b * P + p] = (L)0;
+            }
+            return;
+        }
+    }
     const int nbytes = (P + 7) >> 3;
     const uint8_t *ib = bits + (int64_t)b * nbytes;
     const uint16_t *is = seq + (int64_t)b * P;
@@ -163,6 +265,18 @@ __global__ __launch_bounds__(256) void recover_map_kernel(const uint8_t *__restr
         }
     }
 }
+template <class L>
+__global__ __launch_bounds__(256) void recover_map_kernel(const uint8_t *__restrict__ bits, const uint16_t *__restrict__ seq,
+                                                          int P, int T, const uint32_t *__restrict__ tile_off,
+                                                          L *__restrict__ seg) {
+    recover_map_body<L, false>(bits, seq, P, T, tile_off, nullptr, seg);
+}
+template <class L>
+__global__ __launch_bounds__(256) void recover_map_gated_kernel(const uint8_t *__restrict__ bits, const uint16_t *__restrict__ seq,
+                                                                int P, int T, const uint32_t *__restrict__ tile_off,
+                                                                const int32_t *__restrict__ gate, L *__restrict__ seg) {
+    recover_map_body<L, true>(bits, seq, P, T, tile_off, gate, seg);
+}
 
 // ------------------------------------------------------------------------------------------------
 // f3: decoder body.  For every pixel: pred (intra_pred), residual = dequant of the integer read from the
@@ -170,61 +284,37 @@ __global__ __launch_bounds__(256) void recover_map_kernel(const uint8_t *__restr
 // rec = pred + residual (fp32), optional point cloud rec * tm.
 // steps (DecodeSteps, ref_rules.h): one double (uniform) or per-label through salience (non-uniform).
 // ------------------------------------------------------------------------------------------------
+// Gated form (rpcc_decompress_batch, StreamGate below; the body of both kernels: decode_tile.inc): the frame's status is settled here -- the stream check's, or E_RESIDUAL when the stream's
+// residual count is not the label map's -- and a refused frame's workgroups read nothing and write the zeros themselves, the label map's included.
+// Rows of `model` / entries of `salience` past the stream's own count are read as zero (they may hold anything).
+struct StreamGate {
+    const int32_t *pre;        // [B] status after the stream check (checks 1..7)
+    const int32_t *nnz;        // [B] pixels whose recovered label is not 1
+    const int64_t *payload_len;// [B,5]
+    int32_t *status;           // [B] out
+    void *seg_w;               // the label map, to zero a frame refused here
+};
+__device__ __forceinline__ int stream_final_status(const StreamGate &g, int b) {
+    const int pre = g.pre[b];
+    return pre ? pre : ((g.payload_len[5 * (int64_t)b + 4] >> 1) != (int64_t)g.nnz[b] ? RPCC_STREAM_E_RESIDUAL : RPCC_STREAM_OK);
+}
 __global__ __launch_bounds__(256) void decode_kernel(const uint8_t *__restrict__ seg, const int16_t *__restrict__ q16,
                                                      const float *__restrict__ model, const float *__restrict__ tm,
                                                      const uint32_t *__restrict__ hist, const uint8_t *__restrict__ salience,
                                                      DecodeSteps steps, int P, int M, int KP, int T,
                                                      float *__restrict__ ri_rec, float *__restrict__ pc_rec) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float *smodel = reinterpret_cast<float *>(smem_raw);                 // [KP*4]
-    uint32_t *segcnt = reinterpret_cast<uint32_t *>(smodel + 4 * KP);    // [16][KP+1]
-    const int SEGP = KP + 1;
-    uint32_t *soff = segcnt + 16 * SEGP;                                 // [KP] this tile's input offsets per label
-    const int b = blockIdx.y, t = blockIdx.x, K = M + 2;
-    // per-frame bases (wave-uniform) + byte offsets; all loads of the tile are issued first (unconditional, clamped)
-    seg += (int64_t)b * P;
-    q16 += (int64_t)b * P;
-    ri_rec += (int64_t)b * P;
-    if (pc_rec) pc_rec += (int64_t)b * P * 3;
-    int lab[4], rank[4], lraw[4];
-    f32x3 ray[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const uint32_t p = (uint32_t)min(t * TILE + j * 256 + (int)threadIdx.x, P - 1);
-        lraw[j] = ld_at(seg, p);
-        ray[j] = ld_at(reinterpret_cast<const f32x3 *>(tm), p * 12u);
-    }
-    for (int i = threadIdx.x; i < 4 * K; i += 256) smodel[i] = model[(int64_t)b * K * 4 + i];
-    for (int i = threadIdx.x; i < K; i += 256) soff[i] = hist[((int64_t)b * T + t) * KP + i];
-    for (int i = threadIdx.x; i < 16 * SEGP; i += 256) segcnt[i] = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int p = t * TILE + j * 256 + threadIdx.x;
-        lab[j] = (p < P && lraw[j] != 1) ? lraw[j] : -1;
-        rank[j] = segment_rank(j, lab[j], segcnt, SEGP);
-    }
-    segment_offsets(segcnt, SEGP, soff, K);
-    int16_t qv[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++)  // gather of the label-ordered integers (clamped: unused for label 1 / outside)
-        qv[j] = ld_at(q16, (lab[j] >= 0 ? segment_slot(j, lab[j], rank[j], segcnt, SEGP) : 0u) * 2u);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int p = t * TILE + j * 256 + threadIdx.x;
-        if (p >= P) continue;
-        const int l = lraw[j];
-        const float pr = intra_pred(smodel[4 * l], smodel[4 * l + 1], smodel[4 * l + 2], smodel[4 * l + 3], ray[j].x, ray[j].y, ray[j].z);
-        float res = 0.0f;  // label 1 keeps the zero of np.zeros_like (compress_utils.py:115)
-        if (lab[j] >= 0) res = dequant(qv[j], dequant_step(steps, salience, (int64_t)b * K + l));
-        const float rec = pr + res;          // tools/decompress.py:104
-        st_at(ri_rec, (uint32_t)p * 4u, rec);
-        if (pc_rec) {
-            f32x3 o;
-            o.x = rec * ray[j].x; o.y = rec * ray[j].y; o.z = rec * ray[j].z;
-            st_at(reinterpret_cast<f32x3 *>(pc_rec), (uint32_t)p * 12u, o);
-        }
-    }
+#define DECODE_GATED 0
+#include "decode_tile.inc"
+#undef DECODE_GATED
+}
+__global__ __launch_bounds__(256) void decode_gated_kernel(const uint8_t *__restrict__ seg, const int16_t *__restrict__ q16,
+                                                           const float *__restrict__ model, const float *__restrict__ tm,
+                                                           const uint32_t *__restrict__ hist, const uint8_t *__restrict__ salience,
+                                                           DecodeSteps steps, int P, int M, int KP, int T,
+                                                           float *__restrict__ ri_rec, float *__restrict__ pc_rec, StreamGate gate) {
+#define DECODE_GATED 1
+#include "decode_tile.inc"
+#undef DECODE_GATED
 }
 // its LDS: smodel f32 [KP*4] | the segments'
 static inline size_t decode_lds_bytes(int KP) { return (size_t)KP * 4 * 4 + segment_lds_bytes(KP); }

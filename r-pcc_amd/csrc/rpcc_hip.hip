@@ -4061,3 +4061,77 @@ extern "C" int rpcc_decode_wide(const uint16_t *seg, const int16_t *q16, const f
     LAUNCH_CHECK();
     return RPCC_OK;
 }
+
+// ================================================================================================
+// f3 for a batch of streams: rpcc_decompress_batch  (stream_check_kernel, stream_status_kernel, the gated kernels: codec_kernels.h)
+// ================================================================================================
+// ws: [ pre-status i32 [B] | nnz i32 [B] | largest salience level u32 [B] | tile counts u32 [B,T] | tile idx maxima u32 [B,T] | the decoder's part ],
+// the decoder's part being rpcc_decode's model part (byte labels) or rpcc_decode_wide's whole layout (uint16 labels).
+struct DecompressLayout { int32_t *pre, *nnz; uint32_t *sal_max, *tile_cnt, *tile_max; char *dec; size_t bytes; };
+static DecompressLayout decompress_layout(void *ws, int B, int P, int M, bool wide) {
+    const size_t T = (size_t)ntiles(P);
+    Carve c(ws);
+    DecompressLayout l;
+    l.pre = c.take<int32_t>((size_t)B * 4); l.nnz = c.take<int32_t>((size_t)B * 4); l.sal_max = c.take<uint32_t>((size_t)B * 4);
+    l.tile_cnt = c.take<uint32_t>((size_t)B * T * 4); l.tile_max = c.take<uint32_t>((size_t)B * T * 4);
+    l.dec = c.take(wide ? wide_layout(nullptr, B, P, M, 0).bytes : ws_layout(nullptr, B, P, M).bytes);
+    l.bytes = c.bytes();
+    return l;
+}
+extern "C" size_t rpcc_decompress_workspace_bytes(int B, int P, int M) {
+    if (B <= 0 || P <= 0 || M <= 0 || M > RPCC_MAX_CLUSTERS_WIDE) return 0;
+    return decompress_layout(nullptr, B, P, M, M > RPCC_MAX_CLUSTERS).bytes;
+}
+
+template <class L>
+static int decompress_entry(const uint8_t *contour_bits, const uint16_t *idx_sequence, const float *model, const int16_t *q16, const uint8_t *salience,
+                            const int64_t *payload_len, const int32_t *entropy_status, const float *tm, const double *level_acc, int levels,
+                            int B, int H, int W, int M, int32_t *status, L *seg, float *ri_rec, float *pc_rec, void *ws, void *stream) {
+    constexpr bool wide = sizeof(L) == 2;
+    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && (int64_t)H * W <= 0x7FFFFFFF / 16);
+    ARG_TRY(wide ? (M > RPCC_MAX_CLUSTERS && M <= RPCC_MAX_CLUSTERS_WIDE) : (M > 0 && M <= RPCC_MAX_CLUSTERS));
+    ARG_TRY(contour_bits && idx_sequence && model && q16 && payload_len && entropy_status && tm && level_acc && status && seg && ri_rec && ws);
+    ARG_TRY(levels >= 0 && levels <= 8 && (levels == 0 || salience != nullptr));
+    hipStream_t st = (hipStream_t)stream;
+    const int P = H * W, T = ntiles(P), K = M + 2;
+    const DecompressLayout l = decompress_layout(ws, B, P, M, wide);
+    stream_check_kernel<<<dim3(T, B), 256, 0, st>>>(contour_bits, idx_sequence, salience, payload_len, entropy_status, levels != 0, P, K, T,
+                                                    l.tile_cnt, l.tile_max, l.sal_max);
+    stream_status_kernel<<<B, 256, 0, st>>>(l.tile_cnt, l.tile_max, l.sal_max, payload_len, entropy_status, levels, P, K, T, l.pre);
+    recover_map_gated_kernel<L><<<dim3(T, B), 256, 0, st>>>(contour_bits, idx_sequence, P, T, l.tile_cnt, l.pre, seg);
+    LAUNCH_CHECK();
+    DecodeSteps steps;
+    steps.levels = levels;
+    for (int i = 0; i < 8; i++) steps.acc[i] = i < (levels ? levels : 1) ? level_acc[i] : 0.0;
+    const StreamGate gate = {l.pre, l.nnz, payload_len, status, seg};
+    int rc;
+    if constexpr (wide) {
+        const WideWs w = wide_layout(l.dec, B, P, M, 0);
+        // (the per-label counts land in the workspace's key-point counters, as in rpcc_decode_wide)
+        if ((rc = wide_order<uint16_t>(seg, nullptr, nullptr, nullptr, B, P, M, w, w.kpn, l.nnz, false, st))) return rc;
+        wide_decode_gated_kernel<uint16_t><<<dim3((P + 255) / 256, B), 256, 0, st>>>(seg, q16, model, tm, w.pos, salience, steps, P, K, ri_rec, pc_rec, gate);
+    } else {
+        const int KP = kpad(M);
+        const WsLayout wl = ws_layout(l.dec, B, P, M);
+        HIP_TRY(hipMemsetAsync(wl.sums, 0, (size_t)((char *)wl.hist - (char *)wl.sums), st));
+        // the label histogram the decoder consumes also counts the pixels whose label is not 1 (check 8)
+        if ((rc = launch_hist_scan(nullptr, seg, nullptr, B, P, M, wl, nullptr, nullptr, l.nnz, st))) return rc;
+        decode_gated_kernel<<<dim3(T, B), 256, decode_lds_bytes(KP), st>>>(seg, q16, model, tm, wl.hist, salience, steps, P, M, KP, T, ri_rec, pc_rec, gate);
+    }
+    LAUNCH_CHECK();
+    return RPCC_OK;
+}
+extern "C" int rpcc_decompress_batch(const uint8_t *contour_bits, const uint16_t *idx_sequence, const float *model, const int16_t *q16,
+                                     const uint8_t *salience, const int64_t *payload_len, const int32_t *entropy_status, const float *tm,
+                                     const double *level_acc, int levels, int B, int H, int W, int M, int32_t *status, uint8_t *seg, float *ri_rec,
+                                     float *pc_rec, void *ws, void *stream) {
+    return decompress_entry(contour_bits, idx_sequence, model, q16, salience, payload_len, entropy_status, tm, level_acc, levels, B, H, W, M, status, seg,
+                            ri_rec, pc_rec, ws, stream);
+}
+extern "C" int rpcc_decompress_batch_wide(const uint8_t *contour_bits, const uint16_t *idx_sequence, const float *model, const int16_t *q16,
+                                          const uint8_t *salience, const int64_t *payload_len, const int32_t *entropy_status, const float *tm,
+                                          const double *level_acc, int levels, int B, int H, int W, int M, int32_t *status, uint16_t *seg, float *ri_rec,
+                                          float *pc_rec, void *ws, void *stream) {
+    return decompress_entry(contour_bits, idx_sequence, model, q16, salience, payload_len, entropy_status, tm, level_acc, levels, B, H, W, M, status, seg,
+                            ri_rec, pc_rec, ws, stream);
+}

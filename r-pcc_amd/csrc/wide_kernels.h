@@ -203,25 +203,58 @@ __global__ __launch_bounds__(256) void wide_quantise_kernel(const float *__restr
     const float res = ri[g] - intra_pred(m[0], m[1], m[2], m[3], tm[3 * p], tm[3 * p + 1], tm[3 * p + 2]);
     q16[(int64_t)b * P + o] = (int16_t)quantise(res, label_acc ? label_acc[(int64_t)b * K + l] : acc);   // astype(np.int16): two's-complement truncation
 }
-// f3: the decoder's body on the positions (decode_kernel for any K)
-template <class L>
-__global__ __launch_bounds__(256) void wide_decode_kernel(const L *__restrict__ seg, const int16_t *__restrict__ q16, const float *__restrict__ model,
-                                                          const float *__restrict__ tm, const int32_t *__restrict__ pos, const uint8_t *__restrict__ salience,
-                                                          DecodeSteps steps, int P, int K, float *__restrict__ ri_rec, float *__restrict__ pc_rec) {
+// f3: the decoder's body on the positions (decode_kernel for any K).  GATED: as decode_body<true> (codec_kernels.h) -- the frame's final status,
+// zeros for a refused frame, model rows / salience entries past the stream's own count read as zero.
+template <class L, bool GATED>
+__device__ __forceinline__ void wide_decode_body(const L *__restrict__ seg, const int16_t *__restrict__ q16, const float *__restrict__ model,
+                                                 const float *__restrict__ tm, const int32_t *__restrict__ pos, const uint8_t *__restrict__ salience,
+                                                 const DecodeSteps &steps, int P, int K, float *__restrict__ ri_rec, float *__restrict__ pc_rec,
+                                                 const StreamGate &gate) {
     const int b = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+    int nrow = K, nsal = K;
+    if constexpr (GATED) {
+        const int st = stream_final_status(gate, b);
+        if (p == 0) gate.status[b] = st;
+        if (st != RPCC_STREAM_OK) {
+            if (p < P) {
+                const int64_t g = (int64_t)b * P + p;
+                static_cast<L *>(gate.seg_w)[g] = (L)0;
+                ri_rec[g] = 0.0f;
+                if (pc_rec) { pc_rec[3 * g] = 0.0f; pc_rec[3 * g + 1] = 0.0f; pc_rec[3 * g + 2] = 0.0f; }
+            }
+            return;
+        }
+        nrow = (int)(gate.payload_len[5 * (int64_t)b + 3] >> 4);
+        nsal = (int)gate.payload_len[5 * (int64_t)b];
+    }
     if (p >= P) return;
     const int64_t g = (int64_t)b * P + p;
     const int l = min((int)seg[g], K - 1), o = pos[g];   // (wide_keys_kernel: labels above K - 1 count as K - 1)
     const float *m = model + ((int64_t)b * K + l) * 4;
-    const float p0 = m[0], p1 = m[1], p2 = m[2], p3 = m[3];
+    float p0, p1, p2, p3;
+    if (GATED && l >= nrow) { p0 = 0.0f; p1 = 0.0f; p2 = 0.0f; p3 = 0.0f; }
+    else { p0 = m[0]; p1 = m[1]; p2 = m[2]; p3 = m[3]; }
     const float tx = tm[3 * p], ty = tm[3 * p + 1], tz = tm[3 * p + 2];
     const float pr = intra_pred(p0, p1, p2, p3, tx, ty, tz);
     float res = 0.0f;
     if (o >= 0) {
-        const double st = dequant_step(steps, salience, (int64_t)b * K + l);
+        const double st = (GATED && steps.levels && l >= nsal) ? steps.acc[0] : dequant_step(steps, salience, (int64_t)b * K + l);
         res = dequant(q16[(int64_t)b * P + o], st);
     }
     const float rec = pr + res;
     ri_rec[g] = rec;
     if (pc_rec) { pc_rec[3 * g] = rec * tx; pc_rec[3 * g + 1] = rec * ty; pc_rec[3 * g + 2] = rec * tz; }
+}
+template <class L>
+__global__ __launch_bounds__(256) void wide_decode_kernel(const L *__restrict__ seg, const int16_t *__restrict__ q16, const float *__restrict__ model,
+                                                          const float *__restrict__ tm, const int32_t *__restrict__ pos, const uint8_t *__restrict__ salience,
+                                                          DecodeSteps steps, int P, int K, float *__restrict__ ri_rec, float *__restrict__ pc_rec) {
+    wide_decode_body<L, false>(seg, q16, model, tm, pos, salience, steps, P, K, ri_rec, pc_rec, StreamGate{});
+}
+template <class L>
+__global__ __launch_bounds__(256) void wide_decode_gated_kernel(const L *__restrict__ seg, const int16_t *__restrict__ q16, const float *__restrict__ model,
+                                                                const float *__restrict__ tm, const int32_t *__restrict__ pos,
+                                                                const uint8_t *__restrict__ salience, DecodeSteps steps, int P, int K,
+                                                                float *__restrict__ ri_rec, float *__restrict__ pc_rec, StreamGate gate) {
+    wide_decode_body<L, true>(seg, q16, model, tm, pos, salience, steps, P, K, ri_rec, pc_rec, gate);
 }

@@ -3,7 +3,7 @@
 dumps / loads are python-lz4 0.7.0's names and forms: a uint32 little-endian uncompressed size, then one raw LZ4 block; the
 blocks are valid LZ4, so liblz4 or the reference's lz4.loads reads them, and loads reads any LZ4 block.  compress_utils takes
 this module where the lz4 package is not installed.  dumps_many / loads_many code a list with one copy to the device, one
-launch and one copy back; encode_descriptors / pack_containers are the device forms the batch pipeline uses."""
+launch and one copy back; encode_descriptors / pack_containers / decode_descriptors are the device forms the batch pipelines use."""
 import struct
 
 import numpy as np
@@ -105,6 +105,18 @@ def dumps_many(buffers, device=None):
         raise RuntimeError("rpcc_lz4_encode: a stream was refused (length out of range)")
     body = both[8 * n:]
     return [body[o: o + g].tobytes() for o, g in zip(off, got)]
+
+
+def decode_descriptors(addr, lens, dst, dst_off, dst_cap):
+    """Device form of loads over descriptors: stream s reads lens[s] bytes (dumps form) at the device address addr[s] and is written at
+    dst[dst_off[s]:], at most dst_cap[s] bytes (addr, lens, dst_off, dst_cap: i64 GPU tensors [n]; dst: u8 GPU tensor).  Enqueued on the
+    current stream, nothing waited for.  -> (dst_len i64 [n], status i32 [n]) GPU tensors."""
+    n = addr.numel()
+    dst_len = torch.empty(n, dtype=torch.int64, device=addr.device)
+    status = torch.empty(n, dtype=torch.int32, device=addr.device)
+    if n:
+        L.check(L.lib().rpcc_lz4_decode(ptr(addr), ptr(lens), n, ptr(dst), ptr(dst_off), ptr(dst_cap), ptr(dst_len), ptr(status), stream()))
+    return dst_len, status
 
 
 def decode_many(blobs, device=None):

@@ -311,6 +311,41 @@ def decode(seg, q16, model, tm, level_acc, salience=None, want_points=False, ws=
     return rec, pc
 
 
+def decompress_workspace(B, P, M, device):
+    """Work buffer of decompress_batch (rpcc_decompress_workspace_bytes; needs no initialisation)."""
+    return torch.empty(max(_lib.lib().rpcc_decompress_workspace_bytes(B, P, M), 1), dtype=torch.uint8, device=device)
+
+
+def decompress_batch(bits, seq, model, q16, payload_len, entropy_status, tm, level_acc, H, W, salience=None, want_points=True, ws=None, out=None):
+    """f3 for a batch of streams (rpcc_decompress_batch; cluster_num above 254: rpcc_decompress_batch_wide): the decoded payloads of B frames as the
+    entropy decoders left them -- bits u8 [B,ceil(P/8)], seq u16 [B,P], model f32 [B,K,4], q16 i16 [B,P], salience u8 [B,K] (non-uniform), every
+    row padded to the geometry's maximum and free to hold anything past payload_len i64 [B,5] (container order; entropy_status i32 [B,5] likewise) --
+    checked as tools/decompress.py:decode_frame checks them and decoded.  level_acc: float (uniform) or sequence (non-uniform, with salience).
+    out: (status, seg, ri_rec, pc_rec or None) to write into.  -> (status i32 [B]: 0 or _lib.STREAM_E_*, seg [B,H,W], ri_rec f32 [B,H,W],
+    pc_rec f32 [B,H,W,3] or None); a refused frame's rows are zero.  Nothing is waited for."""
+    B, P, M = bits.shape[0], H * W, model.shape[1] - 2
+    dev = _dev(bits)
+    wide = is_wide(M)
+    uniform = salience is None
+    assert bits.shape == (B, (P + 7) // 8) and bits.dtype == torch.uint8 and seq.numel() == B * P and seq.dtype == torch.uint16
+    assert q16.numel() == B * P and q16.dtype == torch.int16 and model.dtype == torch.float32 and model.shape == (B, M + 2, 4)
+    assert payload_len.shape == (B, 5) and payload_len.dtype == torch.int64 and entropy_status.shape == (B, 5) and entropy_status.dtype == torch.int32
+    assert uniform or (salience.shape == (B, M + 2) and salience.dtype == torch.uint8)
+    acc = [float(level_acc)] if uniform else [float(a) for a in level_acc]
+    arr = (C.c_double * len(acc))(*acc)
+    ws = decompress_workspace(B, P, M, dev) if ws is None else ws
+    if out is None:
+        out = (torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B, H, W), dtype=label_dtype(M), device=dev),
+               torch.empty((B, H, W), dtype=torch.float32, device=dev), torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_points else None)
+    status, seg, rec, pc = out
+    assert status.dtype == torch.int32 and status.numel() == B and seg.dtype == label_dtype(M) and seg.numel() == B * P
+    assert rec.dtype == torch.float32 and rec.numel() == B * P and (pc is None or (pc.dtype == torch.float32 and pc.numel() == 3 * B * P))
+    entry = _lib.lib().rpcc_decompress_batch_wide if wide else _lib.lib().rpcc_decompress_batch
+    check(entry(ptr(bits), ptr(seq), ptr(model), ptr(q16), ptr(salience), ptr(payload_len), ptr(entropy_status), ptr(tm), arr, 0 if uniform else len(acc),
+                B, H, W, M, ptr(status), ptr(seg), ptr(rec), ptr(pc), ptr(ws), stream()))
+    return status, seg, rec, pc
+
+
 def pack_payload(q16, nnz, packed=None, capacity=None, total=None):
     """f2: the batch's residual stream with the frames back to back (what the container / the payload gather holds):
     packed[:sum(nnz)] = concat_b q16[b][:nnz[b]].  `packed` (i16, >= capacity entries) and `total` (i64 [1]) are

@@ -1,12 +1,16 @@
 """Batched front-end: B frames of one lidar geometry through the fused HIP entry, then the host-side
 payload assembly (casts, container, entropy coder) of the reference's compress_point_cloud /
 save_compressed_bitstream.  This is the counterpart of the closure body of
-tools/compress_datalist.py:91-142 for a whole batch at once."""
+tools/compress_datalist.py:91-142 for a whole batch at once.  BatchDecompressor is the way back: a list of .rpcc containers through one
+entropy launch and one fused decode call per chunk."""
+import struct
+
 import numpy as np
 import torch
 
 from . import ops
-from .compress_utils import BasicCompressor, pack_bitstream, pack_frames  # noqa: F401
+from . import _lib
+from .compress_utils import _ORDER, BasicCompressor, pack_bitstream, pack_frames, unpack_bitstream  # noqa: F401
 
 
 class BatchCompressor:
@@ -236,3 +240,196 @@ class MixedBatchCompressor:
     def compress(self, frames, lidars):
         """frames: list of [N,3] arrays; lidars: the lidar name of every frame.  -> list of .rpcc byte strings."""
         return self.collect(self.submit(frames, lidars))
+
+
+STREAM_TEXT = {_lib.STREAM_E_ENTROPY: "an entropy stream was refused by the device decoder",
+               _lib.STREAM_E_PLANE: "plane_param payload is not a whole number of float32 [.,4] rows, or holds more than cluster_num + 2 rows",
+               _lib.STREAM_E_CONTOUR: "contour_map does not hold the bytes this range image needs (wrong --lidar?)",
+               _lib.STREAM_E_WIDTH: "idx_sequence / residual_quantized payloads are not 16-bit arrays",
+               _lib.STREAM_E_NSEQ: "idx_sequence does not hold one label per run the contour map marks",
+               _lib.STREAM_E_LABEL: "idx_sequence names a label without a stored model row",
+               _lib.STREAM_E_SALIENCE: "salience_level does not fit the model rows or the configured levels",
+               _lib.STREAM_E_RESIDUAL: "residual_quantized does not hold one value per non-empty pixel of the label map",
+               _lib.STREAM_E_CONTAINER: "the container's length prefixes do not fit its bytes"}
+
+
+def container_spans(blob, uniform=True):
+    """The (offset, length) of every payload of one .rpcc container by unpack_bitstream's rules (compress_utils), in container order; None for
+    a container they refuse: a prefix that is cut off or negative, or a payload longer than the bytes left."""
+    spans, off = [], 0
+    for _ in range(4 if uniform else 5):
+        if off + 4 > len(blob):
+            return None
+        (n,) = struct.unpack_from("i", blob, off)
+        if n < 0 or off + 4 + n > len(blob):
+            return None
+        spans.append((off + 4, n))
+        off += 4 + n
+    return spans
+
+
+class BatchDecompressor:
+    """The .rpcc containers of FPS streams (cluster_num fixed by the configuration) decoded a chunk at a time: the containers' length prefixes are
+    parsed on the host, the chunk's bytes go up in one copy, ONE launch of the back-end's device decoder writes every stream of the chunk
+    straight into the padded [B, ...] arrays rpcc_decompress_batch reads -- what a stream may decode to follows from the geometry alone -- and
+    one ops.decompress_batch checks and decodes the frames (status per frame: _lib.STREAM_E_*).  accuracy / level_acc / uniform are
+    tools/decompress.py:decode_frame's arguments, and its results are this class's, bit for bit.  The device decoders are used whatever the
+    device_entropy / device_bunzip2 flags of a BasicCompressor handed in say: those govern the per-frame path.
+    DBSCAN streams size their label count per frame: they stay on decode_frame."""
+
+    CHUNK_FRAMES = 32              # frames per chunk at most, as the datalist tool reads them
+    CHUNK_BUDGET_BYTES = 2 << 30   # device bytes one chunk may take: padded payloads, bzip2 work slots, work buffer and outputs
+
+    def __init__(self, transformer, cluster_num, accuracy, uniform=True, level_acc=None, basic_compressor="bzip2"):
+        if cluster_num is None:
+            raise ValueError("BatchDecompressor: cluster_num=None (a DBSCAN stream sizes its label count per frame): decode such streams with "
+                             "tools.decompress.decode_frame")
+        self.M = ops.check_cluster_num(cluster_num)
+        self.T, self.device = transformer, transformer.device
+        self.accuracy, self.uniform = accuracy, bool(uniform)
+        if not self.uniform and level_acc is None:
+            raise ValueError("BatchDecompressor: the non-uniform framework needs level_acc")
+        self.level_acc = None if level_acc is None else [float(a) for a in level_acc]
+        self.method = basic_compressor.method_name if isinstance(basic_compressor, BasicCompressor) else basic_compressor
+        assert self.method in BasicCompressor.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate)"
+        self.host_bc = BasicCompressor(method_name=self.method)   # the E_ENTROPY fallback: the host library's decoder
+        P, K = transformer.H * transformer.W, self.M + 2
+        self.ns = 4 if self.uniform else 5
+        # decoded bytes a stream can have, in container order (salience first when present): fixed by the geometry
+        self.caps = ([] if self.uniform else [K]) + [(P + 7) // 8, 2 * P, 16 * K, 2 * P]
+        self._work = {}
+        self.chunk = max(1, min(self.CHUNK_FRAMES, self.CHUNK_BUDGET_BYTES // self._frame_bytes()))
+
+    def _work_caps(self, levels):
+        """bzip2 work slot bytes of the streams of one frame (8-byte multiples) for the streams' levels; None for the other back-ends."""
+        if self.method != "bzip2":
+            return None
+        from . import bunzip2_codec
+        for key in zip(levels, self.caps):
+            if key not in self._work:
+                self._work[key] = (bunzip2_codec.work_bytes(bunzip2_codec.block_bound(*key)) + 7) // 8 * 8
+        return [self._work[key] for key in zip(levels, self.caps)]
+
+    def _frame_bytes(self):
+        """Device bytes a frame of a chunk takes at most (bzip2: every stream at level 9)."""
+        P = self.T.H * self.T.W
+        work = sum(self._work_caps([9] * self.ns) or [0])
+        outs = P * (2 if ops.is_wide(self.M) else 1) + 4 * P + 12 * P
+        ws = -(-_lib.lib().rpcc_decompress_workspace_bytes(self.CHUNK_FRAMES, P, self.M) // self.CHUNK_FRAMES)
+        return sum(self.caps) + 5 * 256 + work + outs + ws
+
+    def _chunk_device(self, blobs, out, data=None):
+        """One chunk: parse, upload, entropy launch, decode call on the current stream.  out: the chunk's rows of (status, seg, rec, pc).
+        data: (device u8 tensor, offsets) when the containers are on the device already (the tensor must stay alive until the stream has run)."""
+        from . import lz4_codec
+        B, ns, dev = len(blobs), self.ns, self.device
+        H, W, K = self.T.H, self.T.W, self.M + 2
+        P = H * W
+        spans = [container_spans(b, self.uniform) for b in blobs]
+        sound = [i for i, sp in enumerate(spans) if sp is not None]
+        n = ns * len(sound)
+        # the padded arrays, one allocation: [salience | contour bits | idx | model | residuals], every part 256-aligned
+        row = self.caps
+        part = np.zeros(ns + 1, np.int64)
+        part[1:] = np.cumsum([(B * r + 255) // 256 * 256 for r in row])
+        arrays = [lz4_codec._as_bytes(b) for b in blobs]
+        boff = np.zeros(B + 1, np.int64)
+        boff[1:] = np.cumsum([(a.size + 7) // 8 * 8 for a in arrays])
+        # descriptors [addr | lens | dst_off | dst_cap | work_off | work_cap | sound frames | refused frames] and the chunk's bytes: one pinned buffer
+        nmeta = 6 * n + B
+        host = torch.empty(8 * nmeta + (int(boff[-1]) if data is None else 0), dtype=torch.uint8, pin_memory=True)
+        up = torch.empty(host.numel(), dtype=torch.uint8, device=dev)
+        meta_h = host[: 8 * nmeta].numpy().view(np.int64)
+        base = up.data_ptr() + 8 * nmeta if data is None else data[0].data_ptr()
+        offs = boff if data is None else data[1]
+        if data is None:
+            body = host[8 * nmeta:].numpy()
+            for a, o in zip(arrays, boff[:-1]):
+                body[o: o + a.size] = a
+        sp = np.array([spans[i] for i in sound], np.int64).reshape(len(sound), ns, 2)
+        fr = np.array(sound, np.int64)
+        meta_h[0 * n: 1 * n] = (base + offs[fr][:, None] + sp[:, :, 0]).reshape(-1)
+        meta_h[1 * n: 2 * n] = sp[:, :, 1].reshape(-1)
+        meta_h[2 * n: 3 * n] = (part[None, :ns] + fr[:, None] * np.array(row, np.int64)[None, :]).reshape(-1)
+        meta_h[3 * n: 4 * n] = np.tile(np.array(row, np.int64), len(sound))
+        work = None
+        if self.method == "bzip2":
+            wcap = np.zeros((len(sound), ns), np.int64)
+            for j, i in enumerate(sound):   # the level byte of each stream ("BZh1" .. "BZh9"; anything else is refused by the decoder)
+                lv = [int(arrays[i][o + 3]) - 0x30 if l > 3 and 0x31 <= int(arrays[i][o + 3]) <= 0x39 else 1 for o, l in spans[i]]
+                wcap[j] = self._work_caps(lv)
+            woff = np.cumsum(wcap.reshape(-1)) - wcap.reshape(-1)
+            meta_h[4 * n: 5 * n], meta_h[5 * n: 6 * n] = woff, wcap.reshape(-1)
+            work = torch.empty(max(int(wcap.sum()), 8), dtype=torch.uint8, device=dev)
+        bad = np.array([i for i in range(B) if spans[i] is None], np.int64)
+        meta_h[6 * n: 6 * n + len(sound)], meta_h[6 * n + len(sound): 6 * n + B] = fr, bad
+        up.copy_(host, non_blocking=True)
+        meta = up[: 8 * nmeta].view(torch.int64)
+        d = [meta[k * n: (k + 1) * n] for k in range(6)]
+        dst = torch.empty(int(part[-1]), dtype=torch.uint8, device=dev)
+        if self.method == "lz4":
+            dst_len, est = lz4_codec.decode_descriptors(d[0], d[1], dst, d[2], d[3])
+        elif self.method == "bzip2":
+            from . import bunzip2_codec
+            dst_len, _, est = bunzip2_codec.decode_descriptors(d[0], d[1], dst, d[2], d[3], work, d[4], d[5])
+        else:
+            from . import inflate_codec
+            dst_len, est = inflate_codec.decode_descriptors(d[0], d[1], dst, d[2], d[3])
+        # [B,5] lengths / statuses in container order (uniform: no salience column); a frame whose container was refused: status 1, no length
+        plen = torch.zeros((B, 5), dtype=torch.int64, device=dev)
+        pest = torch.ones((B, 5), dtype=torch.int32, device=dev)
+        if len(sound) == B:
+            plen[:, 5 - ns:], pest[:, 5 - ns:] = dst_len.view(B, ns), est.view(B, ns)
+        elif sound:
+            idx = meta[6 * n: 6 * n + len(sound)]
+            plen[idx, 5 - ns:], pest[idx, 5 - ns:] = dst_len.view(-1, ns), est.view(-1, ns)
+        view = lambda c, dt, shape: dst[int(part[c]): int(part[c]) + B * row[c]].view(dt).view(shape)
+        c0 = ns - 4
+        sal = None if self.uniform else view(0, torch.uint8, (B, K))
+        ops.decompress_batch(view(c0, torch.uint8, (B, (P + 7) // 8)), view(c0 + 1, torch.uint16, (B, P)), view(c0 + 2, torch.float32, (B, K, 4)),
+                             view(c0 + 3, torch.int16, (B, P)), plen, pest, self.T.tm_dev, self.accuracy if self.uniform else self.level_acc,
+                             H, W, salience=sal, out=out)
+        if len(bad):
+            out[0][meta[6 * n + len(sound): 6 * n + B]] = _lib.STREAM_E_CONTAINER
+
+    def upload(self, blobs):
+        """The containers' bytes on the device, a chunk per copy, for decompress_device(blobs, uploaded=...): callers that hold the containers
+        in HBM already (the length prefixes are still read from the host copies)."""
+        from . import lz4_codec
+        with torch.cuda.device(self.device):
+            return [lz4_codec._upload([lz4_codec._as_bytes(b) for b in blobs[c0: c0 + self.chunk]], self.device) for c0 in range(0, len(blobs), self.chunk)]
+
+    def decompress_device(self, blobs, want_points=True, uploaded=None):
+        """blobs: .rpcc byte strings of one geometry and configuration (uploaded: what upload(blobs) returned, else they are copied up here).  -> (status i32 [B]: 0 or _lib.STREAM_E_*, seg [B,H,W], ri_rec f32 [B,H,W],
+        pc_rec f32 [B,H,W,3] or None) GPU tensors, queued on the current stream and not waited for; a refused frame's rows are zero."""
+        B, H, W, dev = len(blobs), self.T.H, self.T.W, self.device
+        out = (torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B, H, W), dtype=ops.label_dtype(self.M), device=dev),
+               torch.empty((B, H, W), dtype=torch.float32, device=dev), torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_points else None)
+        with torch.cuda.device(dev):
+            for c0 in range(0, B, self.chunk):
+                c1 = min(c0 + self.chunk, B)
+                self._chunk_device(blobs[c0: c1], tuple(None if o is None else o[c0: c1] for o in out), None if uploaded is None else uploaded[c0 // self.chunk])
+        return out
+
+    def decompress(self, blobs, want_points=True):
+        """-> [(rec f32 [H,W], pc f32 [H,W,3] or None, seg [H,W])] as tools/decompress.py:decode_frame returns them, a chunk's arrays in one
+        copy each.  A frame whose entropy streams the device decoder refuses (E_ENTROPY: bzip2 with trailing bytes or the randomised bit, a
+        second gzip member, the empty blob -- or a damaged stream) is decoded once more through decode_frame with the host library, which
+        raises for what it refuses too; any other refusal raises ValueError with the frame's index and the status text."""
+        from .tools.decompress import decode_frame
+        res = []
+        for c0 in range(0, len(blobs), self.chunk):
+            part = blobs[c0: c0 + self.chunk]
+            status, seg, rec, pc = (None if t is None else t.cpu().numpy() for t in self.decompress_device(part, want_points))
+            for i, st in enumerate(status):
+                if st == _lib.STREAM_OK:
+                    res.append((rec[i], pc[i] if pc is not None else None, seg[i]))
+                    continue
+                if st != _lib.STREAM_E_ENTROPY:
+                    raise ValueError("frame %d: %s (status %d)" % (c0 + i, STREAM_TEXT.get(int(st), "refused"), int(st)))
+                try:
+                    res.append(decode_frame(unpack_bitstream(part[i], self.uniform), self.host_bc, self.T, self.M, self.accuracy,
+                                            self.level_acc, self.uniform, want_points=want_points))
+                except (ValueError, OSError, EOFError) as e:
+                    raise ValueError("frame %d: %s" % (c0 + i, e)) from e
+        return res

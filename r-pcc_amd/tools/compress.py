@@ -39,6 +39,9 @@ def make_parser(datalist=False):
                        help="multi-GPU: every rank entropy-codes its shard, the .rpcc bytes are gathered to rank 0 (RCCL) in "
                             "datalist order and rank 0 writes all files (default: every rank writes its own files).")
         p.add_argument("--gather-round", dest="gather_round", type=int, default=4096, help="--gather: frames per rank and round.")
+        p.add_argument("--batch_decode", action="store_true",
+                       help="decompress_datalist.py: decode every chunk of files through pipeline.BatchDecompressor (one entropy launch and one "
+                            "fused decode call per chunk, FPS streams only); the output files are the same.")
     else:
         p.add_argument("--input", help="single frame input for static compression.")
         p.add_argument("--output", help="output bitstream.")

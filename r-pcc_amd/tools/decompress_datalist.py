@@ -21,6 +21,30 @@ from rpcc_amd.tools.decompress import decode_frame, stream_cluster_num  # noqa: 
 CHUNK = 32   # .rpcc files read and entropy-decoded together
 
 
+def output_path(args, name):
+    rel = name[1:] if name.startswith("/") else name
+    out = os.path.join(args.output_dir, rel)
+    return out.replace(out.split(".")[-1], "bin")
+
+
+def decompress_batched(args, dataset, mine, cluster_num, accuracy, level_acc, uniform, basic_compressor):
+    """--batch_decode: the chunks through pipeline.BatchDecompressor (the files' bytes as they are, one device pass per chunk)."""
+    from rpcc_amd.pipeline import BatchDecompressor
+    bd = BatchDecompressor(dataset.PCTransformer, cluster_num, accuracy, uniform=uniform, level_acc=level_acc, basic_compressor=basic_compressor)
+    for c0 in range(0, len(mine), CHUNK):
+        names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
+        blobs = []
+        for name in names:
+            with open(name, "rb") as f:
+                blobs.append(f.read())
+        for name, (rec, pc, _) in zip(names, bd.decompress(blobs)):
+            out = output_path(args, name)
+            os.makedirs(os.path.dirname(out), exist_ok=True)
+            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3))
+            if args.output:
+                print("%s -> %s (%d points)" % (name, out, int((rec != 0).sum())))
+
+
 def decompress(args):
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -29,6 +53,8 @@ def decompress(args):
     dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device)
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     mine = list(shard_indices(len(dataset), rank, world))
+    if getattr(args, "batch_decode", False):
+        return decompress_batched(args, dataset, mine, stream_cluster_num(segment_cfg), accuracy, level_acc, uniform, basic_compressor)
     for c0 in range(0, len(mine), CHUNK):
         names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
         cds = [read_compressed_bitstream(name, uniform=uniform) for name in names]

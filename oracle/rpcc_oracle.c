@@ -18,6 +18,7 @@
  * a4/a9 RANSAC is third-party Open3D in the reference (random, unpinned); orc_ransac_plane is the
  * build's own seeded definition, not a restatement.
  */
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -374,6 +375,14 @@ void orc_intra_predict(const int *seg, const float *mp, const float *tm, long P,
     }
 }
 
+/* a11 / a13: the conversion of cpp_modules.cpp:315,419, (int)roundf(res / step).  Where the rounded quotient is NaN or lies outside     */
+/* [-2^31, 2^31) the C expression is undefined; the reference's x86 binary gives cvttss2si's "integer indefinite", INT_MIN, and that */
+/* is the rule, stated here instead of left to the compiler (-2^31 itself converts to INT_MIN either way).                         */
+static int quantise(float res, float step) {
+    float r = roundf(res / step);
+    return fabsf(r) < 2147483648.0f ? (int)r : INT_MIN;
+}
+
 /* a11: uniform_quantize, cpp_modules.cpp:288-334.  roundf(res/acc), skip label 1, output grouped */
 /* by label ascending, row-major inside a label.  Returns nnz.                                   */
 long orc_uniform_quantize(const int *seg, const float *res, long P, float acc, int *out) {
@@ -386,7 +395,7 @@ long orc_uniform_quantize(const int *seg, const float *res, long P, float acc, i
     long total = cnt[cn];
     for (long i = 0; i < P; i++) {
         int s = seg[i];
-        if (s != 1) out[cnt[s]++] = (int)roundf(res[i] / acc);
+        if (s != 1) out[cnt[s]++] = quantise(res[i], acc);
     }
     free(cnt);
     return total;
@@ -420,7 +429,7 @@ long orc_nonuniform_quantize(const int *seg, const float *res, const int *kp, co
     long total = cnt[cn];
     for (long i = 0; i < P; i++) {
         int s = seg[i];
-        if (s != 1) out[cnt[s]++] = (int)roundf(res[i] / lacc[salience[s]]);
+        if (s != 1) out[cnt[s]++] = quantise(res[i], lacc[salience[s]]);
     }
     free(cnt); free(kpn); free(pn);
     return total;

@@ -63,7 +63,17 @@ __device__ __forceinline__ int salience_level(int k, int pixels, int keypoints, 
 
 // a11 / a13  quantisation of a residual (cpp_modules.cpp:315; step: the uniform accuracy or the label's, :404,419).  The caller
 // stores the integer as int16 (astype(np.int16): two's-complement truncation) or int32.
-__device__ __forceinline__ int quantise(float res, float step) { return (int)roundf(res / step); }
+// The conversion rule: a rounded quotient that is NaN or outside [-2^31, 2^31) gives INT_MIN -- what the reference's x86 binary returns
+// (cvttss2si's "integer indefinite"; int16: 0) for a C expression that is undefined there.  The device's own conversion saturates
+// (+overflow -> INT_MAX, int16 -1) and turns NaN into 0, so the rule is stated, not left to the instruction; NaN fails the comparison,
+// and -2^31 converts to INT_MIN either way.  Reached by far returns sharing a cluster, by infinite or NaN predictions (a horizontal beam
+// against a horizontal plane row) and by a zero step: DESIGN.md section 3, tests/value_cases.py.
+// (NaN VALUES elsewhere -- predictions, reconstructions -- are held to the oracle by their places only; observed, not asserted: the 0 / 0 and
+// inf * 0 NaNs of tests/value_cases.py's scene B carry x86's default pattern 0xFFC00000 on gfx950 too.)
+__device__ __forceinline__ int quantise(float res, float step) {
+    const float r = roundf(res / step);
+    return fabsf(r) < 2147483648.0f ? (int)r : INT_MIN;
+}
 
 // f3  dequantize_residual (compress_utils.py:114-132).  The step: one double (uniform: levels == 0, salience is not read and may be NULL)
 // or that of the label's level salience[i]; the residual: int16 * python float -> float64 -> stored into a float32 array.

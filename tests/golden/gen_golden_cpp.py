@@ -32,8 +32,8 @@ g = z.get("geom")   # H, W, horizontal FOV, vertical max, vertical min
 fn = {"project": lambda: [ds.point_cloud_to_range_image_even(z["xyz"], int(g[0]), int(g[1]), float(g[2]), float(g[3]), float(g[4]))],
       "point_modeling": lambda: [sg.point_modeling(z["ri"].reshape(z["ri"].shape + (1,)), z["seg"])],
       "intra_predict": lambda: [sg.intra_predict(z["seg"], z["mp"], z["tm"])],
-      "uniform_quantize": lambda: [q.uniform_quantize(z["seg"], z["res"], 0.04)],
-      "nonuniform_quantize": lambda: list(q.nonuniform_quantize(z["seg"], z["res"], z["kp"], z["lk"], z["la"], 2)),
+      "uniform_quantize": lambda: [q.uniform_quantize(z["seg"], z["res"], float(z["acc"]) if "acc" in z else 0.04)],
+      "nonuniform_quantize": lambda: list(q.nonuniform_quantize(z["seg"], z["res"], z["kp"], z["lk"], z["la"], int(z["gl"]) if "gl" in z else 2)),
       "features": lambda: list(fe.extract_features_with_segment(z["ri"], z["seg"], *[int(v) for v in z["params"]])),
       "contour": lambda: list(ct.extract_contour(z["seg"])),
       "recover_map": lambda: [ct.recover_map(z["cm"], z["sq"])]}[sys.argv[4]]
@@ -88,6 +88,29 @@ def main():
         qn_o, s_o = orc.nonuniform_quantize(seg, res, kp, lk, la, 2)
         out["quantizers"] = {"in": ins(seg=seg, res=res, kp=kp), "q": T.sha(like(q_r, orc.uniform_quantize(seg, res, 0.04))),
                              "qn": T.sha(like(qn_r, qn_o)), "sal": T.sha(like(s_r, s_o))}
+
+        # the hostile values of tests/value_cases.py: Table A through both quantisers, scene B through the predictor and both quantisers
+        seg, res, kp = T._value_table_inputs()
+        lkv, lav = np.array(T.vc.LEVEL_KP_NUM), T.vc.LABEL_STEPS
+        qn_r, s_r = run_ref(tmp, "nonuniform_quantize", seg=seg, res=res, kp=kp, lk=lkv, la=lav, gl=np.array(T.vc.GROUND_LEVEL))
+        qn_o, s_o = orc.nonuniform_quantize(seg, res, kp, lkv, lav, T.vc.GROUND_LEVEL)
+        out["value_table"] = {"in": ins(seg=seg, res=res, kp=kp), "q": {}, "qn": T.sha(like(qn_r, qn_o)), "sal": T.sha(like(s_r, s_o))}
+        for step in T.vc.UNIFORM_STEPS:
+            q_r, = run_ref(tmp, "uniform_quantize", seg=seg, res=res, acc=np.array(float(step)))
+            out["value_table"]["q"][T._step_key(step)] = T.sha(like(q_r, orc.uniform_quantize(seg, res, float(step))))
+        out["scene_b"] = {}
+        for frame in (0, 1):
+            seg, mp, tm, ri, kp = T._scene_b_inputs(frame)
+            pr_r, = run_ref(tmp, "intra_predict", seg=seg, mp=mp, tm=tm)
+            pr_r = np.asarray(pr_r, np.float32).reshape(seg.shape + (1,))
+            with np.errstate(all="ignore"):
+                res = (ri - pr_r[..., 0]).astype(np.float32)
+            q_r, = run_ref(tmp, "uniform_quantize", seg=seg, res=res)
+            qn_r, s_r = run_ref(tmp, "nonuniform_quantize", seg=seg, res=res, kp=kp, lk=lk, la=la)
+            qn_o, s_o = orc.nonuniform_quantize(seg, res, kp, lk, la, 2)
+            out["scene_b"][str(frame)] = {"in": ins(seg=seg, mp=mp, tm=tm, ri=ri, kp=kp, res=T._nan_canon(res)), "pred": T.sha(T._nan_canon(pr_r)),
+                                          "q": T.sha(like(q_r, orc.uniform_quantize(seg, res, 0.04))), "qn": T.sha(like(qn_r, qn_o)),
+                                          "sal": T.sha(like(s_r, s_o))}
 
         # the cells compared are the ones the restatement writes (feat != 0; key points > 0), as the test selects them
         seg, ri = T._feature_inputs()

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import feature_cases as fc
+import value_cases as vc
 from oracle import oracle as orc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -147,6 +148,63 @@ def test_quantizers_match(man):
     check_inputs(rec, seg=seg, res=res, kp=kp)
     q_o = orc.uniform_quantize(seg, res, 0.04)
     assert sha(q_o) == rec["q"]
+    lk, la = QUANT_LEVELS
+    qn_o, s_o = orc.nonuniform_quantize(seg, res, kp, lk, la, 2)
+    assert sha(qn_o) == rec["qn"] and sha(s_o) == rec["sal"]
+
+
+def _nan_canon(a):
+    """NaNs with one bit pattern (the reference does not define theirs reproducibly: sign and payload are the compiler's and the chip's)."""
+    a = np.array(a, np.float32)
+    a[np.isnan(a)] = np.uint32(0x7FC00000).view(np.float32)
+    return a
+
+
+def _step_key(step):
+    return "%.9g" % float(step)
+
+
+def _value_table_inputs():
+    """Table A of tests/value_cases.py as the 2-D arrays the reference's quantisers take."""
+    seg, res, kp = vc.table_a_image(20)
+    return seg.reshape(1, -1).copy(), res.reshape(1, -1).copy(), kp.reshape(1, -1).copy()
+
+
+def test_quantizers_match_on_value_table(man):
+    """Ties, near ties, the int16 wrap, the int32 edge, infinite and NaN quotients, zero steps: the restatement's stated conversion rule
+    (INT_MIN for what C leaves undefined) is what the reference's x86 binary returns, for the uniform quantiser at both steps and for
+    the non-uniform one with the per-label steps 2^-5, 0.04, 1e-30 and 0."""
+    rec = man["value_table"]
+    seg, res, kp = _value_table_inputs()
+    check_inputs(rec, seg=seg, res=res, kp=kp)
+    for step in vc.UNIFORM_STEPS:
+        assert sha(orc.uniform_quantize(seg, res, float(step))) == rec["q"][_step_key(step)], step
+    qn_o, s_o = orc.nonuniform_quantize(seg, res, kp, np.array(vc.LEVEL_KP_NUM), vc.LABEL_STEPS, vc.GROUND_LEVEL)
+    assert sha(qn_o) == rec["qn"] and sha(s_o) == rec["sal"]
+    assert (qn_o == vc.INT_MIN).any() and np.array_equal(s_o, vc.label_levels(22))
+
+
+def _scene_b_inputs(frame):
+    """Scene B of tests/value_cases.py: labels, the model rows of one frame, the transform map with tz == 0 on row 15, the range image, a key-point map that
+    gives the labels all four salience levels."""
+    b = vc.scene_b()
+    return b["seg"], b["model"][frame], b["tm"], b["ri"], b["kp"]
+
+
+@pytest.mark.parametrize("frame", [0, 1])
+def test_predict_and_quantizers_match_on_scene_b(man, frame):
+    """Predictions of +inf, -inf and NaN (compared with the NaNs' bits made equal), the (a + b) + c branch, the row that cancels only in
+    unfused arithmetic, the prediction 3e38 -- and the quantisers on ri - pred."""
+    rec = man["scene_b"][str(frame)]
+    seg, mp, tm, ri, kp = _scene_b_inputs(frame)
+    check_inputs(rec, seg=seg, mp=mp, tm=tm, ri=ri, kp=kp)
+    pr_o = orc.intra_predict(seg, mp, tm)
+    assert sha(_nan_canon(pr_o)) == rec["pred"]
+    assert np.isinf(pr_o).any() and (frame == 0 or np.isnan(pr_o).any())
+    with np.errstate(all="ignore"):
+        res = ri - pr_o[..., 0]
+    check_inputs(rec, res=_nan_canon(res))
+    assert sha(orc.uniform_quantize(seg, res, 0.04)) == rec["q"]
     lk, la = QUANT_LEVELS
     qn_o, s_o = orc.nonuniform_quantize(seg, res, kp, lk, la, 2)
     assert sha(qn_o) == rec["qn"] and sha(s_o) == rec["sal"]

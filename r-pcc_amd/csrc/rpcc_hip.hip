@@ -2362,6 +2362,43 @@ extern "C" int rpcc_fps_range(const float *ri, const float *tm, float *temp, con
 }
 
 // ================================================================================================
+// steps that the per-label aggregations share (assignment, label histogram, quantiser)
+// ================================================================================================
+// Those kernels give a lane four pixels and aggregate a wavefront's pixels label by label: the pending pixels are four lane masks in
+// scalar registers (one per pixel slot), a round takes the label of the first pending pixel and every pixel that carries it.
+// The labels of the four consecutive pixels from pixel q on in one 4- or 8-byte load (q % 4 == 0 and seg aligned for it: hist_vec / quantise_vec):
+template <class L>
+__device__ __forceinline__ void load_labels4(const L *seg, uint32_t q, int (&lab)[4]) {
+    if (sizeof(L) == 1) {
+        const uint32_t l4 = ld_at(reinterpret_cast<const uint32_t *>(seg), q);
+        lab[0] = (int)(l4 & 255u); lab[1] = (int)((l4 >> 8) & 255u); lab[2] = (int)((l4 >> 16) & 255u); lab[3] = (int)(l4 >> 24);
+    } else {
+        const uint2 l8 = ld_at(reinterpret_cast<const uint2 *>(seg), q * 2u);
+        lab[0] = (int)(l8.x & 0xFFFFu); lab[1] = (int)(l8.x >> 16); lab[2] = (int)(l8.y & 0xFFFFu); lab[3] = (int)(l8.y >> 16);
+    }
+}
+// a round's label: that of the first pending pixel of the lowest pending slot (pend[e]: the lanes whose pixel e is pending; not all empty).
+__device__ __forceinline__ int round_label(const int (&lab)[4], const unsigned long long (&pend)[4]) {
+    if (pend[0]) return __builtin_amdgcn_readlane(lab[0], (int)__ffsll((long long)pend[0]) - 1);
+    if (pend[1]) return __builtin_amdgcn_readlane(lab[1], (int)__ffsll((long long)pend[1]) - 1);
+    if (pend[2]) return __builtin_amdgcn_readlane(lab[2], (int)__ffsll((long long)pend[2]) - 1);
+    return __builtin_amdgcn_readlane(lab[3], (int)__ffsll((long long)pend[3]) - 1);
+}
+// The point model's range sums are exact integers in units of 2^-28 m (DESIGN.md "point model").  The value of a range r (bit pattern rb) in
+// [2^-5, 2^8) is read off its bits: r * 2^28 = mantissa << (exponent + 5), below 2^36, as an 18-bit low part and a high part (r * 2^28 =
+// hi << 18 | lo) whose sums over a wavefront's 256 pixels stay below 2^32.  false, and nothing to add, for a range outside that window (or
+// NaN): the caller raises the frame's flags[4 b], and point_model_row sums that frame sequentially.
+__device__ __forceinline__ bool range_fixed(uint32_t rb, uint32_t &lo, uint32_t &hi) {
+    const float r = u2f(rb);
+    lo = hi = 0u;
+    if (!(r >= 0.03125f && r < 256.0f)) return false;
+    const uint32_t sh = (rb >> 23) - 122u, m = (rb & 0x7FFFFFu) | 0x800000u;   // biased exponent 122 .. 134
+    lo = (m << sh) & 0x3FFFFu;
+    hi = m >> (18u - sh);
+    return true;
+}
+
+// ================================================================================================
 // a7  assignment + relabel  (utils/segment_utils.py:21-23,64-67,127-131,168-169)
 // ================================================================================================
 // distance = concat(ground fp64, radius fp32->fp64); seg = argmax(-abs(distance)) = first minimum of
@@ -2465,11 +2502,19 @@ __device__ __forceinline__ int assign_label(float r, float tx, float ty, float t
 #define ASSIGN_WAVES 4   // wavefronts per workgroup (they share the centre table in LDS, nothing else)
 #define ASSIGN_VGPR_ATTR
 // L: label type (uint8_t: cluster_num <= 254; uint16_t: up to RPCC_MAX_CLUSTERS_MID), NR: screening rounds of 64 centres (4 / 16)
-template <class L = uint8_t, int NR = 4>
+// S = LabelSums (the fused batch with the point model): the wavefront also adds the ranges of its tile's cluster pixels (label >= 2) to the
+// labels' sums [B][KP] -- what the label histogram would otherwise read ri again for; sums / flags are zero at entry (BatchInit).  The sums
+// are integers (range_fixed), so neither the tiles' order nor the wavefronts' matters.  S = NoSums: labels only.  (The form is the type
+// of the last argument, so a launch names L and NR alone.)
+struct NoSums {};
+struct LabelSums { int64_t *sums; int32_t *flags; int KP; };
+template <class L = uint8_t, int NR = 4, class S = NoSums>
 __global__ __launch_bounds__(64 * ASSIGN_WAVES) ASSIGN_VGPR_ATTR void assign_kernel(const float *__restrict__ ri, const float *__restrict__ tm,
                                                      const double *__restrict__ ground,
                                                      const float *__restrict__ centers, int H, int W, int M,
-                                                     L *__restrict__ seg, const float *__restrict__ temp) {   // temp: the FPS state after its last iteration, or NULL
+                                                     L *__restrict__ seg, const float *__restrict__ temp,   // temp: the FPS state after its last iteration, or NULL
+                                                     const S acc) {
+    constexpr bool SUMS = std::is_same<S, LabelSums>::value;
     extern __shared__ __attribute__((aligned(16))) float4 cen4[];  // [M] (x,y,z,0)
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int P = H * W;
@@ -2617,25 +2662,69 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES) ASSIGN_VGPR_ATTR void assign_ker
                 }
             }
         }
+        int lab[ASSIGN_PX];
 #pragma unroll
         for (int e = 0; e < ASSIGN_PX; e++) {
-            int label = assign_label(r[e], tx[e], ty[e], tz[e], x[e], y[e], z[e], m1[e], m2[e], k1[e], cen4, G);
-            if (r[e] == 0.0f) label = 1;
-            if (valid[e]) st_at(seg_b, (uint32_t)p[e] * (uint32_t)sizeof(L), (L)label);
+            lab[e] = assign_label(r[e], tx[e], ty[e], tz[e], x[e], y[e], z[e], m1[e], m2[e], k1[e], cen4, G);
+            if (r[e] == 0.0f) lab[e] = 1;
+            if (valid[e]) st_at(seg_b, (uint32_t)p[e] * (uint32_t)sizeof(L), (L)lab[e]);
+        }
+        if constexpr (SUMS) {
+            int todo[ASSIGN_PX];   // the pixel's label if its range is to be summed (a cluster label is never an empty or invalid pixel's), else -1
+#pragma unroll
+            for (int e = 0; e < ASSIGN_PX; e++) todo[e] = lab[e] >= 2 ? lab[e] : -1;
+            // The histogram's aggregation (model_hist_body) without its round limit, since no LDS table takes what is left: one round per
+            // distinct cluster label of the tile -- usually one or two --, one 64-bit atomic per round.  Every test of the loop is wave-uniform.
+            static_assert(ASSIGN_PX == 4, "four pixel slots: round_label");
+            uint32_t lo[ASSIGN_PX], hi[ASSIGN_PX];
+            bool inexact = false;
+            unsigned long long pend[ASSIGN_PX];
+#pragma unroll
+            for (int e = 0; e < ASSIGN_PX; e++) {
+                lo[e] = hi[e] = 0u;
+                if (todo[e] >= 2) inexact |= !range_fixed(f2u(r[e]), lo[e], hi[e]);
+                pend[e] = __ballot(todo[e] >= 2);
+            }
+#pragma unroll 1
+            while ((pend[0] | pend[1] | pend[2] | pend[3]) != 0ull) {
+                const int cur = round_label(todo, pend);
+                uint32_t slo = 0u, shi = 0u;
+#pragma unroll
+                for (int e = 0; e < ASSIGN_PX; e++) {
+                    const bool mine = todo[e] == cur;
+                    pend[e] &= ~__ballot(mine);
+                    slo += mine ? lo[e] : 0u;
+                    shi += mine ? hi[e] : 0u;
+                }
+                slo = dpp_sum_u32(slo); shi = dpp_sum_u32(shi);
+                if (lane == 0)
+                    atomicAdd(reinterpret_cast<unsigned long long *>(&acc.sums[(int64_t)b * acc.KP + cur]), (unsigned long long)slo + ((unsigned long long)shi << 18));
+            }
+            if (__any(inexact) && lane == 0) acc.flags[4 * b] = 1;
         }
     }
 }
 
+static inline int kpad(int M);   // (labels per row of the sums block: with the model part's layout, a8)
 // uint16 labels: 8 screening rounds of 64 centres up to 510 clusters, 16 above
-template <class L>
-static int launch_assign(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H,
-                         int W, int M, L *seg, hipStream_t st, const float *temp = nullptr) {
+template <class L, class S>
+static void launch_assign_form(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H, int W, int M, L *seg,
+                               hipStream_t st, const float *temp, const S acc) {
     const int ntile = ((H + ASSIGN_ROWS - 1) / ASSIGN_ROWS) * ((W + 31) / 32);
     const dim3 grid((ntile + ASSIGN_WAVES * ASSIGN_TILES_PER_WAVE - 1) / (ASSIGN_WAVES * ASSIGN_TILES_PER_WAVE), B);
     const size_t sh = (size_t)M * sizeof(float4);
-    if constexpr (sizeof(L) == 1) assign_kernel<L, 4><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp);
-    else if (M <= 510)            assign_kernel<L, 8><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp);
-    else                          assign_kernel<L, 16><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp);
+    if constexpr (sizeof(L) == 1) assign_kernel<L, 4><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp, acc);
+    else if (M <= 510)            assign_kernel<L, 8><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp, acc);
+    else                          assign_kernel<L, 16><<<grid, 64 * ASSIGN_WAVES, sh, st>>>(ri, tm, ground, centers, H, W, M, seg, temp, acc);
+}
+// sums / flags (both or neither; of the model part of the batch's workspace, zero): the form that adds the labels' range sums, for a caller
+// whose histogram then only counts
+template <class L>
+static int launch_assign(const float *ri, const float *tm, const double *ground, const float *centers, int B, int H,
+                         int W, int M, L *seg, hipStream_t st, const float *temp = nullptr, int64_t *sums = nullptr, int32_t *flags = nullptr) {
+    ARG_TRY((sums == nullptr) == (flags == nullptr));
+    if (sums != nullptr) launch_assign_form(ri, tm, ground, centers, B, H, W, M, seg, st, temp, LabelSums{sums, flags, kpad(M)});
+    else                 launch_assign_form(ri, tm, ground, centers, B, H, W, M, seg, st, temp, NoSums{});
     LAUNCH_CHECK();
     return RPCC_OK;
 }
@@ -2883,38 +2972,21 @@ __global__ __launch_bounds__(SCANW_THREADS) void model_scan_wide_kernel(const fl
 // -- usually most of the 256 -- are aggregated once per wavefront (four compare masks counted in scalar registers, two DPP
 // sums for the range total), the others add themselves to LDS directly: integer sums, any order.  The fixed-point value of a
 // range r in [2^-5, 2^8) is read off its bit pattern: r * 2^28 = mantissa << (exponent + 5), an integer below 2^36, kept as
-// an 18-bit low part and a high part whose sums over a wavefront stay below 2^32.
+// an 18-bit low part and a high part whose sums over a wavefront stay below 2^32 (range_fixed; load_labels4 and round_label: ahead of a7).
 //
-// Two steps are shared with the quantiser (predict_quantize_body: same pixels per lane, same rounds): the labels of the four consecutive
-// pixels from pixel q on in one 4- or 8-byte load (q % 4 == 0 and seg aligned for it: hist_vec / quantise_vec),
-template <class L>
-__device__ __forceinline__ void load_labels4(const L *seg, uint32_t q, int (&lab)[4]) {
-    if (sizeof(L) == 1) {
-        const uint32_t l4 = ld_at(reinterpret_cast<const uint32_t *>(seg), q);
-        lab[0] = (int)(l4 & 255u); lab[1] = (int)((l4 >> 8) & 255u); lab[2] = (int)((l4 >> 16) & 255u); lab[3] = (int)(l4 >> 24);
-    } else {
-        const uint2 l8 = ld_at(reinterpret_cast<const uint2 *>(seg), q * 2u);
-        lab[0] = (int)(l8.x & 0xFFFFu); lab[1] = (int)(l8.x >> 16); lab[2] = (int)(l8.y & 0xFFFFu); lab[3] = (int)(l8.y >> 16);
-    }
-}
-// and a round's label: that of the first pending pixel of the lowest pending slot (pend[e]: the lanes whose pixel e is pending; not all empty).
-__device__ __forceinline__ int round_label(const int (&lab)[4], const unsigned long long (&pend)[4]) {
-    if (pend[0]) return __builtin_amdgcn_readlane(lab[0], (int)__ffsll((long long)pend[0]) - 1);
-    if (pend[1]) return __builtin_amdgcn_readlane(lab[1], (int)__ffsll((long long)pend[1]) - 1);
-    if (pend[2]) return __builtin_amdgcn_readlane(lab[2], (int)__ffsll((long long)pend[2]) - 1);
-    return __builtin_amdgcn_readlane(lab[3], (int)__ffsll((long long)pend[3]) - 1);
-}
-template <bool VEC, class L = uint8_t>
+// SUMS = false is the count-only form: no range is loaded, no sum code is compiled, and the LDS holds the counts alone (hist_lds_bytes).
+// It serves the callers that need offsets only (the plane model, the decoder) and the fused batch, whose assignment has added the labels'
+// range sums already (assign_kernel<.., LabelSums>); `ri`, `sums` and `flags` are not touched then.
+template <bool VEC, class L = uint8_t, bool SUMS = true>
 __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, const L *__restrict__ seg,
                                                 int P, int KP, int T, int64_t *__restrict__ sums,
                                                 int32_t *__restrict__ flags, uint32_t *__restrict__ hist, const int b, const int t) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    unsigned long long *ssum = reinterpret_cast<unsigned long long *>(smem_raw);  // [KP]
-    uint32_t *scnt = reinterpret_cast<uint32_t *>(ssum + KP);                      // [KP]
+    unsigned long long *ssum = reinterpret_cast<unsigned long long *>(smem_raw);              // [KP] (SUMS only)
+    uint32_t *scnt = reinterpret_cast<uint32_t *>(SUMS ? smem_raw + (size_t)KP * 8 : smem_raw);  // [KP]
     const int lane = threadIdx.x & 63;
     const L *seg_b = seg + (int64_t)b * P;
-    const float *ri_b = ri != nullptr ? ri + (int64_t)b * P : nullptr;
-    const bool want_sum = ri != nullptr;
+    const float *ri_b = SUMS ? ri + (int64_t)b * P : nullptr;
     const int p0 = t * TILE + 4 * (int)threadIdx.x;
     const int nval = min(max(P - p0, 0), 4);
     int lab[4];
@@ -2923,21 +2995,22 @@ __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, co
     if (VEC) {
         const uint32_t q = (uint32_t)(nval > 0 ? p0 : 0);
         load_labels4(seg_b, q, lab);
-        if (want_sum) {
+        if constexpr (SUMS) {
             const uint4 r4 = ld_at(reinterpret_cast<const uint4 *>(ri_b), q * 4u);
             rb[0] = r4.x; rb[1] = r4.y; rb[2] = r4.z; rb[3] = r4.w;
-        } else {
-            rb[0] = rb[1] = rb[2] = rb[3] = 0x3F800000u;
         }
     } else {
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             const uint32_t gp = (uint32_t)min(p0 + e, P - 1);
             lab[e] = ld_at(seg_b, gp * (uint32_t)sizeof(L));
-            rb[e] = want_sum ? f2u(ld_at(ri_b, gp * 4u)) : 0x3F800000u;
+            if constexpr (SUMS) rb[e] = f2u(ld_at(ri_b, gp * 4u));
         }
     }
-    for (int k = threadIdx.x; k < KP; k += blockDim.x) { ssum[k] = 0ull; scnt[k] = 0u; }  // while the loads are in flight
+    for (int k = threadIdx.x; k < KP; k += blockDim.x) {   // while the loads are in flight
+        if constexpr (SUMS) ssum[k] = 0ull;
+        scnt[k] = 0u;
+    }
     __syncthreads();
     bool inexact = false;
     int todo[4];
@@ -2946,15 +3019,8 @@ __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, co
     for (int e = 0; e < 4; e++) {
         todo[e] = e < nval ? lab[e] : -1;
         lo[e] = hi[e] = 0u;
-        if (want_sum && todo[e] >= 2) {
-            const float r = u2f(rb[e]);
-            if (!(r >= 0.03125f && r < 256.0f)) {
-                inexact = true;
-            } else {   // r * 2^28, exact (see above): biased exponent 122 .. 134
-                const uint32_t sh = (rb[e] >> 23) - 122u, m = (rb[e] & 0x7FFFFFu) | 0x800000u;
-                lo[e] = (m << sh) & 0x3FFFFu;
-                hi[e] = m >> (18u - sh);
-            }
+        if constexpr (SUMS) {
+            if (todo[e] >= 2) inexact |= !range_fixed(rb[e], lo[e], hi[e]);
         }
     }
     // up to HIST_ROUNDS labels of the wavefront are aggregated (the label of the first pixel still pending: 256 consecutive
@@ -2975,10 +3041,9 @@ __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, co
             const unsigned long long m = __ballot(mine);
             ctot += (int)__popcll(m);
             pend[e] &= ~m;
-            slo += mine ? lo[e] : 0u;
-            shi += mine ? hi[e] : 0u;
+            if constexpr (SUMS) { slo += mine ? lo[e] : 0u; shi += mine ? hi[e] : 0u; }
         }
-        const bool sum = want_sum && cur >= 2;
+        const bool sum = SUMS && cur >= 2;
         if (sum) { slo = dpp_sum_u32(slo); shi = dpp_sum_u32(shi); }
         if (lane == 0) {
             atomicAdd(&scnt[cur], (uint32_t)ctot);
@@ -2989,53 +3054,66 @@ __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, co
     for (int e = 0; e < 4; e++) {
         if (pend[e] != 0ull && ((pend[e] >> lane) & 1ull)) {   // (first test wave-uniform: usually nothing is left)
             atomicAdd(&scnt[todo[e]], 1u);
-            if (want_sum && todo[e] >= 2) atomicAdd(&ssum[todo[e]], (unsigned long long)lo[e] + ((unsigned long long)hi[e] << 18));
+            if constexpr (SUMS) {
+                if (todo[e] >= 2) atomicAdd(&ssum[todo[e]], (unsigned long long)lo[e] + ((unsigned long long)hi[e] << 18));
+            }
         }
     }
-    if (__any(inexact) && lane == 0) flags[4 * b] = 1;
+    if constexpr (SUMS) {
+        if (__any(inexact) && lane == 0) flags[4 * b] = 1;
+    }
     __syncthreads();
     for (int k = threadIdx.x; k < KP; k += blockDim.x) {
         hist[((int64_t)b * T + t) * KP + k] = scnt[k];
-        if (ssum[k]) atomicAdd(reinterpret_cast<unsigned long long *>(&sums[(int64_t)b * KP + k]), ssum[k]);
+        if constexpr (SUMS) {
+            if (ssum[k]) atomicAdd(reinterpret_cast<unsigned long long *>(&sums[(int64_t)b * KP + k]), ssum[k]);
+        }
     }
 }
-template <bool VEC, class L = uint8_t>
+template <bool VEC, class L = uint8_t, bool SUMS = true>
 __global__ __launch_bounds__(256) void model_hist_kernel(const float *__restrict__ ri, const L *__restrict__ seg,
                                                          int P, int KP, int T, int64_t *__restrict__ sums,
                                                          int32_t *__restrict__ flags, uint32_t *__restrict__ hist) {
-    model_hist_body<VEC, L>(ri, seg, P, KP, T, sums, flags, hist, blockIdx.y, blockIdx.x);
+    model_hist_body<VEC, L, SUMS>(ri, seg, P, KP, T, sums, flags, hist, blockIdx.y, blockIdx.x);
 }
+// (rpcc_compress_batch_mixed: every group's assignment has added its range sums, so the shared launch is the count-only form)
 struct HistGroup {
-    const float *ri;
     const uint8_t *seg;
     int P, T, vec;
-    int64_t *sums;
-    int32_t *flags;
     uint32_t *hist;
 };
 __global__ __launch_bounds__(256) void model_hist_multi_kernel(const MultiArgs<HistGroup> m, int KP) {
     int b, t;
     const HistGroup &a = multi_locate(m, b, t);
-    if (a.vec) model_hist_body<true>(a.ri, a.seg, a.P, KP, a.T, a.sums, a.flags, a.hist, b, t);
-    else       model_hist_body<false>(a.ri, a.seg, a.P, KP, a.T, a.sums, a.flags, a.hist, b, t);
+    if (a.vec) model_hist_body<true, uint8_t, false>(nullptr, a.seg, a.P, KP, a.T, nullptr, nullptr, a.hist, b, t);
+    else       model_hist_body<false, uint8_t, false>(nullptr, a.seg, a.P, KP, a.T, nullptr, nullptr, a.hist, b, t);
 }
-// model_hist_body's LDS (ssum u64 [KP] | scnt u32 [KP]) and whether a group may take its VEC form: the 4-pixel loads of seg and -- when the
-// range sums are wanted -- of ri are aligned and never straddle the frame's end
-static inline size_t hist_lds_bytes(int KP) { return (size_t)KP * 8 + (size_t)KP * 4; }
+// model_hist_body's LDS ((with sums) ssum u64 [KP] | scnt u32 [KP]) and whether a group may take its VEC form: the 4-pixel loads of seg and
+// -- when the range sums are wanted -- of ri are aligned and never straddle the frame's end
+static inline size_t hist_lds_bytes(int KP, bool sums) { return (sums ? (size_t)KP * 8 : 0) + (size_t)KP * 4; }
 template <class L>
 static inline bool hist_vec(int P, const L *seg, const float *ri) { return (P & 3) == 0 && seg4_aligned(seg) && (ri == nullptr || aligned16(ri)); }
 static inline int scan_kp2(int M) { int v = 1; while (v < M + 2) v <<= 1; return v; }   // labels rounded up to a power of two (<= 256)
 // histogram + scan: tile x label counts (and the labels' range sums when ri is given), then the offsets of the ordered scatter, counts, nnz and
-// -- with `model` -- the point model's rows.  The sums / flags block must be zero (memset or BatchInit).
+// -- with `model` -- the point model's rows.  The sums / flags block must be zero (memset or BatchInit) before the sums are added: by the
+// histogram here, or -- summed = true -- by the assignment that wrote seg (launch_assign with lay.sums / lay.flags); the histogram is then
+// the count-only form, and ri serves the scan's sequential fallback alone (point_model_row).
 template <class L>
 static int launch_hist_scan(const float *ri, const L *seg, const double *ground, int B, int P, int M, const WsLayout &lay, float *model,
-                            int32_t *counts, int32_t *nnz, hipStream_t st) {
+                            int32_t *counts, int32_t *nnz, hipStream_t st, bool summed = false) {
     const int KP = kpad(M), T = ntiles(P);
-    const size_t sh = hist_lds_bytes(KP);
+    const bool hist_sums = ri != nullptr && !summed;
+    const size_t sh = hist_lds_bytes(KP, hist_sums);
+    const bool vec = hist_vec(P, seg, hist_sums ? ri : nullptr);
     // (The scan as the tail of the histogram kernel -- the frame's last workgroup to finish runs it -- was measured in round 4: a workgroup must
     // release its rows device-wide before it draws its ticket, and an agent-scope fence writes the XCD's L2 back: 62 us -> 2.9 ms.)
-    if (hist_vec(P, seg, ri)) model_hist_kernel<true, L><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
-    else                      model_hist_kernel<false, L><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
+    if (hist_sums) {
+        if (vec) model_hist_kernel<true, L, true><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
+        else     model_hist_kernel<false, L, true><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
+    } else {
+        if (vec) model_hist_kernel<true, L, false><<<dim3(T, B), 256, sh, st>>>(nullptr, seg, P, KP, T, nullptr, nullptr, lay.hist);
+        else     model_hist_kernel<false, L, false><<<dim3(T, B), 256, sh, st>>>(nullptr, seg, P, KP, T, nullptr, nullptr, lay.hist);
+    }
     LAUNCH_CHECK();
     if constexpr (sizeof(L) == 1) {
         const ScanArgs sa = {ri, seg, ground, P, M, KP, T, scan_kp2(M), lay.sums, lay.flags, lay.hist, model, counts, nnz};
@@ -3050,10 +3128,10 @@ static int launch_hist_scan(const float *ri, const L *seg, const double *ground,
 // One workgroup per frame: label totals, tile offsets, label bases, means, model rows.
 template <class L>
 static int launch_point_model(const float *ri, const L *seg, const double *ground, int B, int P, int M,
-                              float *model, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared = false) {
+                              float *model, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared = false, bool summed = false) {
     const WsLayout lay = ws_layout(ws, B, P, M);
     if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
-    return launch_hist_scan(ri, seg, ground, B, P, M, lay, model, counts, nnz, st);
+    return launch_hist_scan(ri, seg, ground, B, P, M, lay, model, counts, nnz, st, summed);
 }
 
 template <class L>
@@ -3672,9 +3750,11 @@ static int run_stage(const BatchPlan &p, int stage, hipStream_t st) {
                                 p.tiled ? p.tiletab : nullptr, io->timer, st, p.rays_soa);
     case ST_ASSIGN_LABELS:
         // (the FPS state is the un-fused minimum the assignment's bound needs; a CUDA-binary mode contracts it)
+        // (the point model's range sums are added by the assignment -- into the block BatchInit cleared --, its histogram only counts)
         if ((rc = launch_assign(io->ri, io->tm, io->ground, io->centers, Bs, p.g.H, p.g.W, M, seg, st,
-                                (io->flags & RPCC_FPS_MODE_BITS) ? nullptr : p.temp))) return rc;
-        if (io->model_method == 0) return launch_point_model(io->ri, seg, io->ground, Bs, P, M, io->model, io->counts, io->nnz, p.ws, st, true);
+                                (io->flags & RPCC_FPS_MODE_BITS) ? nullptr : p.temp, io->model_method == 0 ? p.L.sums : nullptr,
+                                io->model_method == 0 ? p.L.flags : nullptr))) return rc;
+        if (io->model_method == 0) return launch_point_model(io->ri, seg, io->ground, Bs, P, M, io->model, io->counts, io->nnz, p.ws, st, true, true);
         if ((rc = launch_label_scan(seg, Bs, P, M, io->counts, io->nnz, p.ws, st, true))) return rc;
         return launch_label_order(io->ri, io->tm, seg, Bs, P, M, p.ws, p.extra, st);
     case ST_PLANES:
@@ -3822,8 +3902,10 @@ static int mixed_assign(const BatchPlan *pl, int G, hipStream_t st) {
     int rc;
     for (int i = 0; i < G; i++) {
         const rpcc_batch_io *io = pl[i].io;
+        const bool point = io->model_method == 0;   // (the point model's range sums: as in run_stage)
         if ((rc = launch_assign(io->ri, io->tm, io->ground, io->centers, pl[i].Bs, pl[i].g.H, pl[i].g.W, pl[i].M, io->seg, st,
-                                (io->flags & RPCC_FPS_MODE_BITS) ? nullptr : pl[i].temp))) return rc;
+                                (io->flags & RPCC_FPS_MODE_BITS) ? nullptr : pl[i].temp, point ? pl[i].L.sums : nullptr,
+                                point ? pl[i].L.flags : nullptr))) return rc;
     }
     return RPCC_OK;
 }
@@ -3837,14 +3919,14 @@ static int mixed_labels(const BatchPlan *pl, int G, hipStream_t st) {
         const rpcc_batch_io *io = p.io;
         const int T = ntiles(p.P);
         const bool point = io->model_method == 0;
-        const float *ri = point ? io->ri : nullptr;   // (the plane model needs no range sums)
-        multi_add(mh, HistGroup{ri, io->seg, p.P, T, hist_vec(p.P, io->seg, ri) ? 1 : 0, p.L.sums, p.L.flags, p.L.hist}, p.Bs, T);
+        const float *ri = point ? io->ri : nullptr;   // (the scan's sequential fallback; the sums themselves came with the assignment)
+        multi_add(mh, HistGroup{io->seg, p.P, T, hist_vec(p.P, io->seg, (const float *)nullptr) ? 1 : 0, p.L.hist}, p.Bs, T);
         multi_add(ms, ScanArgs{ri, io->seg, point ? io->ground : nullptr, p.P, M, KP, T, scan_kp2(M), p.L.sums, p.L.flags, p.L.hist,
                                point ? io->model : nullptr, io->counts, io->nnz}, p.Bs, 1);
         const PlaneLayout pa = plane_layout(p.extra, p.Bs, p.P);
         if (!point) multi_add(mo, OrderGroup{io->seg, p.L.hist, p.P, T, pa.order, io->ri, io->tm, pa.pts4}, p.Bs, T);
     }
-    model_hist_multi_kernel<<<mh.first[mh.n], 256, hist_lds_bytes(KP), st>>>(mh, KP);
+    model_hist_multi_kernel<<<mh.first[mh.n], 256, hist_lds_bytes(KP, false), st>>>(mh, KP);
     LAUNCH_CHECK();
     model_scan_multi_kernel<<<ms.first[ms.n], SCAN_THREADS, 0, st>>>(ms);
     LAUNCH_CHECK();

@@ -107,17 +107,7 @@ __global__ __launch_bounds__(256) void wide_keys_kernel(const L *__restrict__ se
     if (valid) { keys[g] = ((uint32_t)b << 16) | l; vals[g] = (uint32_t)p; }
     uint32_t lo = 0u, hi = 0u;   // r * 2^28 = hi << 18 | lo: the sums of either part over a wavefront stay below 2^32
     bool bad = false;
-    if (valid && ri != nullptr && l >= 2u) {
-        const uint32_t rb = f2u(ri[g]);
-        const float r = u2f(rb);
-        if (!(r >= 0.03125f && r < 256.0f)) {
-            bad = true;
-        } else {   // biased exponent 122 .. 134: r * 2^28 = mantissa << (exponent - 122)
-            const uint32_t sh = (rb >> 23) - 122u, m = (rb & 0x7FFFFFu) | 0x800000u;
-            lo = (m << sh) & 0x3FFFFu;
-            hi = m >> (18u - sh);
-        }
-    }
+    if (valid && ri != nullptr && l >= 2u) bad = !range_fixed(f2u(ri[g]), lo, hi);
     if (__any(bad) && lane == 0) flags[4 * b] = 1;
     unsigned long long pend = __ballot(valid);
 #pragma unroll 1

@@ -44,7 +44,7 @@ extern "C" {
 
 /* Caller's buffers (held by tests/test_gpu_buffers.py: exact sizes, hostile contents, guard bytes around them).
  * Work buffers -- `ws`, `scratch`, `fps_table`, sized by rpcc_workspace_bytes[_general], rpcc_wide_workspace_bytes,
- * rpcc_project_scratch_bytes, rpcc_fps_table_bytes, rpcc_plane_workspace_bytes, rpcc_codec_workspace_bytes, rpcc_decompress_workspace_bytes -- need NO initialisation: they
+ * rpcc_project_scratch_bytes, rpcc_fps_table_bytes, rpcc_plane_workspace_bytes, rpcc_codec_workspace_bytes, rpcc_decompress_workspace_bytes, rpcc_labels_workspace_bytes -- need NO initialisation: they
  * may hold anything, including what an earlier call left there under other arguments (another B, P, M, point count or entry point), and a
  * buffer larger than asked for may be handed to calls of different shapes in turn.  Every entry clears or overwrites what it reads; the
  * fused batch compares its per-frame projection flags with a mark kept inside ws, and a stale word that happens to equal the mark only
@@ -67,7 +67,9 @@ extern "C" {
  * (r-pcc_amd/_lib.py does).  100: round 3.  101: rpcc_batch_io.point_stride_bytes.  102: the uint16-label entries (rpcc_*_wide), rpcc_compress_batch_stages.
  * 103: the scanner-order window projection entry, the RPCC_PROJECT_* bits of rpcc_batch_io.flags, the uint16 stage entries (rpcc_assign_wide ...).
  * 104: the window projection entry and the RPCC_PROJECT_* bits removed (rpcc_batch_io.flags takes the FPS bits only).
- * 105: rpcc_decompress_batch, rpcc_decompress_batch_wide, rpcc_decompress_workspace_bytes and the RPCC_STREAM_* status codes. */
+ * 105: rpcc_decompress_batch, rpcc_decompress_batch_wide, rpcc_decompress_workspace_bytes and the RPCC_STREAM_* status codes.
+ * (rpcc_compress_batch_labels, rpcc_labels_workspace_bytes, rpcc_labels_io and the RPCC_LABELS_* codes were added under 105: they leave every
+ * struct and argument that existed as it was, and a binding that needs them finds a library without them when it resolves its symbols.) */
 #define RPCC_ABI_VERSION 105
 int rpcc_version(void);
 const char *rpcc_last_error(void);
@@ -395,6 +397,48 @@ int rpcc_contour_encode_wide(const uint16_t *seg, int B, int H, int W, uint8_t *
 int rpcc_contour_decode_wide(const uint8_t *contour_bits, const uint16_t *idx_sequence, int B, int H, int W, uint16_t *seg, void *ws, void *stream);
 int rpcc_decode_wide(const uint16_t *seg, const int16_t *q16, const float *model, const float *tm, const double *level_acc, int levels,
                      const uint8_t *salience, int B, int P, int M, float *ri_rec, float *pc_rec, void *ws, void *stream);
+
+/* ---- the batch from a caller's label map: a8..a13 for B frames whose segmentation exists already ------------------------------------ *
+ * The stages of rpcc_compress_batch behind its assignment, entered with int32 labels in rpcc_seg_dbscan's convention (include/rpcc_seg.h;
+ * the reference's segment_method 'DBSCAN', utils/segment_utils.py:149-169): ground 0, ri == 0 pixels 1, noise 2, clusters from 3.  M is a label
+ * CAP, not a cluster count: frame b uses the labels 0 .. max_label[b], and these must be <= M + 1; K = M + 2 rows per frame as everywhere.
+ * M <= RPCC_MAX_CLUSTERS: byte labels, the kernels of rpcc_compress_batch; up to RPCC_MAX_CLUSTERS_MID: uint16 labels, the same kernels as
+ * rpcc_compress_batch_wide runs for such counts; above: RPCC_ERR_ARG.  One pass over the int32 labels (the label intake) writes the narrow map
+ * `seg`, checks every label against min(max_label[b], M + 1) and leaves the per-tile label counts -- for the point model the per-label range
+ * sums too -- that the label histogram would otherwise read `seg` again for; point or plane model, key points and salience levels, prediction
+ * and quantiser follow as in rpcc_compress_batch.  Everything is queued on `stream`; nothing synchronises.
+ *   ws       dev, rpcc_labels_workspace_bytes(B, P, M, general) bytes (general != 0: plane model and / or non-uniform framework); needs no
+ *            initialisation, like every work buffer (see "Caller's buffers")
+ * A frame is REFUSED when max_label[b] is RPCC_LABELS_CAPPED (what rpcc_seg_dbscan writes as RPCC_SEG_CAPPED), negative or above M + 1, or when
+ * one of its labels lies outside 0 .. max_label[b]: its status is RPCC_LABELS_E_CAPPED / RPCC_LABELS_E_RANGE, every output row of it (seg,
+ * model, counts, all P entries of q16, salience, key_point_map) is zero bytes and nnz[b] = 0; none of its labels is used as an index.  The
+ * other frames of the batch are what they are without it. */
+#define RPCC_LABELS_CAPPED (-1)
+#define RPCC_LABELS_OK 0
+#define RPCC_LABELS_E_RANGE 1
+#define RPCC_LABELS_E_CAPPED 2
+typedef struct rpcc_labels_io {
+    const float *ri;          /* dev f32 [B,P] */
+    const float *tm;          /* dev f32 [P,3] */
+    const double *ground;     /* dev f64 [B,4] */
+    const int32_t *labels;    /* dev i32 [B,P] */
+    const int32_t *max_label; /* dev i32 [B] */
+    const int64_t *frame_ids; /* dev i64 [B] or NULL (the plane model's seeds; see rpcc_plane_model) */
+    void *seg;                /* dev u8 [B,P] (M <= RPCC_MAX_CLUSTERS) or u16 [B,P] out */
+    float *model;             /* dev f32 [B,K,4] out */
+    int32_t *counts;          /* dev i32 [B,K] out */
+    int16_t *q16;             /* dev i16 [B,P] out */
+    int32_t *nnz;             /* dev i32 [B] out */
+    int32_t *status;          /* dev i32 [B] out: RPCC_LABELS_OK or RPCC_LABELS_E_* */
+    int32_t model_method;     /* as in rpcc_batch_io, with plane_cos_cut / plane_seed */
+    double plane_cos_cut;
+    int64_t plane_seed;
+    const rpcc_nonuniform_cfg *nonuniform; /* HOST, or NULL: uniform framework */
+    uint8_t *salience;        /* dev u8 [B,K] out (non-uniform) */
+    uint8_t *key_point_map;   /* dev u8 [B,P] out (non-uniform) */
+} rpcc_labels_io;
+size_t rpcc_labels_workspace_bytes(int B, int P, int M, int general);
+int rpcc_compress_batch_labels(const rpcc_labels_io *io, int B, rpcc_geom g, int M, float acc, void *ws, void *stream);
 
 /* ---- f3 for a batch of streams: the decoding counterpart of rpcc_compress_batch ------------------------------------------------ *
  * Takes the decoded payloads of B frames where the entropy decoders left them -- every row padded to the geometry's maximum -- and gives label maps,

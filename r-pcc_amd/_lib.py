@@ -28,6 +28,13 @@ class BatchIO(C.Structure):
                 ("point_stride_bytes", C.c_int32)]
 
 
+class LabelsIO(C.Structure):   # rpcc_labels_io
+    _fields_ = [("ri", C.c_void_p), ("tm", C.c_void_p), ("ground", C.c_void_p), ("labels", C.c_void_p), ("max_label", C.c_void_p),
+                ("frame_ids", C.c_void_p), ("seg", C.c_void_p), ("model", C.c_void_p), ("counts", C.c_void_p), ("q16", C.c_void_p),
+                ("nnz", C.c_void_p), ("status", C.c_void_p), ("model_method", C.c_int32), ("plane_cos_cut", C.c_double),
+                ("plane_seed", C.c_int64), ("nonuniform", C.c_void_p), ("salience", C.c_void_p), ("key_point_map", C.c_void_p)]
+
+
 class NonuniformCfg(C.Structure):
     _fields_ = [("levels", C.c_int32), ("level_kp_num", C.c_int32 * 8), ("level_acc", C.c_float * 8), ("ground_level", C.c_int32),
                 ("feature_region", C.c_int32), ("segments", C.c_int32), ("sharp_num", C.c_int32), ("less_sharp_num", C.c_int32),
@@ -42,6 +49,7 @@ MAX_CLUSTERS_WIDE = 65533   # RPCC_MAX_CLUSTERS_WIDE: the uint16-label entries (
 MAX_CLUSTERS_MID = 1022     # RPCC_MAX_CLUSTERS_MID: the tuned kernels on uint16 labels; the uint16 STAGE entries (rpcc_assign_wide ...)
 STREAM_OK, STREAM_E_ENTROPY, STREAM_E_PLANE, STREAM_E_CONTOUR, STREAM_E_WIDTH = 0, 1, 2, 3, 4     # RPCC_STREAM_* (rpcc_decompress_batch)
 STREAM_E_NSEQ, STREAM_E_LABEL, STREAM_E_SALIENCE, STREAM_E_RESIDUAL, STREAM_E_CONTAINER = 5, 6, 7, 8, 9
+LABELS_OK, LABELS_E_RANGE, LABELS_E_CAPPED = 0, 1, 2     # RPCC_LABELS_* (rpcc_compress_batch_labels)
 ABI_VERSION = 105      # RPCC_ABI_VERSION: the layout of rpcc_batch_io / rpcc_geom this binding was written for
 
 
@@ -110,6 +118,8 @@ _SIGS = {
     "rpcc_decompress_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "rpcc_decompress_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_double), _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rpcc_decompress_batch_wide": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_double), _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rpcc_labels_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "rpcc_compress_batch_labels": (C.c_int, [C.POINTER(LabelsIO), _I, Geom, _I, _F, _VP, _VP]),
     "rpcc_debug_stamps": (C.c_int, [_VP]),
     "rpcc_timer_create": (_VP, []),
     "rpcc_timer_destroy": (None, [_VP]),
@@ -170,7 +180,11 @@ class Binding:
                                 % (self.name, self.path))
             h = C.CDLL(self.path)
             for name, (res, args) in self.sigs.items():
-                fn = getattr(h, name)
+                try:
+                    fn = getattr(h, name)
+                except AttributeError:   # (a library from before an entry was added under the same interface version)
+                    raise RpccError("%s.so (%s) has no %s (stale build: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`)"
+                                    % (self.name, self.path, name)) from None
                 fn.restype = res
                 fn.argtypes = args
             version = getattr(h, self.prefix + "_version")()

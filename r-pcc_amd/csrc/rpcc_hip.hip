@@ -2977,14 +2977,13 @@ __global__ __launch_bounds__(SCANW_THREADS) void model_scan_wide_kernel(const fl
 // SUMS = false is the count-only form: no range is loaded, no sum code is compiled, and the LDS holds the counts alone (hist_lds_bytes).
 // It serves the callers that need offsets only (the plane model, the decoder) and the fused batch, whose assignment has added the labels'
 // range sums already (assign_kernel<.., LabelSums>); `ri`, `sums` and `flags` are not touched then.
+template <bool SUMS>
+__device__ __forceinline__ void hist_aggregate(const int (&lab)[4], const uint32_t (&rb)[4], const int nval, int KP, int T, int64_t *__restrict__ sums,
+                                               int32_t *__restrict__ flags, uint32_t *__restrict__ hist, const int b, const int t);
 template <bool VEC, class L = uint8_t, bool SUMS = true>
 __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, const L *__restrict__ seg,
                                                 int P, int KP, int T, int64_t *__restrict__ sums,
                                                 int32_t *__restrict__ flags, uint32_t *__restrict__ hist, const int b, const int t) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    unsigned long long *ssum = reinterpret_cast<unsigned long long *>(smem_raw);              // [KP] (SUMS only)
-    uint32_t *scnt = reinterpret_cast<uint32_t *>(SUMS ? smem_raw + (size_t)KP * 8 : smem_raw);  // [KP]
-    const int lane = threadIdx.x & 63;
     const L *seg_b = seg + (int64_t)b * P;
     const float *ri_b = SUMS ? ri + (int64_t)b * P : nullptr;
     const int p0 = t * TILE + 4 * (int)threadIdx.x;
@@ -3007,6 +3006,18 @@ __device__ __forceinline__ void model_hist_body(const float *__restrict__ ri, co
             if constexpr (SUMS) rb[e] = f2u(ld_at(ri_b, gp * 4u));
         }
     }
+    hist_aggregate<SUMS>(lab, rb, nval, KP, T, sums, flags, hist, b, t);
+}
+// The aggregation of a tile's labels (lab[e], e < nval: the lane's pixels; rb[e] their ranges' bits when SUMS) into hist[b][t][.] and -- SUMS --
+// the frame's sums / flag: what model_hist_body does with the labels it loaded, and labels_in_kernel (labels_kernels.h) with the ones it narrowed.
+// The caller has issued its loads and not yet used them.  Every lab[e] < KP.
+template <bool SUMS>
+__device__ __forceinline__ void hist_aggregate(const int (&lab)[4], const uint32_t (&rb)[4], const int nval, int KP, int T, int64_t *__restrict__ sums,
+                                               int32_t *__restrict__ flags, uint32_t *__restrict__ hist, const int b, const int t) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    unsigned long long *ssum = reinterpret_cast<unsigned long long *>(smem_raw);              // [KP] (SUMS only)
+    uint32_t *scnt = reinterpret_cast<uint32_t *>(SUMS ? smem_raw + (size_t)KP * 8 : smem_raw);  // [KP]
+    const int lane = threadIdx.x & 63;
     for (int k = threadIdx.x; k < KP; k += blockDim.x) {   // while the loads are in flight
         if constexpr (SUMS) ssum[k] = 0ull;
         scnt[k] = 0u;
@@ -3097,17 +3108,18 @@ static inline int scan_kp2(int M) { int v = 1; while (v < M + 2) v <<= 1; return
 // histogram + scan: tile x label counts (and the labels' range sums when ri is given), then the offsets of the ordered scatter, counts, nnz and
 // -- with `model` -- the point model's rows.  The sums / flags block must be zero (memset or BatchInit) before the sums are added: by the
 // histogram here, or -- summed = true -- by the assignment that wrote seg (launch_assign with lay.sums / lay.flags); the histogram is then
-// the count-only form, and ri serves the scan's sequential fallback alone (point_model_row).
+// the count-only form, and ri serves the scan's sequential fallback alone (point_model_row).  counted = true: no histogram launch at all.
 template <class L>
 static int launch_hist_scan(const float *ri, const L *seg, const double *ground, int B, int P, int M, const WsLayout &lay, float *model,
-                            int32_t *counts, int32_t *nnz, hipStream_t st, bool summed = false) {
+                            int32_t *counts, int32_t *nnz, hipStream_t st, bool summed = false, bool counted = false) {
     const int KP = kpad(M), T = ntiles(P);
     const bool hist_sums = ri != nullptr && !summed;
     const size_t sh = hist_lds_bytes(KP, hist_sums);
     const bool vec = hist_vec(P, seg, hist_sums ? ri : nullptr);
     // (The scan as the tail of the histogram kernel -- the frame's last workgroup to finish runs it -- was measured in round 4: a workgroup must
     // release its rows device-wide before it draws its ticket, and an agent-scope fence writes the XCD's L2 back: 62 us -> 2.9 ms.)
-    if (hist_sums) {
+    if (counted) {   // lay.hist holds the tile counts already, and lay.sums what `summed` says (labels_in_kernel wrote both with seg)
+    } else if (hist_sums) {
         if (vec) model_hist_kernel<true, L, true><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
         else     model_hist_kernel<false, L, true><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
     } else {
@@ -3128,10 +3140,11 @@ static int launch_hist_scan(const float *ri, const L *seg, const double *ground,
 // One workgroup per frame: label totals, tile offsets, label bases, means, model rows.
 template <class L>
 static int launch_point_model(const float *ri, const L *seg, const double *ground, int B, int P, int M,
-                              float *model, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared = false, bool summed = false) {
+                              float *model, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared = false, bool summed = false,
+                              bool counted = false) {
     const WsLayout lay = ws_layout(ws, B, P, M);
     if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
-    return launch_hist_scan(ri, seg, ground, B, P, M, lay, model, counts, nnz, st, summed);
+    return launch_hist_scan(ri, seg, ground, B, P, M, lay, model, counts, nnz, st, summed, counted);
 }
 
 template <class L>
@@ -3627,13 +3640,13 @@ extern "C" size_t rpcc_plane_workspace_bytes(int B, int P, int M) { return B > 0
 
 // hist / scan for a segmentation without the point sums: tile offsets (ordered scatter), counts, nnz
 template <class L>
-static int launch_label_scan(const L *seg, int B, int P, int M, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared) {
+static int launch_label_scan(const L *seg, int B, int P, int M, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared, bool counted = false) {
     const WsLayout lay = ws_layout(ws, B, P, M);
     // (Not a requirement of this scan: without ri and model neither kernel below adds to or reads sums / flags -- the results are the same
     // with the clear left out, tests/test_gpu_buffers.py::test_plane_model_workspace runs it on hostile contents.  It only keeps the block in
     // the state launch_hist_scan's comment asks for; launch_point_model's clear is the one that matters.)
     if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
-    return launch_hist_scan(nullptr, seg, nullptr, B, P, M, lay, nullptr, counts, nnz, st);
+    return launch_hist_scan(nullptr, seg, nullptr, B, P, M, lay, nullptr, counts, nnz, st, false, counted);
 }
 // plane rows from a segmentation whose tile offsets (launch_label_scan) are in ws; extra = the plane area (plane_layout).  Two launches:
 // the label-ordered lists, then the fits.
@@ -4142,6 +4155,82 @@ extern "C" int rpcc_decode_wide(const uint16_t *seg, const int16_t *q16, const f
     wide_decode_kernel<uint16_t><<<dim3((P + 255) / 256, B), 256, 0, st>>>(seg, q16, model, tm, w.pos, salience, steps, P, M + 2, ri_rec, pc_rec);
     LAUNCH_CHECK();
     return RPCC_OK;
+}
+
+// ================================================================================================
+// the batch from a caller's label map: rpcc_compress_batch_labels  (labels_in_kernel, labels_refuse_kernel: labels_kernels.h)
+// ================================================================================================
+#include "labels_kernels.h"
+
+// ws: [ model part | 256 | tile notes i32 [B,T] | (general) plane area | key points per label i32 [B,K] | label steps f32 [B,K] ]
+struct LabelsLayout { WsLayout L; int32_t *tile_bad, *kpn = nullptr; char *extra = nullptr; float *label_acc = nullptr; size_t bytes; };
+static LabelsLayout labels_layout(void *ws, int B, int P, int M, bool general) {
+    Carve c(ws);
+    LabelsLayout l;
+    l.L = ws_layout(ws, B, P, M); c.take(l.L.bytes); c.take(256);
+    l.tile_bad = c.take<int32_t>((size_t)B * ntiles(P) * 4);
+    if (general) {
+        const size_t ksz = round_up((size_t)B * (M + 2) * 4, 256);
+        l.extra = c.take(plane_layout(nullptr, B, P).bytes);
+        l.kpn = c.take<int32_t>(ksz); l.label_acc = c.take<float>(ksz);
+    }
+    l.bytes = round_up(c.bytes(), 256);
+    return l;
+}
+extern "C" size_t rpcc_labels_workspace_bytes(int B, int P, int M, int general) {
+    return B > 0 && P > 0 && M > 0 && M <= RPCC_MAX_CLUSTERS_MID ? labels_layout(nullptr, B, P, M, general != 0).bytes : 0;
+}
+
+template <class L>
+static int run_labels(const rpcc_labels_io *io, int B, rpcc_geom g, int M, float acc, void *ws, hipStream_t st) {
+    const int P = g.H * g.W, KP = kpad(M), T = ntiles(P), K = M + 2;
+    const bool point = io->model_method == 0;
+    const rpcc_nonuniform_cfg *nu = io->nonuniform;
+    const LabelsLayout l = labels_layout(ws, B, P, M, !point || nu != nullptr);
+    L *seg = reinterpret_cast<L *>(io->seg);
+    int rc;
+    // The intake accumulates the point model's sums and flags over a frame's tiles: they are cleared ahead of it (the one thing a kernel cannot
+    // do for itself); the key-point counters are cleared by the intake, the tile counts and notes are plain stores.
+    if (point) HIP_TRY(hipMemsetAsync(l.L.sums, 0, (size_t)((char *)l.L.hist - (char *)l.L.sums), st));
+    const ZeroRange zero = {reinterpret_cast<uint32_t *>(l.kpn), nu ? B * K : 0};
+    const bool vec = hist_vec(P, seg, point ? io->ri : nullptr) && aligned16(io->labels);
+    const size_t sh = hist_lds_bytes(KP, point);
+#define LABELS_IN(V_, S_) labels_in_kernel<V_, L, S_><<<dim3(T, B), 256, sh, st>>>(io->labels, io->max_label, io->ri, P, M, KP, T, seg, l.L.sums, l.L.flags, l.L.hist, l.tile_bad, zero)
+    if (point) { if (vec) LABELS_IN(true, true); else LABELS_IN(false, true); }
+    else       { if (vec) LABELS_IN(true, false); else LABELS_IN(false, false); }
+#undef LABELS_IN
+    LAUNCH_CHECK();
+    if (point) {   // the sums came with the labels, and so did the tile counts: the scan alone
+        if ((rc = launch_point_model(io->ri, seg, io->ground, B, P, M, io->model, io->counts, io->nnz, ws, st, true, true, true))) return rc;
+    } else {
+        if ((rc = launch_label_scan(seg, B, P, M, io->counts, io->nnz, ws, st, true, true))) return rc;
+        if ((rc = launch_label_order(io->ri, io->tm, seg, B, P, M, ws, l.extra, st))) return rc;
+        if ((rc = launch_plane_fits(io->tm, io->ground, B, P, M, io->plane_cos_cut, (uint32_t)io->plane_seed, io->frame_ids, io->model, io->counts, ws,
+                                    l.extra, st))) return rc;
+    }
+    if (nu) {
+        if ((rc = launch_features(io->ri, seg, B, g.H, g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num, nu->flat_num, nullptr,
+                                  io->key_point_map, st, l.kpn, K))) return rc;
+        if ((rc = launch_salience_levels<L>(io->counts, l.kpn, B, M, salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level),
+                                            io->salience, l.label_acc, st))) return rc;
+    }
+    if ((rc = launch_predict_quantize(io->ri, io->tm, seg, io->model, acc, nu ? l.label_acc : nullptr, nullptr, B, P, M, io->q16, nullptr, nullptr, ws, st))) return rc;
+    labels_refuse_kernel<L><<<dim3(T, B), 256, 0, st>>>(io->max_label, l.tile_bad, P, M, T, io->status, seg, io->model, io->counts, io->q16, io->nnz,
+                                                        nu ? io->salience : nullptr, nu ? io->key_point_map : nullptr);
+    LAUNCH_CHECK();
+    return RPCC_OK;
+}
+
+extern "C" int rpcc_compress_batch_labels(const rpcc_labels_io *io, int B, rpcc_geom g, int M, float acc, void *ws, void *stream) {
+    ARG_TRY(io != nullptr && ws != nullptr && B > 0 && B <= RPCC_MAX_BATCH && M > 0 && M <= RPCC_MAX_CLUSTERS_MID && g.H > 1 && g.W > 0);
+    ARG_TRY(io->ri && io->tm && io->ground && io->labels && io->max_label && io->seg && io->model && io->counts && io->q16 && io->nnz && io->status);
+    ARG_TRY(io->model_method == 0 || io->model_method == 1);
+    if (io->nonuniform) {
+        const rpcc_nonuniform_cfg *nu = io->nonuniform;
+        ARG_TRY(io->salience && io->key_point_map && nu->levels >= 1 && nu->levels <= 8 && nu->ground_level >= 0 && nu->ground_level < nu->levels);
+    }
+    if (M <= RPCC_MAX_CLUSTERS) return run_labels<uint8_t>(io, B, g, M, acc, ws, (hipStream_t)stream);
+    return run_labels<uint16_t>(io, B, g, M, acc, ws, (hipStream_t)stream);
 }
 
 // ================================================================================================

@@ -37,7 +37,7 @@ class _Slot:
         self.offs_dev = torch.zeros((B + 1,), dtype=torch.int64, device=device)
         self.fid_dev = torch.zeros((B,), dtype=torch.int64, device=device)
         self.ground = torch.zeros((B, 4), dtype=torch.float64, device=device)
-        self.buf = ops.BatchBuffers(B, bc.T.geom, bc.M, device, max_points=self.cap, general=bc.general)
+        self.buf = bc.new_buffers(B, max_points=self.cap)
         self.codec_ws = ops.codec_workspace(B, P, bc.M, device)
         # packed device payload + its pinned mirror: residuals (<= points), index sequence (<= pixels), bits, rows, lengths
         self.qp = torch.empty((self.cap,), dtype=torch.int16, device=device)
@@ -52,6 +52,7 @@ class _Slot:
         self.nseq_pin = torch.empty((B,), dtype=torch.int32).pin_memory()
         self.sal_pin = torch.empty((B, K), dtype=torch.uint8).pin_memory() if bc.general else None
         self.tot_pin = torch.zeros((2,), dtype=torch.int64).pin_memory()
+        self.status_pin = torch.zeros((B,), dtype=torch.int32).pin_memory() if bc.dbscan else None   # (rpcc_compress_batch_labels: refused frames)
         self.h2d_done = torch.cuda.Event()
         self.done = torch.cuda.Event()
         self.n = 0
@@ -198,10 +199,8 @@ class StreamingCompressor:
             slot.h2d_done.record(self.copy_stream)
         with torch.cuda.stream(self.compute_stream):
             self.compute_stream.wait_event(slot.h2d_done)
-            nu = None if bc.uniform else ops.nonuniform_cfg(bc.acc, bc.cfg)
-            ops.compress_batch(slot.xyz_dev[:npts], slot.offs_dev, bc.T.tm_dev, slot.ground, slot.buf, bc.ground_threshold, bc.acc,
-                               ground_seed=bc.seed, frame_ids=slot.fid_dev, model_method=bc.model_method,
-                               angle_threshold=bc.cfg.get("plane_angle_threshold", 75), plane_seed=bc.seed, nonuniform=nu)
+            # (FPS: one ops.compress_batch; DBSCAN: projection, ground fit, dbscan_segment, ops.compress_batch_labels)
+            bc.run_batch(slot.xyz_dev[:npts], slot.offs_dev, slot.ground, slot.buf, frame_ids=slot.fid_dev)
             bits, seq, nseq = ops.contour_encode(slot.buf.seg, bc.M, ws=slot.codec_ws)
             ops.pack_payload(slot.buf.q16, slot.buf.nnz, packed=slot.qp, capacity=slot.cap, total=slot.tot[0:1])
             ops.pack_payload(seq.view(torch.int16), nseq, packed=slot.sp, capacity=slot.sp.numel(), total=slot.tot[1:2])
@@ -214,6 +213,8 @@ class StreamingCompressor:
             slot.bits_pin.copy_(bits, non_blocking=True)
             slot.model_pin.copy_(slot.buf.model, non_blocking=True)
             slot.counts_pin.copy_(slot.buf.counts, non_blocking=True)
+            if slot.status_pin is not None:
+                slot.status_pin.copy_(slot.buf.status, non_blocking=True)
             if slot.sal_pin is not None and slot.buf.salience is not None:
                 slot.sal_pin.copy_(slot.buf.salience, non_blocking=True)
             slot.keep = (bits, seq, nseq)
@@ -223,6 +224,8 @@ class StreamingCompressor:
     def _collect(self, slot):
         slot.enq.result()                       # the enqueue thread has issued the batch (raises what it raised)
         slot.done.synchronize()
+        if slot.status_pin is not None:   # a frame DBSCAN gave more labels than max_labels (or a capped union-find): raise as collect() does
+            self.bc.check_status(slot.status_pin.numpy()[:slot.n])
         stot = int(slot.tot_pin[1])
         if stot > self.seq_eager:
             # an unusually long index sequence: the rest is fetched now, on a stream of its own (the compute stream already

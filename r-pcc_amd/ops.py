@@ -392,9 +392,17 @@ class BatchBuffers:
     """Device buffers of one batch (B frames, one geometry), allocated once and reused.  general=True adds what the
     plane model / the non-uniform framework need (salience levels, key-point map, the larger work buffer)."""
 
-    def __init__(self, B, geom, M, device, max_points=None, general=False):
+    def __init__(self, B, geom, M, device, max_points=None, general=False, labels=False):
+        """labels=True: the buffers of compress_batch_labels (the batch entered with a caller's label map) -- M is then its label cap
+        (<= RPCC_MAX_CLUSTERS_MID), ws the work buffer of that entry (rpcc_labels_workspace_bytes: no projection, no FPS) and status
+        i32 [B] its per-frame result.  Such buffers do not serve compress_batch."""
         M = check_cluster_num(M)
         self.wide = is_wide(M)     # uint16 labels, the rpcc_*_wide entries
+        self.labels = bool(labels)
+        self.labels_general = bool(general)
+        if labels and M > _lib.MAX_CLUSTERS_MID:
+            raise _lib.RpccError("label cap %d: compress_batch_labels takes labels up to RPCC_MAX_CLUSTERS_MID + 1 = %d (include/rpcc_hip.h)"
+                                 % (M + 1, _lib.MAX_CLUSTERS_MID + 1))
         general = general or self.wide   # (the wide entry serves every framework / model combination from one workspace)
         P = geom.H * geom.W
         K = M + 2
@@ -414,7 +422,11 @@ class BatchBuffers:
         # when a batch holds more (dense or dual-return sweeps), so the default no longer reserves twice that up front.
         self.max_points = int(max_points) if max_points is not None else B * P
         self.general = bool(general)
-        self.ws = workspace(B, P, M, device, self.max_points, general=self.general)
+        if labels:
+            self.ws = labels_workspace(B, P, M, device, general=self.labels_general)
+            self.status = torch.empty((B,), dtype=i32, device=device)
+        else:
+            self.ws = workspace(B, P, M, device, self.max_points, general=self.general)
         # (zeros, not empty: the library writes every level in the non-uniform framework and does not touch the tensor
         # in the uniform one, where consumers that copy it whole -- loader.StreamingCompressor's pinned copy, bench.py's
         # output dump -- then read defined bytes)
@@ -484,6 +496,40 @@ def compress_batch(xyz, offsets, tm, ground, buf, ground_threshold=0.1, acc=0.04
     return buf
 
 
+def labels_workspace(B, P, M, device, general=False):
+    """Work buffer of compress_batch_labels (rpcc_labels_workspace_bytes; needs no initialisation)."""
+    n = _lib.lib().rpcc_labels_workspace_bytes(B, P, M, 1 if general else 0)
+    if not n:
+        raise _lib.RpccError("rpcc_labels_workspace_bytes(%d, %d, %d): no such batch (label cap 1 .. %d)" % (B, P, M, _lib.MAX_CLUSTERS_MID))
+    return torch.empty((n + 255) // 256 * 256, dtype=torch.uint8, device=device)
+
+
+def compress_batch_labels(ri, tm, ground, labels, max_label, buf, acc=0.04, model_method="point", angle_threshold=75, plane_seed=0,
+                          frame_ids=None, nonuniform=None):
+    """a8..a13 for a batch whose segmentation the caller has (rpcc_compress_batch_labels): ri f32 [B,H,W], ground f64 [B,4], labels i32
+    [B,H,W] and max_label i32 [B] as dbscan.dbscan_segment returns them (ground 0, empty 1, noise 2, clusters from 3; -1 for a capped
+    frame).  buf: BatchBuffers(B, geom, M, device, general=..., labels=True) with M the label CAP (labels up to M + 1); its seg, model,
+    counts, q16, nnz (salience, key_point_map) are filled as compress_batch fills them.  -> buf.status i32 [B]: _lib.LABELS_OK, or
+    _lib.LABELS_E_RANGE / _lib.LABELS_E_CAPPED for a refused frame, whose rows are zero bytes.  Nothing is waited for."""
+    assert buf.labels, "BatchBuffers(..., labels=True) is needed"
+    general = model_method != "point" or nonuniform is not None
+    assert not general or buf.labels_general, "BatchBuffers(..., general=True) is needed for the plane model / non-uniform framework"
+    B, P = buf.B, buf.P
+    assert ri.dtype == torch.float32 and ri.numel() == B * P and labels.dtype == torch.int32 and labels.numel() == B * P
+    assert max_label.dtype == torch.int32 and max_label.numel() == B and ground.dtype == torch.float64 and ground.numel() == 4 * B
+    fid = _frame_ids(frame_ids, B, ri.device)
+    buf._frame_ids, buf._nonuniform = fid, nonuniform   # (alive until the stream has consumed them)
+    io = _lib.LabelsIO(ptr(ri).value, ptr(tm).value, ptr(ground).value, ptr(labels).value, ptr(max_label).value,
+                       ptr(fid).value if fid is not None else None, ptr(buf.seg).value, ptr(buf.model).value, ptr(buf.counts).value,
+                       ptr(buf.q16).value, ptr(buf.nnz).value, ptr(buf.status).value, 0 if model_method == "point" else 1,
+                       angle_cos_cut(angle_threshold) if model_method != "point" else 0.0, int(plane_seed),
+                       C.addressof(nonuniform) if nonuniform is not None else None,
+                       ptr(buf.salience).value if nonuniform is not None else None,
+                       ptr(buf.key_point_map).value if nonuniform is not None else None)
+    check(_lib.lib().rpcc_compress_batch_labels(C.byref(io), B, buf.geom, buf.M, float(acc), ptr(buf.ws), stream()))
+    return buf.status
+
+
 STAGE_PROJECT, STAGE_GROUND, STAGE_MASK, STAGE_FPS, STAGE_LABELS, STAGE_PLANES, STAGE_QUANTISE = (1 << i for i in range(7))
 
 
@@ -501,6 +547,7 @@ def _batch_io(xyz, offsets, tm, ground, buf, ground_seed=-1, frame_ids=None, fps
     """The rpcc_batch_io of one geometry group (compress_batch's arguments); grows the group's workspace when the batch holds more points."""
     general = model_method != "point" or nonuniform is not None
     assert not general or buf.general, "BatchBuffers(..., general=True) is needed for the plane model / non-uniform framework"
+    assert not buf.labels, "BatchBuffers(..., labels=True) serve compress_batch_labels only"
     if xyz.shape[0] > buf.max_points:
         buf.max_points = int(xyz.shape[0])
         buf.ws = workspace(buf.B, buf.P, buf.M, xyz.device, buf.max_points, general=buf.general)

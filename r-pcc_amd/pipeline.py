@@ -18,8 +18,22 @@ class BatchCompressor:
 
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
                  model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
-                 device_entropy=False, device_bzip2=False):
-        self.M = ops.check_cluster_num(cluster_num)   # (above 254: uint16 labels through the rpcc_*_wide entries; above 65533: refused by name)
+                 device_entropy=False, device_bzip2=False, segment_method="FPS", DBSCAN_eps=1.5, max_labels=None):
+        """segment_method "DBSCAN" (cfgs/compressor.yaml: segment_method, DBSCAN_eps): the frames are segmented by dbscan.dbscan_segment and
+        enter the batch kernels through ops.compress_batch_labels; cluster_num does not apply (tools/compress.py).  max_labels: the labels a
+        frame may use, 0 .. max_labels (default RPCC_MAX_CLUSTERS_MID + 1 = 1023, where the per-frame path raises too; up to 255: byte labels
+        on the device); a frame with more makes collect() raise."""
+        if segment_method not in ("FPS", "DBSCAN"):
+            raise ValueError("segment_method %r: FPS or DBSCAN" % (segment_method,))
+        self.segment_method, self.eps = segment_method, float(DBSCAN_eps)
+        if self.dbscan:
+            top = _lib.MAX_CLUSTERS_MID + 1 if max_labels is None else int(max_labels)
+            if not 2 <= top <= _lib.MAX_CLUSTERS_MID + 1:
+                raise _lib.RpccError("max_labels = %d: the batch kernels take labels up to 2 .. RPCC_MAX_CLUSTERS_MID + 1 = %d (include/rpcc_hip.h)"
+                                     % (top, _lib.MAX_CLUSTERS_MID + 1))
+            self.M = top - 1          # the label cap of rpcc_compress_batch_labels: labels 0 .. M + 1
+        else:
+            self.M = ops.check_cluster_num(cluster_num)   # (above 254: uint16 labels through the rpcc_*_wide entries; above 65533: refused by name)
         self.T = transformer
         self.device = torch.device(device) if device is not None else transformer.device
         self.acc = accuracy * 2                     # tools/compress.py:46
@@ -37,6 +51,50 @@ class BatchCompressor:
     def general(self):
         return not (self.uniform and self.model_method == "point")
 
+    @property
+    def dbscan(self):
+        return self.segment_method == "DBSCAN"
+
+    def new_buffers(self, B, max_points=None):
+        """The BatchBuffers run_batch fills for a batch of B frames (the streaming loader keeps one per slot)."""
+        return ops.BatchBuffers(B, self.T.geom, self.M, self.device, max_points=max_points, general=self.general, labels=self.dbscan)
+
+    def run_batch(self, xyz, offsets, ground, buf, frame_ids=None, fit_ground=True):
+        """The device work of one batch into buf, on the current stream, nothing waited for.  ground f64 [B,4]: fitted here (fit_ground: the
+        seeded RANSAC, frame b drawing with seed + frame_ids[b]) or the caller's.  FPS: one ops.compress_batch.  DBSCAN: ops.project (packed
+        xyz or the stored 16-byte rows), ops.ground_ransac with the per-frame path's seed and identities, dbscan_segment(min_points = 10,
+        as the reference hard-codes it) without the read-back of its max_label, then ops.compress_batch_labels, whose per-frame status
+        (buf.status) collect() reads."""
+        nu = None if self.uniform else ops.nonuniform_cfg(self.acc, self.cfg)
+        angle = self.cfg.get("plane_angle_threshold", 75)
+        if not self.dbscan:
+            ops.compress_batch(xyz, offsets, self.T.tm_dev, ground, buf, self.ground_threshold, self.acc,
+                               ground_seed=self.seed if fit_ground else -1, frame_ids=frame_ids, model_method=self.model_method,
+                               angle_threshold=angle, plane_seed=self.seed, nonuniform=nu)
+            return
+        from .dbscan import dbscan_segment
+        tm = self.T.tm_dev
+        ops.project(xyz, offsets, self.T.geom, ri=buf.ri)
+        if fit_ground:
+            g, _ = ops.ground_ransac(buf.ri, tm, seed=self.seed, frame_ids=frame_ids)
+            ground.copy_(g)
+        labels, top = dbscan_segment(buf.ri, tm, ground, self.eps, min_points=10, check=False)
+        ops.compress_batch_labels(buf.ri, tm, ground, labels, top, buf, self.acc, model_method=self.model_method, angle_threshold=angle,
+                                  plane_seed=self.seed, frame_ids=frame_ids, nonuniform=nu)
+
+    def check_status(self, status):
+        """status: a batch's buf.status on the host (None for FPS).  Raises RpccError naming the refused frames (their places in the batch)
+        and the label limit, in the words of PointCloudSegment._dbscan and dbscan_segment."""
+        if status is None or not np.any(status):
+            return
+        bad = [int(i) for i in np.flatnonzero(status)]
+        capped = [int(i) for i in np.flatnonzero(np.asarray(status) == _lib.LABELS_E_CAPPED)]
+        if capped:
+            raise _lib.RpccError("librpcc_seg: a union-find loop hit its iteration cap (frames %s)" % (capped,))
+        raise _lib.RpccError("DBSCAN found labels above %d in frames %s: the batch kernels take labels up to max_labels = %d (at most "
+                             "RPCC_MAX_CLUSTERS_MID + 1 = %d, include/rpcc_hip.h); use a larger DBSCAN_eps"
+                             % (self.M + 1, bad, self.M + 1, _lib.MAX_CLUSTERS_MID + 1))
+
     def _buffers(self, B):
         """Output buffers for a batch of B frames: the first set no submit() holds (collect() reads a batch's counts, models, salience and
         contour bits from them, so a second submit() before the first collect() must not land in the same set); at most SLOTS sets per
@@ -46,7 +104,7 @@ class BatchCompressor:
         if buf is None:
             if len(ring) >= self.SLOTS:
                 raise RuntimeError("BatchCompressor: %d batches submitted and not collected; collect() one before the next submit()" % len(ring))
-            buf = ops.BatchBuffers(B, self.T.geom, self.M, self.device, general=self.general)
+            buf = self.new_buffers(B)
             buf.codec_ws = ops.codec_workspace(B, self.T.H * self.T.W, self.M, self.device)
             buf.in_flight = False
             ring.append(buf)
@@ -75,6 +133,11 @@ class BatchCompressor:
         """Device part.  xyz f32 [sum N,3], offsets i64 [B+1] on the device.  Returns the BatchBuffers plus
         contour bits / index sequences (and salience for the non-uniform framework), all still in HBM.
         frame_ids: stable identities of the frames (utils.frame_identity) for the seeded plane fits."""
+        if self.dbscan:
+            buf = self._buffers(offsets.numel() - 1)
+            g = torch.zeros((buf.B, 4), dtype=torch.float64, device=self.device) if ground is None else ground
+            self.run_batch(xyz, offsets, g, buf, frame_ids, fit_ground=ground is None)
+            return self._encode(dict(buf=buf, ground=g))
         args = self._group_args(xyz, offsets, ground, frame_ids)
         ops.compress_batch(ground_threshold=self.ground_threshold, acc=self.acc, **args)
         return self._encode(args)
@@ -151,8 +214,10 @@ class BatchCompressor:
             qo, so = np.concatenate([[0], np.cumsum(nnz)]), np.concatenate([[0], np.cumsum(nseq_h)])
             bits_h, model = bits.cpu().numpy(), buf.model.cpu().numpy()
             sal_h = None if sal is None else sal.cpu().numpy()
+            status = buf.status.cpu().numpy() if self.dbscan else None
         finally:
             buf.in_flight = False   # everything collect() needs is on the host -- or the call failed: either way the slot is free again
+        self.check_status(status)
         def assemble(b):
             nrow = int(np.flatnonzero(seg_max[b])[-1]) + 1          # max(seg)+1 rows (tools/compress.py:102)
             od = {"residual_quantized": q16[qo[b]: qo[b + 1]]}
@@ -175,8 +240,10 @@ class BatchCompressor:
         try:
             ctx["stream"].synchronize()
             fr = frame.cpu().numpy()
+            status = ctx["buf"].status.cpu().numpy() if self.dbscan else None
         finally:
             ctx["buf"].in_flight = False
+        self.check_status(status)
         n = ctx["n"]
         if (fr[1, :n] < 0).any():
             raise RuntimeError("rpcc_lz4: the containers of frames %s were not built" % np.flatnonzero(fr[1, :n] < 0).tolist())
@@ -209,6 +276,9 @@ class MixedBatchCompressor:
                                     # keeps that many buffer sets, a further submit() before a collect() raises
 
     def __init__(self, transformers, **kw):
+        if kw.get("segment_method", "FPS") != "FPS":
+            raise NotImplementedError("MixedBatchCompressor: segment_method %r -- the mixed-geometry call runs FPS only; DBSCAN: one "
+                                      "BatchCompressor(segment_method='DBSCAN') per lidar" % (kw["segment_method"],))
         self.bcs = {name: BatchCompressor(t, **kw) for name, t in transformers.items()}
         first = next(iter(self.bcs.values()))
         self.device, self.ground_threshold, self.acc = first.device, first.ground_threshold, first.acc
@@ -275,15 +345,23 @@ class BatchDecompressor:
     one ops.decompress_batch checks and decodes the frames (status per frame: _lib.STREAM_E_*).  accuracy / level_acc / uniform are
     tools/decompress.py:decode_frame's arguments, and its results are this class's, bit for bit.  The device decoders are used whatever the
     device_entropy / device_bunzip2 flags of a BasicCompressor handed in say: those govern the per-frame path.
-    DBSCAN streams size their label count per frame: they stay on decode_frame."""
+    DBSCAN streams size their label count per frame (cluster_num=None, as decode_frame takes it): with max_labels=N they are decoded under the
+    label cap N - 1 -- rpcc_decompress_batch takes a frame's row count from its plane payload -- with decode_frame(..., None, ...)'s refusals; a
+    frame with more rows than the cap is decoded once more through decode_frame.  Label maps come back in the cap's dtype."""
 
     CHUNK_FRAMES = 32              # frames per chunk at most, as the datalist tool reads them
     CHUNK_BUDGET_BYTES = 2 << 30   # device bytes one chunk may take: padded payloads, bzip2 work slots, work buffer and outputs
 
-    def __init__(self, transformer, cluster_num, accuracy, uniform=True, level_acc=None, basic_compressor="bzip2"):
+    def __init__(self, transformer, cluster_num, accuracy, uniform=True, level_acc=None, basic_compressor="bzip2", max_labels=None):
+        self.per_frame_rows = cluster_num is None     # DBSCAN streams
         if cluster_num is None:
-            raise ValueError("BatchDecompressor: cluster_num=None (a DBSCAN stream sizes its label count per frame): decode such streams with "
-                             "tools.decompress.decode_frame")
+            if max_labels is None:
+                raise ValueError("BatchDecompressor: cluster_num=None (a DBSCAN stream sizes its label count per frame) needs max_labels, the "
+                                 "label cap of the batch (1023 at most); or decode such streams with tools.decompress.decode_frame")
+            if not 2 <= int(max_labels) <= _lib.MAX_CLUSTERS_MID + 1:
+                raise _lib.RpccError("max_labels = %d: 2 .. RPCC_MAX_CLUSTERS_MID + 1 = %d" % (int(max_labels), _lib.MAX_CLUSTERS_MID + 1))
+            cluster_num = int(max_labels) - 1
+        self.cluster_num = None if self.per_frame_rows else cluster_num   # what decode_frame is given
         self.M = ops.check_cluster_num(cluster_num)
         self.T, self.device = transformer, transformer.device
         self.accuracy, self.uniform = accuracy, bool(uniform)
@@ -391,6 +469,15 @@ class BatchDecompressor:
                              H, W, salience=sal, out=out)
         if len(bad):
             out[0][meta[6 * n + len(sound): 6 * n + B]] = _lib.STREAM_E_CONTAINER
+        if self.per_frame_rows and not self.uniform:
+            # decode_frame(..., None, ...) sizes K from the frame: max(rows, 3).  A salience payload longer than that is refused there, although it
+            # fits the cap's K -- ahead of the residual check, behind all others (rpcc_decompress_batch's order)
+            st = out[0]
+            late = ((st == _lib.STREAM_OK) | (st == _lib.STREAM_E_RESIDUAL)) & (plen[:, 0] > torch.clamp(plen[:, 3] // 16, min=3))
+            st.masked_fill_(late, _lib.STREAM_E_SALIENCE)
+            for o in out[1:]:
+                if o is not None:   # a refused frame's rows are zero (uint16 label maps: through their int16 view)
+                    (o.view(torch.int16) if o.dtype == torch.uint16 else o).masked_fill_(late.view((B,) + (1,) * (o.dim() - 1)), 0)
 
     def upload(self, blobs):
         """The containers' bytes on the device, a chunk per copy, for decompress_device(blobs, uploaded=...): callers that hold the containers
@@ -425,10 +512,10 @@ class BatchDecompressor:
                 if st == _lib.STREAM_OK:
                     res.append((rec[i], pc[i] if pc is not None else None, seg[i]))
                     continue
-                if st != _lib.STREAM_E_ENTROPY:
+                if st != _lib.STREAM_E_ENTROPY and not (st == _lib.STREAM_E_PLANE and self.per_frame_rows):   # (more rows than the cap: per frame)
                     raise ValueError("frame %d: %s (status %d)" % (c0 + i, STREAM_TEXT.get(int(st), "refused"), int(st)))
                 try:
-                    res.append(decode_frame(unpack_bitstream(part[i], self.uniform), self.host_bc, self.T, self.M, self.accuracy,
+                    res.append(decode_frame(unpack_bitstream(part[i], self.uniform), self.host_bc, self.T, self.cluster_num, self.accuracy,
                                             self.level_acc, self.uniform, want_points=want_points))
                 except (ValueError, OSError, EOFError) as e:
                     raise ValueError("frame %d: %s" % (c0 + i, e)) from e

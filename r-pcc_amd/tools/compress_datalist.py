@@ -104,7 +104,9 @@ def compress(args, streaming_factory=None):
                          ground_threshold=segment_cfg["ground_vertical_threshold"], uniform=uniform,
                          model_method=model_cfg["model_method"], compressor_cfg=dict(cfg),
                          basic_compressor=basic_compressor.method_name, seed=args.seed,
-                         device_entropy=basic_compressor.device_entropy, device_bzip2=basic_compressor.device_bzip2)
+                         device_entropy=basic_compressor.device_entropy, device_bzip2=basic_compressor.device_bzip2,
+                         segment_method=segment_cfg["segment_method"], DBSCAN_eps=segment_cfg["DBSCAN_eps"],
+                         max_labels=getattr(args, "max_labels", None))
     mine = shard_indices(len(dataset), rank, world)
     # the ingest mode follows from the WHOLE datalist -- the same decision on every rank, also on one whose shard is empty -- and is
     # settled before the process group forms, so that a datalist --ingest rows cannot take fails on all ranks together

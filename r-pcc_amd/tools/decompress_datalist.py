@@ -30,7 +30,10 @@ def output_path(args, name):
 def decompress_batched(args, dataset, mine, cluster_num, accuracy, level_acc, uniform, basic_compressor):
     """--batch_decode: the chunks through pipeline.BatchDecompressor (the files' bytes as they are, one device pass per chunk)."""
     from rpcc_amd.pipeline import BatchDecompressor
-    bd = BatchDecompressor(dataset.PCTransformer, cluster_num, accuracy, uniform=uniform, level_acc=level_acc, basic_compressor=basic_compressor)
+    # (DBSCAN streams: cluster_num None -- the label count is the frame's; the batch decodes them under a label cap)
+    cap = (getattr(args, "max_labels", None) or 1023) if cluster_num is None else None
+    bd = BatchDecompressor(dataset.PCTransformer, cluster_num, accuracy, uniform=uniform, level_acc=level_acc, basic_compressor=basic_compressor,
+                           max_labels=cap)
     for c0 in range(0, len(mine), CHUNK):
         names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
         blobs = []

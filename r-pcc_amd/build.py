@@ -29,6 +29,7 @@ DEFLATE_SRC, DEFLATE_DEPS, DEFLATE_LIB = _side_library("csrc_deflate", "deflate_
 INFLATE_SRC, INFLATE_DEPS, INFLATE_LIB = _side_library("csrc_inflate", "inflate_kernels.hip", "rpcc_inflate.h", "librpcc_inflate.so")   # gzip decoder
 BUNZIP2_SRC, BUNZIP2_DEPS, BUNZIP2_LIB = _side_library("csrc_bunzip2", "bunzip2_kernels.hip", "rpcc_bunzip2.h", "librpcc_bunzip2.so")   # bzip2 decoder
 BZIP2_SRC, BZIP2_DEPS, BZIP2_LIB = _side_library("csrc_bzip2", "bzip2_kernels.hip", "rpcc_bzip2.h", "librpcc_bzip2.so")   # bzip2 encoder
+FILTER_SRC, FILTER_DEPS, FILTER_LIB = _side_library("csrc_filter", "radius_filter.hip", "rpcc_filter.h", "librpcc_filter.so")   # radius outlier removal
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -109,6 +110,11 @@ def build_bzip2(force=False, verbose=False):
     return _hipcc(BZIP2_SRC, BZIP2_LIB, BZIP2_DEPS, force, verbose)
 
 
+def build_filter(force=False, verbose=False):
+    """librpcc_filter.so: the radius outlier removal kernels (csrc_filter/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(FILTER_SRC, FILTER_LIB, FILTER_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -121,6 +127,7 @@ def build(force=False, verbose=False):
     build_inflate(force, verbose)
     build_bunzip2(force, verbose)
     build_bzip2(force, verbose)
+    build_filter(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

@@ -1,7 +1,8 @@
 """Data access -- mirror of the reference's dataset/__init__.py:52-69 (build_dataset) and
 dataset/dataset.py (DatasetTemplate): .bin / .npy / .txt readers, the lidar registry and the
-range-image loader.  Dataset-specific converters (dataset/datasets/*.py) and the Open3D formats
-(.ply/.pcd read, .pcd write) are out of scope."""
+range-image loader.  use_radius_outlier_removal (dataset/dataset.py:29-35, Open3D's remove_radius_outlier(nb_points=3,
+radius=1)) runs on the GPU through outlier.remove_radius_outlier (librpcc_filter.so).  Dataset-specific
+converters (dataset/datasets/*.py) and the Open3D formats (.ply/.pcd read, .pcd write) are out of scope."""
 import os
 import struct
 
@@ -33,8 +34,8 @@ class DatasetTemplate:
         if datalist is not None:
             with open(datalist, "r") as f:
                 self.data_list = [line.strip() for line in f if line.strip()]
-        if use_radius_outlier_removal:
-            raise NotImplementedError("radius outlier removal needs Open3D (out of scope)")
+        self.use_radius_outlier_removal = bool(use_radius_outlier_removal)
+        self.device = device
         if dataset_cfg is not None:
             self.dataset_cfg = dataset_cfg
             self.PCTransformer = PCTransformer(dataset_cfg, channel_distribute_csv, device=device)
@@ -44,8 +45,16 @@ class DatasetTemplate:
         return len(self.data_list)
 
     def __getitem__(self, index):
+        """dataset/dataset.py:26-41: with use_radius_outlier_removal the range image and the point cloud come from the filtered points
+        (nb_points=3, radius=1); the original point cloud is returned unfiltered."""
         file_name = self.data_list[index]
-        point_cloud, range_image, original = self.load_range_image_points_from_file(file_name)
+        original = self.load_data(file_name)
+        point_cloud = original
+        if self.use_radius_outlier_removal:
+            from .outlier import remove_radius_outlier   # raises RpccError without a visible GPU
+            point_cloud, _ = remove_radius_outlier(original, nb_points=3, radius=1, device=self.device)
+        range_image = np.expand_dims(self.PCTransformer.point_cloud_to_range_image(point_cloud), -1)
+        point_cloud = self.PCTransformer.range_image_to_point_cloud(range_image)
         return point_cloud, range_image, original, file_name
 
     @staticmethod

@@ -18,11 +18,21 @@ class BatchCompressor:
 
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
                  model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
-                 device_entropy=False, device_bzip2=False, segment_method="FPS", DBSCAN_eps=1.5, max_labels=None):
+                 device_entropy=False, device_bzip2=False, segment_method="FPS", DBSCAN_eps=1.5, max_labels=None,
+                 radius_outlier_removal=None):
         """segment_method "DBSCAN" (cfgs/compressor.yaml: segment_method, DBSCAN_eps): the frames are segmented by dbscan.dbscan_segment and
         enter the batch kernels through ops.compress_batch_labels; cluster_num does not apply (tools/compress.py).  max_labels: the labels a
         frame may use, 0 .. max_labels (default RPCC_MAX_CLUSTERS_MID + 1 = 1023, where the per-frame path raises too; up to 255: byte labels
-        on the device); a frame with more makes collect() raise."""
+        on the device); a frame with more makes collect() raise.
+        radius_outlier_removal: None, or (nb_points, radius) -- the reference's use_radius_outlier_removal is (3, 1.0): every frame's points go
+        through outlier.radius_outlier_mask first and the removed ones enter the projection as NaN, which it skips: the containers are those
+        of the compacted frames, with no compaction, no new point count and no read-back in between."""
+        self.outlier = None
+        if radius_outlier_removal is not None:
+            nb_points, radius = radius_outlier_removal
+            if int(nb_points) < 0 or not float(radius) > 0:
+                raise ValueError("radius_outlier_removal = %r: (nb_points >= 0, radius > 0)" % (radius_outlier_removal,))
+            self.outlier = (int(nb_points), float(radius))
         if segment_method not in ("FPS", "DBSCAN"):
             raise ValueError("segment_method %r: FPS or DBSCAN" % (segment_method,))
         self.segment_method, self.eps = segment_method, float(DBSCAN_eps)
@@ -59,6 +69,14 @@ class BatchCompressor:
         """The BatchBuffers run_batch fills for a batch of B frames (the streaming loader keeps one per slot)."""
         return ops.BatchBuffers(B, self.T.geom, self.M, self.device, max_points=max_points, general=self.general, labels=self.dbscan)
 
+    def _filtered(self, xyz, offsets):
+        """radius_outlier_removal: a copy of the points (packed xyz or the stored 16-byte rows alike) in which x, y, z of every removed point
+        are NaN; without the option the points themselves, and nothing reaches librpcc_filter.so."""
+        if self.outlier is None:
+            return xyz
+        from .outlier import radius_outlier_mask
+        return radius_outlier_mask(xyz, offsets, self.outlier[0], self.outlier[1], masked=True).masked
+
     def run_batch(self, xyz, offsets, ground, buf, frame_ids=None, fit_ground=True):
         """The device work of one batch into buf, on the current stream, nothing waited for.  ground f64 [B,4]: fitted here (fit_ground: the
         seeded RANSAC, frame b drawing with seed + frame_ids[b]) or the caller's.  FPS: one ops.compress_batch.  DBSCAN: ops.project (packed
@@ -67,6 +85,7 @@ class BatchCompressor:
         (buf.status) collect() reads."""
         nu = None if self.uniform else ops.nonuniform_cfg(self.acc, self.cfg)
         angle = self.cfg.get("plane_angle_threshold", 75)
+        xyz = self._filtered(xyz, offsets)
         if not self.dbscan:
             ops.compress_batch(xyz, offsets, self.T.tm_dev, ground, buf, self.ground_threshold, self.acc,
                                ground_seed=self.seed if fit_ground else -1, frame_ids=frame_ids, model_method=self.model_method,
@@ -138,7 +157,7 @@ class BatchCompressor:
             g = torch.zeros((buf.B, 4), dtype=torch.float64, device=self.device) if ground is None else ground
             self.run_batch(xyz, offsets, g, buf, frame_ids, fit_ground=ground is None)
             return self._encode(dict(buf=buf, ground=g))
-        args = self._group_args(xyz, offsets, ground, frame_ids)
+        args = self._group_args(self._filtered(xyz, offsets), offsets, ground, frame_ids)
         ops.compress_batch(ground_threshold=self.ground_threshold, acc=self.acc, **args)
         return self._encode(args)
 
@@ -279,6 +298,9 @@ class MixedBatchCompressor:
         if kw.get("segment_method", "FPS") != "FPS":
             raise NotImplementedError("MixedBatchCompressor: segment_method %r -- the mixed-geometry call runs FPS only; DBSCAN: one "
                                       "BatchCompressor(segment_method='DBSCAN') per lidar" % (kw["segment_method"],))
+        if kw.get("radius_outlier_removal") is not None:
+            raise NotImplementedError("MixedBatchCompressor: radius_outlier_removal -- the mixed-geometry call takes the points as they are; "
+                                      "filter them first (outlier.radius_outlier_mask), or use one BatchCompressor per lidar")
         self.bcs = {name: BatchCompressor(t, **kw) for name, t in transformers.items()}
         first = next(iter(self.bcs.values()))
         self.device, self.ground_threshold, self.acc = first.device, first.ground_threshold, first.acc

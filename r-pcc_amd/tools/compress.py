@@ -67,6 +67,9 @@ def make_parser(datalist=False):
     p.add_argument("--model_method", type=str, default=None, help="for manual setting.")
     p.add_argument("--angle_threshold", type=float, default=None, help="for manual setting.")
     p.add_argument("--nonuniform", action="store_true", help="for manual setting.")
+    p.add_argument("--use_radius_outlier_removal", action="store_true",
+                   help="remove the points with at most 3 others within 1 m before the projection (the reference's use_radius_outlier_removal, "
+                        "Open3D remove_radius_outlier(nb_points=3, radius=1); here on the GPU).")
     p.add_argument("--eval", action="store_true", help="evaluate the reconstruction quality.")
     p.add_argument("--cpu", action="store_true", help="accepted for compatibility; the HIP path has no CPU mode.")
     p.add_argument("--seed", type=int, default=0, help="seed of the ground / plane RANSAC (this build).")
@@ -137,6 +140,9 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
     dataset = build_dataset(lidar_type=args.lidar)
     t0 = time.time()
     frame = dataset.load_data(args.input)
+    if getattr(args, "use_radius_outlier_removal", False):
+        from rpcc_amd.outlier import remove_radius_outlier
+        frame, _ = remove_radius_outlier(frame, nb_points=3, radius=1)
     bc = BatchCompressor(dataset.PCTransformer, cluster_num=segment_cfg["cluster_num"], accuracy=accuracy / 2,
                          ground_threshold=segment_cfg["ground_vertical_threshold"], uniform=uniform, model_method=model_cfg["model_method"],
                          compressor_cfg=dict(cfg), basic_compressor=basic_compressor.method_name, seed=args.seed,
@@ -178,12 +184,17 @@ def compress(args):
     # DBSCAN: always the per-frame stages here (compress_datalist.py batches it: pipeline.BatchCompressor(segment_method="DBSCAN")); cluster_num does not apply
     if segment_cfg["segment_method"] != "DBSCAN" and ops.is_wide(ops.check_cluster_num(segment_cfg["cluster_num"])):
         return compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform)
-    dataset = build_dataset(lidar_type=args.lidar)
+    filtered = getattr(args, "use_radius_outlier_removal", False)
+    dataset = build_dataset(lidar_type=args.lidar, use_radius_outlier_removal=filtered)
     model_num = segment_cfg["cluster_num"] + 1
     pc_seg = PointCloudSegment(dataset.transform_map, seed=args.seed, frame_id=frame_identity(args.input))
 
     t_init = time.time()
-    point_cloud, range_image, original_point_cloud = dataset.load_range_image_points_from_file(args.input)
+    if filtered:     # filtered per frame through the dataset (dataset/dataset.py:26-41)
+        dataset.data_list = [args.input]
+        point_cloud, range_image, original_point_cloud, _ = dataset[0]
+    else:
+        point_cloud, range_image, original_point_cloud = dataset.load_range_image_points_from_file(args.input)
     point_num = int((point_cloud[..., 0] != 0).sum())
     t_load_data = time.time()
     seg_idx, ground_model = pc_seg.segment(point_cloud, range_image, segment_cfg, cpu=args.cpu)

@@ -106,7 +106,8 @@ def compress(args, streaming_factory=None):
                          basic_compressor=basic_compressor.method_name, seed=args.seed,
                          device_entropy=basic_compressor.device_entropy, device_bzip2=basic_compressor.device_bzip2,
                          segment_method=segment_cfg["segment_method"], DBSCAN_eps=segment_cfg["DBSCAN_eps"],
-                         max_labels=getattr(args, "max_labels", None))
+                         max_labels=getattr(args, "max_labels", None),
+                         radius_outlier_removal=(3, 1.0) if getattr(args, "use_radius_outlier_removal", False) else None)
     mine = shard_indices(len(dataset), rank, world)
     # the ingest mode follows from the WHOLE datalist -- the same decision on every rank, also on one whose shard is empty -- and is
     # settled before the process group forms, so that a datalist --ingest rows cannot take fails on all ranks together

@@ -44,7 +44,8 @@ extern "C" {
 
 /* Caller's buffers (held by tests/test_gpu_buffers.py: exact sizes, hostile contents, guard bytes around them).
  * Work buffers -- `ws`, `scratch`, `fps_table`, sized by rpcc_workspace_bytes[_general], rpcc_wide_workspace_bytes,
- * rpcc_project_scratch_bytes, rpcc_fps_table_bytes, rpcc_plane_workspace_bytes, rpcc_codec_workspace_bytes, rpcc_decompress_workspace_bytes, rpcc_labels_workspace_bytes -- need NO initialisation: they
+ * rpcc_project_scratch_bytes, rpcc_fps_table_bytes, rpcc_plane_workspace_bytes, rpcc_codec_workspace_bytes, rpcc_decompress_workspace_bytes, rpcc_labels_workspace_bytes,
+ * rpcc_project_beams_scratch_bytes, rpcc_compress_batch_beams_workspace_bytes -- need NO initialisation: they
  * may hold anything, including what an earlier call left there under other arguments (another B, P, M, point count or entry point), and a
  * buffer larger than asked for may be handed to calls of different shapes in turn.  Every entry clears or overwrites what it reads; the
  * fused batch compares its per-frame projection flags with a mark kept inside ws, and a stale word that happens to equal the mark only
@@ -111,6 +112,38 @@ int rpcc_project(const float *xyz, const int64_t *offsets, int64_t total, int B,
  * 16-byte row per point (points 16-byte aligned); 12 (or 0) = packed xyz = rpcc_project.  offsets / total count POINTS. */
 int rpcc_project_strided(const float *points, int point_stride_bytes, const int64_t *offsets, int64_t total, int B,
                          rpcc_geom g, float *ri, void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---- a2 through a per-beam elevation table ---------------------------------------------------- *
+ * replaces the channel_distribute_csv branch of PCTransformer.point_cloud_to_range_image (dataset/transformer.py:13-22,68-91),
+ * batched: the lidars whose beams are not evenly spaced in elevation.  Row h of the image is entry h of the table (radians, f64;
+ * any order, equal entries allowed).  Per point, in input order (the specification is stated once, in tests/beam_table_ref.py):
+ *   depth = sqrtf(x*x + y*y + z*z); a point whose depth is not finite is skipped
+ *   az = atan2f(y, x), + (float)(2 pi) in fp32 when negative;  col = rintf(az / horizontal_fov * W) (half to even) mod W
+ *   el = atan2f(z, sqrtf(x*x + y*y));  row = the FIRST minimum over h of |table[h] - (double)el| in fp64
+ *   ri[row, col] = depth: the LAST point in input order wins its pixel (a depth-0 point that comes last leaves 0); empty pixels are 0
+ * (added under interface version 105, as rpcc_compress_batch_labels was: no existing struct or argument changes)
+ *
+ * The index: built on the host (pure C: no device call, no allocation) into `out`, rpcc_beam_index_bytes(H) bytes, 8-byte aligned;
+ * the caller uploads it once per lidar and passes the device copy (8-byte aligned) as beams_dev.  It holds the table in row order,
+ * the table sorted, the fp32 midpoints of neighbouring sorted entries and the sorted-position -> row map (equal entries: the lowest
+ * row); layout in csrc/beam_index.h.  1 <= H <= 128 and every entry finite, or RPCC_ERR_ARG (rpcc_beam_index_bytes: 0).  An index
+ * must be used with the H it was built for.
+ *   geom     H, W and horizontal_fov (> 0) are used; vertical_max / vertical_min are ignored
+ *   points   packed xyz (point_stride_bytes 0 or 12) or the stored 16-byte rows, as for rpcc_project_strided; total < 2^31
+ *   scratch  dev, rpcc_project_beams_scratch_bytes(total, B, P) bytes (4 per pixel + 4 per point); needs no initialisation
+ * The pixel of a point comes from a screened fast path (the elevation located among the fp32 midpoints) and is recomputed by the
+ * exact sequence above whenever it is not provably the same.
+ * rpcc_project_beams_check (test hook; packed xyz): counts dev u64[3] = {points the fast path is certain about, of those the ones
+ * the exact sequence skips or puts into another pixel (must be 0), points sent to the exact sequence}. */
+#ifndef RPCC_BEAM_MAX_H
+#define RPCC_BEAM_MAX_H 128 /* rows of a per-beam elevation table */
+#endif
+size_t rpcc_beam_index_bytes(int H);
+int rpcc_beam_index_build(const double *angles, int H, void *out);
+size_t rpcc_project_beams_scratch_bytes(int64_t total, int B, int P);
+int rpcc_project_beams(const float *points, int point_stride_bytes, const int64_t *offsets, int64_t total, int B, rpcc_geom g,
+                       const void *beams_dev, float *ri, void *scratch, size_t scratch_bytes, void *stream);
+int rpcc_project_beams_check(const float *xyz, int64_t total, rpcc_geom g, const void *beams_dev, uint64_t *counts, void *stream);
 
 /* ---- a4: ground plane ----------------------------------------------------------------------- *
  * replaces the ground branch of PointCloudSegment.segment: candidate selection + RANSAC
@@ -345,6 +378,16 @@ size_t rpcc_workspace_bytes(int B, int P, int M, int64_t total_points);
 size_t rpcc_workspace_bytes_general(int B, int P, int M, int64_t total_points); /* plane model and / or non-uniform framework */
 int rpcc_compress_batch(const rpcc_batch_io *io, int B, rpcc_geom g, int M, double ground_threshold, float acc,
                         void *ws, void *stream);
+
+/* rpcc_compress_batch with the projection stage replaced by rpcc_project_beams (beams_dev: the device copy of the index built for g.H);
+ * everything behind the projection reads io->ri and io->tm -- the ray table built from the same elevation table -- and is unchanged:
+ * all four framework / model combinations, byte labels up to RPCC_MAX_CLUSTERS clusters and uint16 labels (io->seg) up to
+ * RPCC_MAX_CLUSTERS_MID.  ws: rpcc_compress_batch_beams_workspace_bytes(B, P, M, total_points, general) bytes (general != 0: plane
+ * model and / or non-uniform framework; 0 for a batch this entry does not take).  The mixed-geometry call and cluster counts above
+ * RPCC_MAX_CLUSTERS_MID have no table form. */
+size_t rpcc_compress_batch_beams_workspace_bytes(int B, int P, int M, int64_t total_points, int general);
+int rpcc_compress_batch_beams(const rpcc_batch_io *io, int B, rpcc_geom g, const void *beams_dev, int M, double ground_threshold,
+                              float acc, void *ws, void *stream);
 
 /* A subset of rpcc_compress_batch's stages, in order: bit 0 projection, 1 ground fit, 2 mask (+ first FPS pass), 3 FPS, 4 assignment + label histograms +
  * scan (+ the plane model's label order), 5 plane fits, 6 key points + salience + quantiser.  For callers that interleave the stages of several batches on

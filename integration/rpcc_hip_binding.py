@@ -29,7 +29,8 @@ RPCC_ABI_VERSION = 105      # include/rpcc_hip.h: the structs carry no size fiel
 if _l.rpcc_version() != RPCC_ABI_VERSION:
     raise ImportError("librpcc_hip.so reports interface version %d, this binding was written for %d" % (_l.rpcc_version(), RPCC_ABI_VERSION))
 _l.rpcc_last_error.restype = C.c_char_p
-for _n in ("rpcc_workspace_bytes", "rpcc_project_scratch_bytes", "rpcc_fps_table_bytes", "rpcc_codec_workspace_bytes"):
+for _n in ("rpcc_workspace_bytes", "rpcc_project_scratch_bytes", "rpcc_fps_table_bytes", "rpcc_codec_workspace_bytes", "rpcc_beam_index_bytes",
+           "rpcc_project_beams_scratch_bytes"):
     getattr(_l, _n).restype = C.c_size_t
 
 
@@ -82,6 +83,27 @@ def point_cloud_to_range_image_even(point_cloud, H, W, horizontal_FOV, vertical_
     g = Geom(H, W, horizontal_FOV, vertical_max, vertical_min)  # double -> float exactly like the pybind11 arguments
     _ok(_l.rpcc_project(_p(xyz), _p(offs), C.c_int64(n), 1, g, _p(ri), _p(scratch), C.c_size_t(nb), _s()))
     return ri.view(H, W, 1).cpu().numpy()
+
+
+def point_cloud_to_range_image_table(point_cloud, H, W, horizontal_FOV, vertical_angle):
+    """The `else` branch of PCTransformer.point_cloud_to_range_image (dataset/transformer.py:68-91): vertical_angle = self.vertical_angle, the
+    radians of the channel_distribute_csv column, one per row.  -> f32 [H,W] like that branch (nearest table entry, the last point in input
+    order wins its pixel).  A transformer would build and upload the index once, in __init__, not per call as this stub does."""
+    va = np.ascontiguousarray(vertical_angle, dtype=np.float64)
+    if va.shape != (H,) or not 1 <= H <= 128 or not np.isfinite(va).all():
+        raise ValueError("vertical_angle: %d finite angles (radians) for a range image of at most 128 rows are needed" % H)
+    index = np.zeros(_l.rpcc_beam_index_bytes(H) // 8, dtype=np.float64)
+    _ok(_l.rpcc_beam_index_build(va.ctypes.data_as(C.c_void_p), H, index.ctypes.data_as(C.c_void_p)))
+    beams = torch.from_numpy(index).cuda()
+    xyz = _dev(np.asarray(point_cloud)[:, :3], np.float32)
+    n, P = xyz.shape[0], H * W
+    offs = torch.tensor([0, n], dtype=torch.int64, device="cuda")
+    ri = torch.empty((1, P), dtype=torch.float32, device="cuda")
+    nb = _l.rpcc_project_beams_scratch_bytes(C.c_int64(n), 1, P)
+    scratch = torch.empty((nb,), dtype=torch.uint8, device="cuda")
+    g = Geom(H, W, horizontal_FOV, 0.0, 0.0)   # (the two vertical angles are not used with a table)
+    _ok(_l.rpcc_project_beams(_p(xyz), 12, _p(offs), C.c_int64(n), 1, g, _p(beams), _p(ri), _p(scratch), C.c_size_t(nb), _s()))
+    return ri.view(H, W).cpu().numpy()
 
 
 # ---- ops/fps -----------------------------------------------------------------------------------------

@@ -50,6 +50,7 @@ MAX_CLUSTERS_MID = 1022     # RPCC_MAX_CLUSTERS_MID: the tuned kernels on uint16
 STREAM_OK, STREAM_E_ENTROPY, STREAM_E_PLANE, STREAM_E_CONTOUR, STREAM_E_WIDTH = 0, 1, 2, 3, 4     # RPCC_STREAM_* (rpcc_decompress_batch)
 STREAM_E_NSEQ, STREAM_E_LABEL, STREAM_E_SALIENCE, STREAM_E_RESIDUAL, STREAM_E_CONTAINER = 5, 6, 7, 8, 9
 LABELS_OK, LABELS_E_RANGE, LABELS_E_CAPPED = 0, 1, 2     # RPCC_LABELS_* (rpcc_compress_batch_labels)
+BEAM_MAX_H = 128       # RPCC_BEAM_MAX_H (csrc/beam_index.h): rows of a per-beam elevation table
 ABI_VERSION = 105      # RPCC_ABI_VERSION: the layout of rpcc_batch_io / rpcc_geom this binding was written for
 
 
@@ -76,6 +77,11 @@ _SIGS = {
     "rpcc_project_fastpath_check": (C.c_int, [_VP, _I64, Geom, _VP, _VP]),
     "rpcc_project": (C.c_int, [_VP, _VP, _I64, _I, Geom, _VP, _VP, C.c_size_t, _VP]),
     "rpcc_project_strided": (C.c_int, [_VP, _I, _VP, _I64, _I, Geom, _VP, _VP, C.c_size_t, _VP]),
+    "rpcc_beam_index_bytes": (C.c_size_t, [_I]),
+    "rpcc_beam_index_build": (C.c_int, [_VP, _I, _VP]),
+    "rpcc_project_beams_scratch_bytes": (C.c_size_t, [_I64, _I, _I]),
+    "rpcc_project_beams": (C.c_int, [_VP, _I, _VP, _I64, _I, Geom, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "rpcc_project_beams_check": (C.c_int, [_VP, _I64, Geom, _VP, _VP, _VP]),
     "rpcc_ground_ransac": (C.c_int, [_VP, _VP, _I, _I, C.c_uint32, _VP, _VP, _VP, _VP]),
     "rpcc_ground_mask": (C.c_int, [_VP, _VP, _VP, _D, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "rpcc_fps_table_bytes": (C.c_size_t, [_I, _I, _I]),
@@ -108,6 +114,8 @@ _SIGS = {
     "rpcc_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I64]),
     "rpcc_workspace_bytes_general": (C.c_size_t, [_I, _I, _I, _I64]),
     "rpcc_compress_batch": (C.c_int, [C.POINTER(BatchIO), _I, Geom, _I, _D, _F, _VP, _VP]),
+    "rpcc_compress_batch_beams_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I64, _I]),
+    "rpcc_compress_batch_beams": (C.c_int, [C.POINTER(BatchIO), _I, Geom, _VP, _I, _D, _F, _VP, _VP]),
     "rpcc_compress_batch_stages": (C.c_int, [C.POINTER(BatchIO), _I, Geom, _I, _D, _F, _VP, _I, _VP]),
     "rpcc_compress_batch_mixed": (C.c_int, [C.POINTER(BatchIO), C.POINTER(C.c_int), C.POINTER(Geom), _I, _I, _D, _F, C.POINTER(C.c_void_p), _VP]),
     "rpcc_wide_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I64]),

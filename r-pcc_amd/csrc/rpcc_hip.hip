@@ -1030,6 +1030,9 @@ extern "C" int rpcc_project(const float *xyz, const int64_t *offsets, int64_t to
     return rpcc_project_strided(xyz, 12, offsets, total, B, g, ri, scratch, scratch_bytes, stream);
 }
 
+#include "beam_index.h"
+#include "beams_kernels.h"
+
 // ================================================================================================
 // a4  ground plane: candidate selection + seeded RANSAC  (utils/segment_utils.py:74-82,101-108)
 // ================================================================================================
@@ -3720,6 +3723,7 @@ struct BatchPlan : BatchLayout {
     bool fit_ground, tiled;   // tiled: the FPS is tile-pruned, so the mask kernel fills the tile table
     int32_t *zcnt;
     BatchInit bi;
+    const void *beams = nullptr;   // rpcc_compress_batch_beams: the projection goes through this per-beam index
 };
 static int plan_batch(BatchPlan &p, const rpcc_batch_io *io, int Bs, int64_t npts, rpcc_geom g, int M, double ground_threshold, float acc, char *ws) {
     p.io = io; p.Bs = Bs; p.M = M; p.P = g.H * g.W; p.npts = npts; p.g = g; p.ground_threshold = ground_threshold; p.acc = acc; p.ws = ws;
@@ -3750,6 +3754,12 @@ static int run_stage(const BatchPlan &p, int stage, hipStream_t st) {
     int rc;
     switch (stage) {
     case ST_PROJECT:
+        if (p.beams) {   // (the table projection has no pixel kernel to carry the batch's initialisations: as on the device-atomic path)
+            batch_init_kernel<<<256, 256, 0, st>>>(p.bi);
+            LAUNCH_CHECK();
+            return launch_project_beams(io->xyz, io->offsets, p.npts, Bs, p.g, p.beams, io->ri, p.proj_scratch, p.proj_bytes, st,
+                                        point_floats(io->point_stride_bytes));
+        }
         return launch_project(io->xyz, io->offsets, p.npts, 0, Bs, p.g, io->ri, p.proj_scratch, p.proj_bytes, st,
                               p.rays_soa + 2 * (int64_t)P, p.zcnt, &p.bi, p.epoch, point_floats(io->point_stride_bytes));
     case ST_GROUND:
@@ -3815,10 +3825,12 @@ static int check_batch_io(const rpcc_batch_io *io, int B, rpcc_geom g, int M, co
 
 // the stages of stage_mask (bit i = stage i of the enum above) of one batch whose arguments passed check_batch_io, in order
 template <class L>
-static int run_batch(const rpcc_batch_io *io, int B, rpcc_geom g, int M, double ground_threshold, float acc, void *ws, int stage_mask, hipStream_t st) {
+static int run_batch(const rpcc_batch_io *io, int B, rpcc_geom g, int M, double ground_threshold, float acc, void *ws, int stage_mask, hipStream_t st,
+                     const void *beams = nullptr) {
     BatchPlan p;
     int rc;
     if ((rc = plan_batch(p, io, B, io->total, g, M, ground_threshold, acc, reinterpret_cast<char *>(ws)))) return rc;
+    p.beams = beams;
     for (int stage = 0; stage < ST_COUNT; stage++)
         if (((stage_mask >> stage) & 1) && (rc = run_stage<L>(p, stage, st))) return rc;
     return RPCC_OK;
@@ -4115,6 +4127,27 @@ extern "C" int rpcc_compress_batch_wide(const rpcc_batch_io *io, int B, rpcc_geo
     wide_quantise_kernel<uint16_t><<<dim3((P + 255) / 256, B), 256, 0, st>>>(io->ri, io->tm, seg, io->model, w.pos, acc, label_acc, P, K, io->q16);
     LAUNCH_CHECK();
     return RPCC_OK;
+}
+
+// ---- the fused batch through a per-beam elevation table: rpcc_compress_batch with the projection stage replaced ---------------------
+// Byte labels up to RPCC_MAX_CLUSTERS, uint16 labels (io->seg) up to RPCC_MAX_CLUSTERS_MID: the fused batch's own plan and stages either way.
+extern "C" size_t rpcc_compress_batch_beams_workspace_bytes(int B, int P, int M, int64_t total_points, int general) {
+    if (B <= 0 || P <= 0 || M <= 0 || M > RPCC_MAX_CLUSTERS_MID) return 0;
+    return M > RPCC_MAX_CLUSTERS ? rpcc_wide_workspace_bytes(B, P, M, total_points) : batch_ws_bytes(B, P, M, total_points, general != 0);
+}
+extern "C" int rpcc_compress_batch_beams(const rpcc_batch_io *io, int B, rpcc_geom g, const void *beams_dev, int M, double ground_threshold, float acc,
+                                         void *ws, void *stream) {
+    int rc;
+    ARG_TRY(beams_dev != nullptr && (reinterpret_cast<uintptr_t>(beams_dev) & 7u) == 0 && M <= RPCC_MAX_CLUSTERS_MID);
+    const bool wide = M > RPCC_MAX_CLUSTERS;
+    ARG_TRY(io != nullptr);
+    if ((rc = beams_args_ok(io->total, B, g))) return rc;   // (first: H * W fits an int before anything multiplies them)
+    if ((rc = check_batch_io(io, B, g, M, ws, wide))) return rc;
+    ARG_TRY(!wide || fps_prunable(fps_tiling_range(g.H, g.W)));
+    // (the projection scratch of the batch layout is sized for the even projection's records, which need more than the plane and the remembered pixels)
+    ARG_TRY(beams_layout(nullptr, io->total, B, g.H * g.W).bytes <= batch_layout(nullptr, B, g.H * g.W, M, io->total, true).proj_bytes);
+    if (wide) return run_batch<uint16_t>(io, B, g, M, ground_threshold, acc, ws, (1 << ST_COUNT) - 1, (hipStream_t)stream, beams_dev);
+    return run_batch<uint8_t>(io, B, g, M, ground_threshold, acc, ws, (1 << ST_COUNT) - 1, (hipStream_t)stream, beams_dev);
 }
 
 extern "C" int rpcc_contour_encode_wide(const uint16_t *seg, int B, int H, int W, uint8_t *contour_bits, uint16_t *idx_sequence, int32_t *nseq, void *ws, void *stream) {

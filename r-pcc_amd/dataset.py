@@ -100,10 +100,12 @@ class DatasetTemplate:
             assert False, "File type not correct."
 
 
-def build_dataset(datalist=None, dataset_name=None, lidar_type=None, use_radius_outlier_removal=False, device="cuda:0"):
-    """dataset/__init__.py:52-69."""
+def build_dataset(datalist=None, dataset_name=None, lidar_type=None, use_radius_outlier_removal=False, device="cuda:0",
+                  channel_distribute_csv=None):
+    """dataset/__init__.py:52-69.  channel_distribute_csv: the lidar's per-beam elevation table (DatasetTemplate.__init__ of the reference
+    passes it to PCTransformer; its registry never sets it)."""
     if dataset_name is not None:
-        return DatasetTemplate(datalist, __dataset_cfg__[dataset_name], None, use_radius_outlier_removal, device)
+        return DatasetTemplate(datalist, __dataset_cfg__[dataset_name], channel_distribute_csv, use_radius_outlier_removal, device)
     if lidar_type is not None:
-        return DatasetTemplate(datalist, __lidar_cfg__[lidar_type], None, use_radius_outlier_removal, device)
+        return DatasetTemplate(datalist, __lidar_cfg__[lidar_type], channel_distribute_csv, use_radius_outlier_removal, device)
     return DatasetTemplate(datalist, dataset_cfg=None, use_radius_outlier_removal=use_radius_outlier_removal)

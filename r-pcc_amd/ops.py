@@ -22,12 +22,16 @@ def make_geom(H, W, horizontal_FOV, vertical_max, vertical_min):
     return Geom(int(H), int(W), float(horizontal_FOV), float(vertical_max), float(vertical_min))
 
 
-def transform_map(H, W, horizontal_FOV, vertical_max, vertical_min):
+def transform_map(H, W, horizontal_FOV, vertical_max, vertical_min, vertical_angle=None):
     """a1: PCTransformer.create_transform_map (dataset/transformer.py:41-54).  Frame-invariant host
     work (once per process): python-float cos/sin products rounded to fp32; the reference's H*W Python
-    loop is evaluated as an outer product of the same fp64 factors."""
+    loop is evaluated as an outer product of the same fp64 factors.  vertical_angle (radians, one per row): the altitude
+    of row h is vertical_angle[h] (the per-beam table, dataset/transformer.py:48) instead of the even spacing."""
     vfov = vertical_max - vertical_min
-    alt = [vfov * (h / (H - 1)) + vertical_min for h in range(H)]
+    if vertical_angle is not None:
+        alt = [float(a) for a in beam_table(vertical_angle, H)]
+    else:
+        alt = [vfov * (h / (H - 1)) + vertical_min for h in range(H)]
     azi = [horizontal_FOV * (w / W) for w in range(W)]
     ca = np.array([math.cos(a) for a in alt]); sa = np.array([math.sin(a) for a in alt])
     cz = np.array([math.cos(a) for a in azi]); sz = np.array([math.sin(a) for a in azi])
@@ -49,16 +53,58 @@ def _point_stride(xyz):
     return 4 * int(xyz.shape[1])
 
 
-def project(xyz, offsets, geom, ri=None, scratch=None, atomic_path=False):
+def beam_table(vertical_angle, H=None):
+    """A per-beam elevation table as this build takes it: f64 [H] radians, row h of the image = entry h (any order, equal entries allowed).
+    Refused by name, on the host: an entry that is NaN or +-inf, a length other than H (RANGE_IMAGE_HEIGHT), more than BEAM_MAX_H rows
+    (the reference would raise IndexError or silently put points into wrong rows)."""
+    va = np.ascontiguousarray(np.asarray(vertical_angle, dtype=np.float64).reshape(-1))
+    if H is not None and va.shape[0] != int(H):
+        raise ValueError("per-beam table: %d vertical angles for RANGE_IMAGE_HEIGHT = %d (one per row is needed)" % (va.shape[0], int(H)))
+    if not 1 <= va.shape[0] <= _lib.BEAM_MAX_H:
+        raise ValueError("per-beam table: %d rows; this build takes 1 .. %d (RPCC_BEAM_MAX_H)" % (va.shape[0], _lib.BEAM_MAX_H))
+    if not np.isfinite(va).all():
+        raise ValueError("per-beam table: entry %d is not finite" % int(np.flatnonzero(~np.isfinite(va))[0]))
+    return va
+
+
+def beam_index_host(vertical_angle):
+    """The index of rpcc_project_beams for a table (rpcc_beam_index_build; layout: csrc/beam_index.h) as a uint8 array; built on the host,
+    no device is touched."""
+    va = beam_table(vertical_angle)
+    H = va.shape[0]
+    out = np.zeros(_lib.lib().rpcc_beam_index_bytes(H) // 8, dtype=np.float64)     # (8-byte aligned)
+    check(_lib.lib().rpcc_beam_index_build(va.ctypes.data_as(C.c_void_p), H, out.ctypes.data_as(C.c_void_p)))
+    return out.view(np.uint8)
+
+
+def beam_index(vertical_angle, device):
+    """beam_index_host() uploaded: what project(..., beams=) and compress_batch(..., beams=) take.  Once per transformer."""
+    return torch.from_numpy(beam_index_host(vertical_angle).copy()).to(device)
+
+
+def _check_beams(beams, geom):
+    assert beams.dtype == torch.uint8 and beams.numel() == 24 * geom.H, "beams: the index built for this geometry's H (ops.beam_index)"
+
+
+def project(xyz, offsets, geom, ri=None, scratch=None, atomic_path=False, beams=None):
     """a2 batched.  xyz f32 [total,3] -- or the stored rows f32 [total,4] (x, y, z, intensity), read with a 16-byte stride --,
     offsets i64 [B+1] (device) -> ri f32 [B,H,W].
     atomic_path=True gives the library only the small scratch, which selects the device-atomic kernels
-    (same result as the default LDS-band kernels)."""
+    (same result as the default LDS-band kernels).
+    beams (ops.beam_index): the projection through that per-beam elevation table instead (rpcc_project_beams: nearest table entry, the last point
+    in input order wins its pixel; geom's two vertical angles are ignored and atomic_path has no meaning)."""
     B = offsets.numel() - 1
     P = geom.H * geom.W
     xyz = xyz.contiguous()
     if ri is None:
         ri = torch.empty((B, geom.H, geom.W), dtype=torch.float32, device=_dev(offsets))
+    if beams is not None:
+        _check_beams(beams, geom)
+        if scratch is None:
+            scratch = torch.empty(max(_lib.lib().rpcc_project_beams_scratch_bytes(xyz.shape[0], B, P), 1), dtype=torch.uint8, device=_dev(offsets))
+        check(_lib.lib().rpcc_project_beams(ptr(xyz) if xyz.numel() else None, _point_stride(xyz), ptr(offsets), xyz.shape[0], B, geom,
+                                            ptr(beams), ptr(ri), ptr(scratch), scratch.numel() * scratch.element_size(), stream()))
+        return ri
     if scratch is None:
         n = B * (P + 8) * 4 if atomic_path else _lib.lib().rpcc_project_scratch_bytes(xyz.shape[0], B, P)
         scratch = torch.empty(n, dtype=torch.uint8, device=_dev(offsets))
@@ -75,6 +121,16 @@ def project_fastpath_check(xyz, geom):
     check(_lib.lib().rpcc_project_fastpath_check(ptr(xyz), int(xyz.shape[0]), geom, ptr(counts), stream()))
     c = [int(v) for v in counts.cpu()]
     return c[0], c[1], c[2], c[3] * 1e-9, c[4] * 1e-9
+
+
+def project_beams_check(xyz, geom, beams):
+    """Test hook of the table projection: (points the screened fast path is certain about, of those the ones the exact sequence skips or puts
+    into another pixel -- must be 0 --, points sent to the exact sequence).  xyz: packed f32 [N,3]."""
+    _check_beams(beams, geom)
+    assert xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.dtype == torch.float32 and xyz.is_contiguous()
+    counts = torch.zeros((3,), dtype=torch.int64, device=_dev(xyz))
+    check(_lib.lib().rpcc_project_beams_check(ptr(xyz), int(xyz.shape[0]), geom, ptr(beams), ptr(counts), stream()))
+    return tuple(int(v) for v in counts.cpu())
 
 
 def _frame_ids(frame_ids, B, device):
@@ -479,7 +535,7 @@ def nonuniform_cfg(acc, cfg=None):
 
 def compress_batch(xyz, offsets, tm, ground, buf, ground_threshold=0.1, acc=0.04, ground_seed=-1, frame_ids=None,
                    fps_bruteforce=False, timer=None, model_method="point", angle_threshold=75, plane_seed=0, nonuniform=None,
-                   fps_fma=None, fps_cuda_tie=None):
+                   fps_fma=None, fps_cuda_tie=None, beams=None):
     """Fused a2..a13 for a batch, one call: FPS segmentation, point or plane model, uniform or non-uniform framework
     (tools/compress.py:93-125).  xyz: f32 [total,3], or the stored (x, y, z, intensity) rows f32 [total,4] (16-byte stride,
     no host-side slice).  ground f64 [B,4]: injected models when ground_seed < 0, otherwise output of the seeded
@@ -488,9 +544,20 @@ def compress_batch(xyz, offsets, tm, ground, buf, ground_threshold=0.1, acc=0.04
     (plane_seed, frame_ids) with the reference's angle validation.  nonuniform: a nonuniform_cfg() struct -> key points,
     salience levels (buf.salience) and per-label steps; None = uniform framework with step `acc`.
     fps_fma / fps_cuda_tie: the CUDA-binary FPS modes (_lib.fps_mode_flags); None = the environment variables RPCC_FPS_FMA
-    (0 / 1 / 2) and RPCC_FPS_TIE_CUDA, so every front-end (tools, pipeline, loader) honours them."""
+    (0 / 1 / 2) and RPCC_FPS_TIE_CUDA, so every front-end (tools, pipeline, loader) honours them.
+    beams (ops.beam_index of the lidar's per-beam elevation table; tm then is the ray table built from the same table): the projection
+    stage goes through the table (rpcc_compress_batch_beams); cluster_num up to 1022."""
     io = _batch_io(xyz, offsets, tm, ground, buf, ground_seed, frame_ids, fps_bruteforce, timer, model_method, angle_threshold, plane_seed,
                    nonuniform, fps_fma, fps_cuda_tie)
+    if beams is not None:
+        _check_beams(beams, buf.geom)
+        if buf.M > _lib.MAX_CLUSTERS_MID:
+            raise NotImplementedError("cluster_num = %d with a per-beam elevation table: the table projection serves cluster_num <= %d "
+                                      "(rpcc_compress_batch_beams)" % (buf.M, _lib.MAX_CLUSTERS_MID))
+        buf._beams = beams            # (alive until the stream has consumed it)
+        check(_lib.lib().rpcc_compress_batch_beams(C.byref(io), buf.B, buf.geom, ptr(beams), buf.M, float(ground_threshold), float(acc),
+                                                   ptr(buf.ws), stream()))
+        return buf
     entry = _lib.lib().rpcc_compress_batch_wide if buf.wide else _lib.lib().rpcc_compress_batch   # (cluster_num > 254: uint16 labels)
     check(entry(C.byref(io), buf.B, buf.geom, buf.M, float(ground_threshold), float(acc), ptr(buf.ws), stream()))
     return buf

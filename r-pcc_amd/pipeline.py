@@ -45,6 +45,11 @@ class BatchCompressor:
         else:
             self.M = ops.check_cluster_num(cluster_num)   # (above 254: uint16 labels through the rpcc_*_wide entries; above 65533: refused by name)
         self.T = transformer
+        # a transformer built from a per-beam elevation table (channel_distribute_csv): the projection goes through its index -- the fused
+        # call's, the DBSCAN path's and the streaming loader's alike (all run_batch / _group_args); nothing behind the projection changes
+        if getattr(transformer, "even_dist", True) is False and not self.dbscan and self.M > _lib.MAX_CLUSTERS_MID:
+            raise NotImplementedError("cluster_num = %d with a per-beam elevation table (channel_distribute_csv): the table projection serves "
+                                      "cluster_num <= %d" % (self.M, _lib.MAX_CLUSTERS_MID))
         self.device = torch.device(device) if device is not None else transformer.device
         self.acc = accuracy * 2                     # tools/compress.py:46
         self.ground_threshold = ground_threshold
@@ -60,6 +65,11 @@ class BatchCompressor:
     @property
     def general(self):
         return not (self.uniform and self.model_method == "point")
+
+    @property
+    def beams(self):
+        """The device index of the transformer's per-beam elevation table, or None (evenly spaced beams)."""
+        return getattr(self.T, "beams_dev", None)
 
     @property
     def dbscan(self):
@@ -89,11 +99,11 @@ class BatchCompressor:
         if not self.dbscan:
             ops.compress_batch(xyz, offsets, self.T.tm_dev, ground, buf, self.ground_threshold, self.acc,
                                ground_seed=self.seed if fit_ground else -1, frame_ids=frame_ids, model_method=self.model_method,
-                               angle_threshold=angle, plane_seed=self.seed, nonuniform=nu)
+                               angle_threshold=angle, plane_seed=self.seed, nonuniform=nu, beams=self.beams)
             return
         from .dbscan import dbscan_segment
         tm = self.T.tm_dev
-        ops.project(xyz, offsets, self.T.geom, ri=buf.ri)
+        ops.project(xyz, offsets, self.T.geom, ri=buf.ri, beams=self.beams)
         if fit_ground:
             g, _ = ops.ground_ransac(buf.ri, tm, seed=self.seed, frame_ids=frame_ids)
             ground.copy_(g)
@@ -138,8 +148,11 @@ class BatchCompressor:
         g = torch.zeros((B, 4), dtype=torch.float64, device=self.device) if fit else ground
         # one fused call for all four framework / model combinations (tools/compress.py:109-124)
         nu = None if self.uniform else ops.nonuniform_cfg(self.acc, self.cfg)
-        return dict(xyz=xyz, offsets=offsets, tm=self.T.tm_dev, ground=g, buf=buf, ground_seed=self.seed if fit else -1, frame_ids=frame_ids,
+        args = dict(xyz=xyz, offsets=offsets, tm=self.T.tm_dev, ground=g, buf=buf, ground_seed=self.seed if fit else -1, frame_ids=frame_ids,
                     model_method=self.model_method, angle_threshold=self.cfg.get("plane_angle_threshold", 75), plane_seed=self.seed, nonuniform=nu)
+        if self.beams is not None:   # (never inside a mixed-geometry call: MixedBatchCompressor refuses such transformers)
+            args["beams"] = self.beams
+        return args
 
     def _encode(self, args):
         """Contour bits / index sequences of the segmentation a fused call left in args["buf"]."""
@@ -301,6 +314,10 @@ class MixedBatchCompressor:
         if kw.get("radius_outlier_removal") is not None:
             raise NotImplementedError("MixedBatchCompressor: radius_outlier_removal -- the mixed-geometry call takes the points as they are; "
                                       "filter them first (outlier.radius_outlier_mask), or use one BatchCompressor per lidar")
+        tabled = sorted(name for name, t in transformers.items() if getattr(t, "even_dist", True) is False)
+        if tabled:
+            raise NotImplementedError("MixedBatchCompressor: lidars %s have a per-beam elevation table (channel_distribute_csv) -- the "
+                                      "mixed-geometry call projects evenly spaced beams only; use one BatchCompressor per such lidar" % (tabled,))
         self.bcs = {name: BatchCompressor(t, **kw) for name, t in transformers.items()}
         first = next(iter(self.bcs.values()))
         self.device, self.ground_threshold, self.acc = first.device, first.ground_threshold, first.acc
@@ -364,7 +381,10 @@ class BatchDecompressor:
     """The .rpcc containers of FPS streams (cluster_num fixed by the configuration) decoded a chunk at a time: the containers' length prefixes are
     parsed on the host, the chunk's bytes go up in one copy, ONE launch of the back-end's device decoder writes every stream of the chunk
     straight into the padded [B, ...] arrays rpcc_decompress_batch reads -- what a stream may decode to follows from the geometry alone -- and
-    one ops.decompress_batch checks and decodes the frames (status per frame: _lib.STREAM_E_*).  accuracy / level_acc / uniform are
+    one ops.decompress_batch checks and decodes the frames (status per frame: _lib.STREAM_E_*).  A lidar with a per-beam elevation table
+    (PCTransformer(cfg, channel_distribute_csv)) needs nothing of its own here: the decoder reads the transformer's ray table -- built from that
+    table -- and nothing else of the geometry, so streams of such a lidar decode with the transformer they were encoded with.
+    accuracy / level_acc / uniform are
     tools/decompress.py:decode_frame's arguments, and its results are this class's, bit for bit.  The device decoders are used whatever the
     device_entropy / device_bunzip2 flags of a BasicCompressor handed in say: those govern the per-frame path.
     DBSCAN streams size their label count per frame (cluster_num=None, as decode_frame takes it): with max_labels=N they are decoded under the

@@ -52,6 +52,9 @@ def make_parser(datalist=False):
         p.add_argument("--original_point_cloud", default=None,
                        help="decompress.py --eval: the original point cloud file to compare the reconstruction with.")
     p.add_argument("--lidar", help="lidar type of this point cloud collection.")
+    p.add_argument("--channel_distribute_csv", default=None, metavar="FILE",
+                   help="per-beam elevation table of the lidar (columns channel, vertical_angle in degrees; row h of the range image = line h), "
+                        "for beams that are not evenly spaced: e.g. lidar_cfg/Velodyne_HDL_64E_beams.csv with --lidar Velodyne64E.")
     p.add_argument("--compressor_yaml", default=os.path.join(PKG, "cfgs/compressor.yaml"))
     p.add_argument("--basic_compressor", type=str, default=None, help="for manual setting.")
     p.add_argument("--device_entropy", action="store_true",
@@ -137,7 +140,7 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
     """cluster_num above 254 (labels as uint16): the per-stage mirror classes keep labels in a byte, so the frame goes through the batch front-end
     (pipeline.BatchCompressor -> rpcc_compress_batch_wide) as a batch of one.  Same container, same decoder."""
     from rpcc_amd.pipeline import BatchCompressor
-    dataset = build_dataset(lidar_type=args.lidar)
+    dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
     t0 = time.time()
     frame = dataset.load_data(args.input)
     if getattr(args, "use_radius_outlier_removal", False):
@@ -185,7 +188,8 @@ def compress(args):
     if segment_cfg["segment_method"] != "DBSCAN" and ops.is_wide(ops.check_cluster_num(segment_cfg["cluster_num"])):
         return compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform)
     filtered = getattr(args, "use_radius_outlier_removal", False)
-    dataset = build_dataset(lidar_type=args.lidar, use_radius_outlier_removal=filtered)
+    dataset = build_dataset(lidar_type=args.lidar, use_radius_outlier_removal=filtered,
+                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
     model_num = segment_cfg["cluster_num"] + 1
     pc_seg = PointCloudSegment(dataset.transform_map, seed=args.seed, frame_id=frame_identity(args.input))
 

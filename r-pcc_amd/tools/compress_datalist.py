@@ -99,7 +99,8 @@ def compress(args, streaming_factory=None):
         args.workers = max(1, min(args.workers, available_cpus()))
     apply_fps_mode(args)
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
-    dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device)
+    dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device,
+                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
     bc = BatchCompressor(dataset.PCTransformer, cluster_num=segment_cfg["cluster_num"], accuracy=accuracy / 2,
                          ground_threshold=segment_cfg["ground_vertical_threshold"], uniform=uniform,
                          model_method=model_cfg["model_method"], compressor_cfg=dict(cfg),

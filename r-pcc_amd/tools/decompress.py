@@ -92,7 +92,7 @@ def decompress(args):
     if args.eval and args.original_point_cloud is None:
         raise ValueError("--eval compares with the original point cloud: set --original_point_cloud")
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
-    dataset = build_dataset(lidar_type=args.lidar)
+    dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     t0 = time.time()
     cd = read_compressed_bitstream(args.input, uniform=uniform)

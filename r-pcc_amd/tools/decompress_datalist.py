@@ -53,7 +53,8 @@ def decompress(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
-    dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device)
+    dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device,
+                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     mine = list(shard_indices(len(dataset), rank, world))
     if getattr(args, "batch_decode", False):

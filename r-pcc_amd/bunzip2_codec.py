@@ -6,13 +6,14 @@ trailing bytes, a block with the randomised bit) are handed to bz2.decompress on
 to the device, one launch and one copy back where the sizes are known or guessed right; decode_descriptors is the device form: each
 stream lands at an offset of the caller's choice."""
 import bz2
+import functools
 
 import numpy as np
 import torch
 
 from . import _bunzip2_lib as L
+from . import entropy
 from ._lib import ptr, stream
-from .lz4_codec import _as_bytes, _device, _upload
 
 GUESS_RATIO, GUESS_SLACK = 8, 4096    # a stream of n bytes is first given 8 n + 4096 bytes: this project's payloads shrink 3.4 to 6.6 times
 
@@ -56,31 +57,33 @@ def decode_descriptors(addr, lens, dst, dst_off, dst_cap, work, work_off, work_c
     return dst_len, src_used, status
 
 
-def _level(a):
-    return int(a[3]) - 0x30 if a.size > 3 and 0x31 <= int(a[3]) <= 0x39 else 1
+def level_of(head):
+    """The level a stream states in its fourth byte ("BZh1" .. "BZh9"); 1 for anything else, which the decoder refuses."""
+    return int(head[3]) - 0x30 if len(head) > 3 and 0x31 <= int(head[3]) <= 0x39 else 1
+
+
+@functools.lru_cache(maxsize=None)
+def _slot_work_bytes(level, cap):
+    return (work_bytes(block_bound(level, cap)) + 7) // 8 * 8
+
+
+def stream_work_bytes(head, cap):
+    """The work slot, an 8-byte multiple, of a stream that begins with the bytes head and decodes to at most cap bytes."""
+    return _slot_work_bytes(level_of(head), int(cap))
+
+
+def decode_slots(d, dst, work):
+    """decode_descriptors over the descriptor rows d = [addr, lens, dst_off, dst_cap, work_off, work_cap].  -> (dst_len, status)."""
+    dst_len, _, status = decode_descriptors(d[0], d[1], dst, d[2], d[3], work, d[4], d[5])
+    return dst_len, status
 
 
 def _launch(arrays, cap, blocks, dev):
     """One H2D copy, one launch, one D2H copy -> (status i32 [n], dst_len i64 [n], the slots' bytes, their offsets).  cap: the slots'
     sizes; blocks: the block length each work slot holds."""
-    n = len(arrays)
-    off = np.zeros(n, np.int64)
-    off[1:] = np.cumsum((cap + 7) // 8 * 8)[:-1]
-    wcap = np.array([work_bytes(b) for b in blocks], np.int64)
-    woff = np.zeros(n, np.int64)
-    woff[1:] = np.cumsum((wcap + 7) // 8 * 8)[:-1]
-    with torch.cuda.device(dev):
-        data, doffs = _upload(arrays, dev)
-        addr = np.array([data.data_ptr() + int(o) for o in doffs], np.uint64).view(np.int64)
-        meta = torch.from_numpy(np.stack([addr, np.array([a.size for a in arrays], np.int64), off, cap, woff, wcap])).to(dev, non_blocking=True)
-        work = torch.empty(max(int(woff[-1] + wcap[-1]), 8), dtype=torch.uint8, device=dev)
-        res = torch.empty(24 * n + max(int(off[-1] + cap[-1]), 1), dtype=torch.uint8, device=dev)   # [dst_len | src_used | status | pad | bytes]
-        dst_len, src_used = res[: 8 * n].view(torch.int64), res[8 * n: 16 * n].view(torch.int64)
-        status, out = res[16 * n: 20 * n].view(torch.int32), res[24 * n:]
-        L.check(L.lib().rpcc_bunzip2_decode(ptr(meta[0]), ptr(meta[1]), n, ptr(out), ptr(meta[2]), ptr(meta[3]), ptr(work), ptr(meta[4]),
-                                            ptr(meta[5]), ptr(dst_len), ptr(src_used), ptr(status), stream()))
-        h = res.cpu().numpy()
-    return h[16 * n: 20 * n].view(np.int32).copy(), h[: 8 * n].view(np.int64).copy(), h[24 * n:], off
+    return entropy.decode_list(arrays, cap, dev, lambda n, m, out, cols, status, work: L.check(L.lib().rpcc_bunzip2_decode(
+        ptr(m[0]), ptr(m[1]), n, ptr(out), ptr(m[2]), ptr(m[3]), ptr(work), ptr(m[4]), ptr(m[5]), ptr(cols[0]), ptr(cols[1]), ptr(status),
+        stream())), work_cap=np.array([work_bytes(b) for b in blocks], np.int64), extra=1)
 
 
 def decode_many(blobs, caps=None, device=None):
@@ -94,9 +97,9 @@ def decode_many(blobs, caps=None, device=None):
     n = len(blobs)
     if not n:
         return np.zeros(0, np.int32), []
-    dev = _device(device)
-    arrays = [_as_bytes(b) for b in blobs]
-    level = np.array([_level(a) for a in arrays], np.int64)
+    dev = entropy.device_of(device)
+    arrays = [entropy.as_bytes(b) for b in blobs]
+    level = np.array([level_of(a) for a in arrays], np.int64)
     if caps is None:
         cap = np.array([GUESS_RATIO * a.size + GUESS_SLACK for a in arrays], np.int64)
     else:
@@ -106,7 +109,7 @@ def decode_many(blobs, caps=None, device=None):
     todo = np.arange(n)
     blocks = np.array([block_bound(level[k], cap[k]) for k in todo], np.int64)
     for _ in range(3):
-        s, lens, body, off = _launch([arrays[k] for k in todo], cap[todo].copy(), blocks, dev)
+        s, lens, body, off = _launch([arrays[k] for k in todo], cap[todo], blocks, dev)
         nxt, nblocks = [], []
         for j, k in enumerate(todo):
             st[k] = s[j]
@@ -137,10 +140,7 @@ def decode_many(blobs, caps=None, device=None):
 def decompress_many(blobs, caps=None):
     """[bzip2 stream bytes] -> [bytes].  ValueError names the first bad stream."""
     st, outs = decode_many(blobs, caps)
-    bad = np.flatnonzero(st != L.OK)
-    if bad.size:
-        k = int(bad[0])
-        raise ValueError("bzip2 stream %d: %s (status %d)" % (k, status_text(st[k]), int(st[k])))
+    entropy.raise_first_bad(st, "bzip2", _STATUS)
     return outs
 
 

@@ -7,12 +7,9 @@ pipeline uses, and lz4_codec.pack_containers compacts its output into .rpcc cont
 length out of range) is handed to bz2.compress on the host by compress_many."""
 import bz2
 
-import numpy as np
-import torch
-
 from . import _bzip2_lib as L
+from . import entropy
 from ._lib import ptr, stream
-from .lz4_codec import _as_bytes, _device, _upload
 
 GROUP = 50
 
@@ -43,21 +40,9 @@ def encode_descriptors(addr, lens, caps, ws=None, level=9):
     dst_len i64 GPU tensors, dst_off as numpy): stream s as a bzip2 stream at slots[dst_off[s]:][:dst_len[s]], dst_len[s] < 0 when
     its length was out of range or above its cap.  ws: the caller's work buffer of
     rpcc_bzip2_workspace_bytes(n, sum of caps, level) bytes, 16-byte aligned (allocated here when None)."""
-    dev = addr.device
-    cap = np.array([bound(int(c), level) for c in caps], np.int64)
-    off = np.zeros(len(cap), np.int64)
-    off[1:] = np.cumsum(cap)[:-1]
-    meta = torch.from_numpy(np.stack([off, cap])).to(dev, non_blocking=True)
-    slots = torch.empty(max(int(cap.sum()), 1), dtype=torch.uint8, device=dev)
-    dst_len = torch.empty(len(cap), dtype=torch.int64, device=dev)
-    if len(cap):
-        total = int(sum(int(c) for c in caps))
-        if ws is None:
-            ws = torch.empty(max(L.lib().rpcc_bzip2_workspace_bytes(len(cap), total, level), 16) // 8 + 2, dtype=torch.int64, device=dev)
-            ws = ws[(-ws.data_ptr() // 8) % 2:]      # 16-byte aligned
-        L.check(L.lib().rpcc_bzip2_encode(ptr(addr), ptr(lens), len(cap), total, level, ptr(slots), ptr(meta[0]), ptr(meta[1]), ptr(dst_len),
-                                          ptr(ws), stream()))
-    return slots, meta[0], dst_len, off
+    return entropy.encode_slots(addr, caps, lambda c: bound(c, level), lambda n, total, slots, off, cap, dst_len, w: L.check(L.lib().rpcc_bzip2_encode(
+        ptr(addr), ptr(lens), n, total, level, ptr(slots), ptr(off), ptr(cap), ptr(dst_len), ptr(w), stream())),
+        work_bytes=lambda n, total: L.lib().rpcc_bzip2_workspace_bytes(n, total, level), align=16, ws=ws)
 
 
 def compress_many(buffers, device=None, ws=None, level=9):
@@ -65,19 +50,8 @@ def compress_many(buffers, device=None, ws=None, level=9):
     coded by bz2.compress on the host."""
     if not buffers:
         return []
-    dev = _device(device)
-    arrays = [_as_bytes(b) for b in buffers]
-    with torch.cuda.device(dev):
-        data, offs = _upload(arrays, dev)
-        sizes = [a.size for a in arrays]
-        desc = torch.tensor([[data.data_ptr() + int(o) for o in offs], sizes], dtype=torch.int64).to(dev, non_blocking=True)
-        slots, _, dst_len, off = encode_descriptors(desc[0], desc[1], sizes, ws=ws, level=level)
-        # [dst_len as bytes | slots] leave in one copy
-        both = torch.cat([dst_len.view(torch.uint8), slots]).cpu().numpy()
-        torch.cuda.current_stream(dev).synchronize()
-    n = len(arrays)
-    got = both[: 8 * n].view(np.int64)
-    body = both[8 * n:]
+    arrays = [entropy.as_bytes(b) for b in buffers]
+    got, body, off = entropy.encode_list(arrays, device, encode_descriptors, ws=ws, level=level)
     return [body[o: o + g].tobytes() if g >= 0 else bz2.compress(a.tobytes(), level) for a, o, g in zip(arrays, off, got)]
 
 

@@ -2,8 +2,10 @@
 packing, the .rpcc container and the entropy back-ends (stdlib calls, excluded from the measured path).
 """
 import bz2
+import collections
 import copy
 import gzip
+import importlib
 import os
 import struct
 
@@ -195,6 +197,34 @@ def decompress_point_cloud(compressed_data, basic_compressor, model_num, H, W):
     return residual_quantized, idx_map, salience, plane_param
 
 
+# One row per basic_compressor method: the host library's functions (None: the lz4 package, see BasicCompressor._lz4), the device encoder --
+# module of this package, its list encoder, the BasicCompressor flag that turns it on -- and the device decoder alike; work_slots: its
+# decode_descriptors takes work slots.  The modules are imported where a row is used, not here.
+Backend = collections.namedtuple("Backend", "host_encode host_decode encoder encode_many encode_flag decoder decode_many decode_flag work_slots")
+_GZIP = Backend(gzip.compress, gzip.decompress, "deflate_codec", "compress_many", "device_entropy", "inflate_codec", "decompress_many", "device_entropy", False)
+BACKENDS = {
+    "lz4": Backend(None, None, "lz4_codec", "dumps_many", None, "lz4_codec", "loads_many", None, False),
+    "bzip2": Backend(bz2.compress, bz2.decompress, "bzip2_codec", "compress_many", "device_bzip2", "bunzip2_codec", "decompress_many", "device_bunzip2", True),
+    "gzip": _GZIP,
+    "deflate": _GZIP,
+}
+
+
+def _module(name):
+    return importlib.import_module("." + name, __package__)
+
+
+def device_decoder(method_name):
+    """What pipeline.BatchDecompressor asks of a method's device decoder: (work_bytes(a stream's first bytes, its cap) -> the bytes of its
+    work slot, 0 where the decoder has none; decode_slots(descriptor rows [addr, lens, dst_off, dst_cap, work_off, work_cap], dst, work) ->
+    (dst_len, status) GPU tensors, enqueued on the current stream)."""
+    be = BACKENDS[method_name]
+    codec = _module(be.decoder)
+    if be.work_slots:
+        return codec.stream_work_bytes, codec.decode_slots
+    return (lambda head, cap: 0), (lambda d, dst, work: codec.decode_descriptors(d[0], d[1], dst, d[2], d[3]))
+
+
 class BasicCompressor:
     """utils/compress_utils.py:232-310.  bzip2 / deflate are stdlib; lz4 is the lz4 package (lz4==0.7.0 API in the reference)
     where it is installed, else rpcc_amd.lz4_codec (the same dumps / loads forms, coded on the GPU).  device_entropy=True
@@ -223,32 +253,39 @@ class BasicCompressor:
         assert method_name in self.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate)"
         self.method_name = method_name
 
+    def _resolved(self):
+        """The one place that chooses the back-end, from BACKENDS: (method_name, flags) -> (compress one array, decompress one stream, (device
+        encoder module, its list encoder) or None, the device decoder's list decoder or None).  No method set: four times None."""
+        be = BACKENDS.get(self.method_name)
+        if be is None:
+            return None, None, None, None
+        host, on = (be.host_encode, be.host_decode), lambda flag: getattr(self, flag)
+        if be.host_encode is None:       # 'lz4': the lz4 package where it is installed, else lz4_codec on the device, whatever the flags say
+            pkg = self._lz4()
+            host, on = (lambda a: pkg.dumps(a.tobytes()), pkg.loads), lambda flag: pkg is _module(be.encoder)
+        codec = (_module(be.encoder), getattr(_module(be.encoder), be.encode_many)) if on(be.encode_flag) else None
+        decoder = getattr(_module(be.decoder), be.decode_many) if on(be.decode_flag) else None
+        return (lambda a: codec[1]([a])[0]) if codec else host[0], (lambda s: decoder([s])[0]) if decoder else host[1], codec, decoder
+
+    def _batched(self, name):
+        codec = self._resolved()[2]
+        return codec is not None and codec[0].__name__.endswith("." + name)
+
     def lz4_batched(self):
         """True when 'lz4' runs through rpcc_amd.lz4_codec, which codes a list of arrays in one launch."""
-        if self.method_name != "lz4":
-            return False
-        from . import lz4_codec
-        return self._lz4() is lz4_codec
+        return self._batched("lz4_codec")
 
     def deflate_batched(self):
         """True when 'deflate' / 'gzip' runs through rpcc_amd.deflate_codec (device_entropy), which codes a list of arrays at once."""
-        return self.device_entropy and self.method_name in ("gzip", "deflate")
+        return self._batched("deflate_codec")
 
     def bzip2_batched(self):
         """True when 'bzip2' is encoded through rpcc_amd.bzip2_codec (device_bzip2), which codes a list of arrays at once."""
-        return self.device_bzip2 and self.method_name == "bzip2"
+        return self._batched("bzip2_codec")
 
     def batch_codec(self):
         """(module, its list encoder) of the back-end that codes a list of arrays on the device at once, or None."""
-        if self.lz4_batched():
-            return self._lz4(), self._lz4().dumps_many
-        if self.deflate_batched():
-            from . import deflate_codec
-            return deflate_codec, deflate_codec.compress_many
-        if self.bzip2_batched():
-            from . import bzip2_codec
-            return bzip2_codec, bzip2_codec.compress_many
-        return None
+        return self._resolved()[2]
 
     def compress_dict(self, data_dict):
         if self.batch_codec():
@@ -257,15 +294,7 @@ class BasicCompressor:
 
     def batch_decoder(self):
         """The list decoder of the back-end that decodes a list of streams on the device at once, or None."""
-        if self.lz4_batched():
-            return self._lz4().loads_many
-        if self.deflate_batched():
-            from . import inflate_codec
-            return inflate_codec.decompress_many
-        if self.device_bunzip2 and self.method_name == "bzip2":
-            from . import bunzip2_codec
-            return bunzip2_codec.decompress_many
-        return None
+        return self._resolved()[3]
 
     def decompress_dict(self, data_dict):
         if self.batch_decoder():
@@ -281,29 +310,16 @@ class BasicCompressor:
         return [{k: next(outs) for k in d} for d in data_dicts]
 
     def compress(self, np_array):
-        buf = np.ascontiguousarray(np_array)
-        if self.bzip2_batched():
-            return self.batch_codec()[1]([buf])[0]
-        if self.method_name == "bzip2":
-            return bz2.compress(buf)
-        if self.deflate_batched():
-            return self.batch_codec()[1]([buf])[0]
-        if self.method_name in ("gzip", "deflate"):
-            return gzip.compress(buf)
-        if self.method_name == "lz4":
-            return self._lz4().dumps(buf.tobytes())
-        raise ValueError("no compression method set")
+        encode = self._resolved()[0]
+        if encode is None:
+            raise ValueError("no compression method set")
+        return encode(np.ascontiguousarray(np_array))
 
     def decompress(self, bitstream):
-        if self.method_name == "bzip2":
-            return self.batch_decoder()([bitstream])[0] if self.device_bunzip2 else bz2.decompress(bitstream)
-        if self.deflate_batched():
-            return self.batch_decoder()([bitstream])[0]
-        if self.method_name in ("gzip", "deflate"):
-            return gzip.decompress(bitstream)
-        if self.method_name == "lz4":
-            return self._lz4().loads(bitstream)
-        raise ValueError("no compression method set")
+        decode = self._resolved()[1]
+        if decode is None:
+            raise ValueError("no compression method set")
+        return decode(bitstream)
 
     def calc_compressed_bytes(self, np_array):
         return len(self.compress(np_array))
@@ -314,5 +330,4 @@ class BasicCompressor:
             import lz4
             return lz4
         except ImportError:
-            from . import lz4_codec
-            return lz4_codec
+            return _module("lz4_codec")

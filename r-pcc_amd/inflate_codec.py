@@ -10,8 +10,8 @@ import numpy as np
 import torch
 
 from . import _inflate_lib as L
+from . import entropy
 from ._lib import ptr, stream
-from .lz4_codec import _as_bytes, _device, _upload
 
 MAX_RATIO = 1032      # deflate's largest expansion: 258 bytes from a 2-bit match
 
@@ -54,21 +54,8 @@ def size_fields(a):
     return min(alone, top), min(max(alone, padded), top)
 
 
-def _launch(arrays, cap, dev):
-    """One H2D copy, one launch, one D2H copy -> (status i32 [n], dst_len i64 [n], the slots' bytes, their offsets)."""
-    n = len(arrays)
-    off = np.zeros(n, np.int64)
-    off[1:] = np.cumsum((cap + 7) // 8 * 8)[:-1]
-    with torch.cuda.device(dev):
-        data, doffs = _upload(arrays, dev)
-        addr = np.array([data.data_ptr() + int(o) for o in doffs], np.uint64).view(np.int64)
-        meta = torch.from_numpy(np.stack([addr, np.array([a.size for a in arrays], np.int64), off, cap])).to(dev, non_blocking=True)
-        res = torch.empty(16 * n + max(int(off[-1] + cap[-1]), 1), dtype=torch.uint8, device=dev)   # [dst_len | status | pad | bytes]
-        dst_len, status, out = res[: 8 * n].view(torch.int64), res[8 * n: 12 * n].view(torch.int32), res[16 * n:]
-        L.check(L.lib().rpcc_inflate_decode(ptr(meta[0]), ptr(meta[1]), n, ptr(out), ptr(meta[2]), ptr(meta[3]), ptr(dst_len), ptr(status),
-                                            stream()))
-        h = res.cpu().numpy()
-    return h[8 * n: 12 * n].view(np.int32).copy(), h[: 8 * n].view(np.int64), h[16 * n:], off
+def _decode(n, m, out, cols, status, work):
+    L.check(L.lib().rpcc_inflate_decode(ptr(m[0]), ptr(m[1]), n, ptr(out), ptr(m[2]), ptr(m[3]), ptr(cols[0]), ptr(status), stream()))
 
 
 def decode_many(blobs, device=None):
@@ -78,27 +65,23 @@ def decode_many(blobs, device=None):
     last bytes can mean, see size_fields: padding is not something this project writes.)"""
     if not blobs:
         return np.zeros(0, np.int32), []
-    dev = _device(device)
-    arrays = [_as_bytes(b) for b in blobs]
+    dev = entropy.device_of(device)
+    arrays = [entropy.as_bytes(b) for b in blobs]
     sizes = np.array([size_fields(a) for a in arrays], np.int64).reshape(-1, 2)
-    st, lens, body, off = _launch(arrays, sizes[:, 0].copy(), dev)
-    outs = [body[o: o + l].tobytes() if s == 0 else None for o, l, s in zip(off, lens, st)]
+    res = entropy.decode_list(arrays, sizes[:, 0], dev, _decode)
+    st, outs = res[0], entropy.slot_bytes(*res)
     again = np.flatnonzero((st != L.OK) & (sizes[:, 1] > sizes[:, 0]))
     if again.size:
-        st2, lens2, body2, off2 = _launch([arrays[k] for k in again], sizes[again, 1].copy(), dev)
-        for j, k in enumerate(again):
-            st[k] = st2[j]
-            outs[k] = body2[off2[j]: off2[j] + lens2[j]].tobytes() if st2[j] == 0 else None
+        res = entropy.decode_list([arrays[k] for k in again], sizes[again, 1], dev, _decode)
+        for k, s, o in zip(again, res[0], entropy.slot_bytes(*res)):
+            st[k], outs[k] = s, o
     return st, outs
 
 
 def decompress_many(blobs, device=None):
     """[gzip member bytes] -> [bytes].  ValueError names the first bad stream."""
     st, outs = decode_many(blobs, device)
-    bad = np.flatnonzero(st != L.OK)
-    if bad.size:
-        k = int(bad[0])
-        raise ValueError("gzip stream %d: %s (status %d)" % (k, status_text(st[k]), int(st[k])))
+    entropy.raise_first_bad(st, "gzip", _STATUS)
     return outs
 
 

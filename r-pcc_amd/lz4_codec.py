@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lz4_lib as L
+from . import entropy
 from ._lib import ptr, stream
 
 _STATUS = {L.E_CAPACITY: "header size larger than the output capacity", L.E_TRUNCATED: "truncated header, token, literal or offset",
@@ -22,42 +23,13 @@ def bound(n):
     return 4 + n + n // 255 + 16
 
 
-def _device(device):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_bytes(buf):
-    if isinstance(buf, np.ndarray):
-        return np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
-    return np.frombuffer(memoryview(buf).cast("B"), np.uint8)
-
-
-def _upload(arrays, device):
-    """The arrays in one pinned host buffer, each at an 8-byte aligned offset -> one H2D copy.  -> (device tensor, payload offsets)."""
-    offs = np.zeros(len(arrays) + 1, np.int64)
-    offs[1:] = np.cumsum([(a.size + 7) // 8 * 8 for a in arrays])
-    host = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=True)
-    h = host.numpy()
-    for a, o in zip(arrays, offs[:-1]):
-        h[o: o + a.size] = a
-    return host.to(device, non_blocking=True), offs[:-1]
-
-
 def encode_descriptors(addr, lens, caps):
     """Device form of dumps over descriptors: addr, lens (i64 GPU tensors [n]) the streams' device addresses and byte counts, caps
     (host ints) an upper bound of each length.  Enqueued on the current stream, nothing waited for.  -> (slots u8, dst_off i64,
     dst_len i64 GPU tensors, dst_off as numpy): stream s in dumps form at slots[dst_off[s]:][:dst_len[s]], dst_len[s] < 0 when its
     length was out of range."""
-    dev = addr.device
-    cap = np.array([bound(int(c)) for c in caps], np.int64)
-    off = np.zeros(len(cap), np.int64)
-    off[1:] = np.cumsum(cap)[:-1]
-    meta = torch.from_numpy(np.stack([off, cap])).to(dev, non_blocking=True)
-    slots = torch.empty(max(int(cap.sum()), 1), dtype=torch.uint8, device=dev)
-    dst_len = torch.empty(len(cap), dtype=torch.int64, device=dev)
-    if len(cap):
-        L.check(L.lib().rpcc_lz4_encode(ptr(addr), ptr(lens), len(cap), ptr(slots), ptr(meta[0]), ptr(meta[1]), ptr(dst_len), stream()))
-    return slots, meta[0], dst_len, off
+    return entropy.encode_slots(addr, caps, bound, lambda n, total, slots, off, cap, dst_len, ws: L.check(L.lib().rpcc_lz4_encode(
+        ptr(addr), ptr(lens), n, ptr(slots), ptr(off), ptr(cap), ptr(dst_len), stream())))
 
 
 def encode_tensors(srcs):
@@ -66,7 +38,7 @@ def encode_tensors(srcs):
         if not t.is_cuda or not t.is_contiguous():
             raise ValueError("encode_tensors: expects contiguous GPU tensors")
     nbytes = [t.numel() * t.element_size() for t in srcs]
-    dev = _device(None)
+    dev = entropy.device_of(None)
     desc = torch.tensor([[t.data_ptr() for t in srcs], nbytes], dtype=torch.int64).to(dev, non_blocking=True)
     return encode_descriptors(desc[0], desc[1], nbytes)
 
@@ -89,21 +61,9 @@ def dumps_many(buffers, device=None):
     """[bytes-like or numpy array] -> [dumps form bytes]: one H2D copy, one launch, one D2H copy."""
     if not buffers:
         return []
-    dev = _device(device)
-    arrays = [_as_bytes(b) for b in buffers]
-    with torch.cuda.device(dev):
-        data, offs = _upload(arrays, dev)
-        sizes = [a.size for a in arrays]
-        desc = torch.tensor([[data.data_ptr() + int(o) for o in offs], sizes], dtype=torch.int64).to(dev, non_blocking=True)
-        slots, _, dst_len, off = encode_descriptors(desc[0], desc[1], sizes)
-        # [dst_len as bytes | slots] leave in one copy
-        both = torch.cat([dst_len.view(torch.uint8), slots]).cpu().numpy()
-        torch.cuda.current_stream(dev).synchronize()
-    n = len(arrays)
-    got = both[: 8 * n].view(np.int64)
+    got, body, off = entropy.encode_list([entropy.as_bytes(b) for b in buffers], device, encode_descriptors)
     if (got < 0).any():
         raise RuntimeError("rpcc_lz4_encode: a stream was refused (length out of range)")
-    body = both[8 * n:]
     return [body[o: o + g].tobytes() for o, g in zip(off, got)]
 
 
@@ -123,33 +83,18 @@ def decode_many(blobs, device=None):
     """[dumps form bytes] -> (status int32 [n]: 0 or RPCC_LZ4_E_*, [bytes]): one H2D copy, one launch, one D2H copy."""
     if not blobs:
         return np.zeros(0, np.int32), []
-    dev = _device(device)
-    arrays = [_as_bytes(b) for b in blobs]
+    arrays = [entropy.as_bytes(b) for b in blobs]
     # the header is on the host: size each output by it, but never beyond what a valid block of that length can produce (255:1)
     cap = np.array([min(struct.unpack_from("<I", a)[0], 255 * a.size) if a.size >= 4 else 0 for a in arrays], np.int64)
-    off = np.zeros(len(cap), np.int64)
-    off[1:] = np.cumsum((cap + 7) // 8 * 8)[:-1]
-    n = len(arrays)
-    with torch.cuda.device(dev):
-        data, doffs = _upload(arrays, dev)
-        addr = np.array([data.data_ptr() + int(o) for o in doffs], np.uint64).view(np.int64)
-        meta = torch.from_numpy(np.stack([addr, np.array([a.size for a in arrays], np.int64), off, cap])).to(dev, non_blocking=True)
-        res = torch.empty(16 * n + max(int(off[-1] + cap[-1]), 1), dtype=torch.uint8, device=dev)   # [dst_len | status | pad | bytes]
-        dst_len, status, out = res[: 8 * n].view(torch.int64), res[8 * n: 12 * n].view(torch.int32), res[16 * n:]
-        L.check(L.lib().rpcc_lz4_decode(ptr(meta[0]), ptr(meta[1]), n, ptr(out), ptr(meta[2]), ptr(meta[3]), ptr(dst_len), ptr(status),
-                                        stream()))
-        h = res.cpu().numpy()
-    lens, st, body = h[: 8 * n].view(np.int64), h[8 * n: 12 * n].view(np.int32).copy(), h[16 * n:]
-    return st, [body[o: o + l].tobytes() if s == 0 else None for o, l, s in zip(off, lens, st)]
+    res = entropy.decode_list(arrays, cap, entropy.device_of(device), lambda n, m, out, cols, status, work: L.check(L.lib().rpcc_lz4_decode(
+        ptr(m[0]), ptr(m[1]), n, ptr(out), ptr(m[2]), ptr(m[3]), ptr(cols[0]), ptr(status), stream())))
+    return res[0], entropy.slot_bytes(*res)
 
 
 def loads_many(blobs, device=None):
     """[dumps form bytes] -> [bytes].  ValueError names the first bad stream."""
     st, outs = decode_many(blobs, device)
-    bad = np.flatnonzero(st != L.OK)
-    if bad.size:
-        k = int(bad[0])
-        raise ValueError("lz4 stream %d: %s (status %d)" % (k, _STATUS.get(int(st[k]), "error"), int(st[k])))
+    entropy.raise_first_bad(st, "lz4", _STATUS)
     return outs
 
 

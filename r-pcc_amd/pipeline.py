@@ -8,9 +8,9 @@ import struct
 import numpy as np
 import torch
 
-from . import ops
+from . import entropy, ops
 from . import _lib
-from .compress_utils import _ORDER, BasicCompressor, pack_bitstream, pack_frames, unpack_bitstream  # noqa: F401
+from .compress_utils import _ORDER, BasicCompressor, device_decoder, pack_bitstream, pack_frames, unpack_bitstream  # noqa: F401
 
 
 class BatchCompressor:
@@ -193,7 +193,7 @@ class BatchCompressor:
                    stream=torch.cuda.current_stream(self.device), keep=(xyz, g, seq))
         codec = self.bc.batch_codec()
         if codec:
-            ctx["lz4"] = self._device_containers(codec[0], n, buf, bits, nseq, sal, qp, sp)
+            ctx["containers"] = self._device_containers(codec[0], n, buf, bits, nseq, sal, qp, sp)
         return ctx
 
     def _device_containers(self, codec, B, buf, bits, nseq, sal, qp, sp):
@@ -234,8 +234,8 @@ class BatchCompressor:
         pool: a concurrent.futures executor -- the frames' entropy coding then runs on its threads (bz2 / zlib / lz4
         release the GIL), like the reference's --workers ThreadPoolExecutor (tools/compress_datalist.py:202-206)."""
         buf = ctx["buf"]
-        if "lz4" in ctx:
-            return self._collect_lz4(ctx)
+        if "containers" in ctx:
+            return self._collect_containers(ctx)
         try:
             ctx["stream"].synchronize()
             bits, nseq, sal = ctx["bits"], ctx["nseq"], ctx["sal"]
@@ -266,9 +266,9 @@ class BatchCompressor:
         parts = list(pool.map(chunk, range(0, n, step))) if pool is not None else [chunk(lo) for lo in range(0, n, step)]
         return [blob for part in parts for blob in part]
 
-    def _collect_lz4(self, ctx):
+    def _collect_containers(self, ctx):
         """The containers _device_containers built: the frames' places, then the containers in one copy."""
-        out, frame, _ = ctx["lz4"]
+        out, frame, _ = ctx["containers"]
         try:
             ctx["stream"].synchronize()
             fr = frame.cpu().numpy()
@@ -413,27 +413,21 @@ class BatchDecompressor:
         self.method = basic_compressor.method_name if isinstance(basic_compressor, BasicCompressor) else basic_compressor
         assert self.method in BasicCompressor.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate)"
         self.host_bc = BasicCompressor(method_name=self.method)   # the E_ENTROPY fallback: the host library's decoder
+        self.work_bytes, self.decode_slots = device_decoder(self.method)   # the device decoder, whatever the flags say
         P, K = transformer.H * transformer.W, self.M + 2
         self.ns = 4 if self.uniform else 5
         # decoded bytes a stream can have, in container order (salience first when present): fixed by the geometry
         self.caps = ([] if self.uniform else [K]) + [(P + 7) // 8, 2 * P, 16 * K, 2 * P]
-        self._work = {}
         self.chunk = max(1, min(self.CHUNK_FRAMES, self.CHUNK_BUDGET_BYTES // self._frame_bytes()))
 
-    def _work_caps(self, levels):
-        """bzip2 work slot bytes of the streams of one frame (8-byte multiples) for the streams' levels; None for the other back-ends."""
-        if self.method != "bzip2":
-            return None
-        from . import bunzip2_codec
-        for key in zip(levels, self.caps):
-            if key not in self._work:
-                self._work[key] = (bunzip2_codec.work_bytes(bunzip2_codec.block_bound(*key)) + 7) // 8 * 8
-        return [self._work[key] for key in zip(levels, self.caps)]
+    def _work_caps(self, heads):
+        """Work slot bytes of the streams of one frame (8-byte multiples, 0 where the decoder takes none), from each stream's first bytes."""
+        return [self.work_bytes(h, c) for h, c in zip(heads, self.caps)]
 
     def _frame_bytes(self):
         """Device bytes a frame of a chunk takes at most (bzip2: every stream at level 9)."""
         P = self.T.H * self.T.W
-        work = sum(self._work_caps([9] * self.ns) or [0])
+        work = sum(self._work_caps([b"BZh9"] * self.ns))
         outs = P * (2 if ops.is_wide(self.M) else 1) + 4 * P + 12 * P
         ws = -(-_lib.lib().rpcc_decompress_workspace_bytes(self.CHUNK_FRAMES, P, self.M) // self.CHUNK_FRAMES)
         return sum(self.caps) + 5 * 256 + work + outs + ws
@@ -441,7 +435,6 @@ class BatchDecompressor:
     def _chunk_device(self, blobs, out, data=None):
         """One chunk: parse, upload, entropy launch, decode call on the current stream.  out: the chunk's rows of (status, seg, rec, pc).
         data: (device u8 tensor, offsets) when the containers are on the device already (the tensor must stay alive until the stream has run)."""
-        from . import lz4_codec
         B, ns, dev = len(blobs), self.ns, self.device
         H, W, K = self.T.H, self.T.W, self.M + 2
         P = H * W
@@ -452,19 +445,18 @@ class BatchDecompressor:
         row = self.caps
         part = np.zeros(ns + 1, np.int64)
         part[1:] = np.cumsum([(B * r + 255) // 256 * 256 for r in row])
-        arrays = [lz4_codec._as_bytes(b) for b in blobs]
-        boff = np.zeros(B + 1, np.int64)
-        boff[1:] = np.cumsum([(a.size + 7) // 8 * 8 for a in arrays])
+        arrays = [entropy.as_bytes(b) for b in blobs]
+        boff, bend = entropy.aligned_slots([a.size for a in arrays])
         # descriptors [addr | lens | dst_off | dst_cap | work_off | work_cap | sound frames | refused frames] and the chunk's bytes: one pinned buffer
         nmeta = 6 * n + B
-        host = torch.empty(8 * nmeta + (int(boff[-1]) if data is None else 0), dtype=torch.uint8, pin_memory=True)
+        host = torch.empty(8 * nmeta + ((bend + 7) // 8 * 8 if data is None else 0), dtype=torch.uint8, pin_memory=True)
         up = torch.empty(host.numel(), dtype=torch.uint8, device=dev)
         meta_h = host[: 8 * nmeta].numpy().view(np.int64)
         base = up.data_ptr() + 8 * nmeta if data is None else data[0].data_ptr()
         offs = boff if data is None else data[1]
         if data is None:
             body = host[8 * nmeta:].numpy()
-            for a, o in zip(arrays, boff[:-1]):
+            for a, o in zip(arrays, boff):
                 body[o: o + a.size] = a
         sp = np.array([spans[i] for i in sound], np.int64).reshape(len(sound), ns, 2)
         fr = np.array(sound, np.int64)
@@ -472,29 +464,17 @@ class BatchDecompressor:
         meta_h[1 * n: 2 * n] = sp[:, :, 1].reshape(-1)
         meta_h[2 * n: 3 * n] = (part[None, :ns] + fr[:, None] * np.array(row, np.int64)[None, :]).reshape(-1)
         meta_h[3 * n: 4 * n] = np.tile(np.array(row, np.int64), len(sound))
-        work = None
-        if self.method == "bzip2":
-            wcap = np.zeros((len(sound), ns), np.int64)
-            for j, i in enumerate(sound):   # the level byte of each stream ("BZh1" .. "BZh9"; anything else is refused by the decoder)
-                lv = [int(arrays[i][o + 3]) - 0x30 if l > 3 and 0x31 <= int(arrays[i][o + 3]) <= 0x39 else 1 for o, l in spans[i]]
-                wcap[j] = self._work_caps(lv)
-            woff = np.cumsum(wcap.reshape(-1)) - wcap.reshape(-1)
-            meta_h[4 * n: 5 * n], meta_h[5 * n: 6 * n] = woff, wcap.reshape(-1)
-            work = torch.empty(max(int(wcap.sum()), 8), dtype=torch.uint8, device=dev)
+        wcap = np.array([self._work_caps([arrays[i][o: o + min(l, 4)] for o, l in spans[i]]) for i in sound], np.int64).reshape(-1)
+        meta_h[4 * n: 5 * n], wtotal = entropy.packed_slots(wcap)
+        meta_h[5 * n: 6 * n] = wcap
+        work = torch.empty(wtotal, dtype=torch.uint8, device=dev) if wtotal else None
         bad = np.array([i for i in range(B) if spans[i] is None], np.int64)
         meta_h[6 * n: 6 * n + len(sound)], meta_h[6 * n + len(sound): 6 * n + B] = fr, bad
         up.copy_(host, non_blocking=True)
         meta = up[: 8 * nmeta].view(torch.int64)
         d = [meta[k * n: (k + 1) * n] for k in range(6)]
         dst = torch.empty(int(part[-1]), dtype=torch.uint8, device=dev)
-        if self.method == "lz4":
-            dst_len, est = lz4_codec.decode_descriptors(d[0], d[1], dst, d[2], d[3])
-        elif self.method == "bzip2":
-            from . import bunzip2_codec
-            dst_len, _, est = bunzip2_codec.decode_descriptors(d[0], d[1], dst, d[2], d[3], work, d[4], d[5])
-        else:
-            from . import inflate_codec
-            dst_len, est = inflate_codec.decode_descriptors(d[0], d[1], dst, d[2], d[3])
+        dst_len, est = self.decode_slots(d, dst, work)
         # [B,5] lengths / statuses in container order (uniform: no salience column); a frame whose container was refused: status 1, no length
         plen = torch.zeros((B, 5), dtype=torch.int64, device=dev)
         pest = torch.ones((B, 5), dtype=torch.int32, device=dev)
@@ -524,9 +504,8 @@ class BatchDecompressor:
     def upload(self, blobs):
         """The containers' bytes on the device, a chunk per copy, for decompress_device(blobs, uploaded=...): callers that hold the containers
         in HBM already (the length prefixes are still read from the host copies)."""
-        from . import lz4_codec
         with torch.cuda.device(self.device):
-            return [lz4_codec._upload([lz4_codec._as_bytes(b) for b in blobs[c0: c0 + self.chunk]], self.device) for c0 in range(0, len(blobs), self.chunk)]
+            return [entropy.upload([entropy.as_bytes(b) for b in blobs[c0: c0 + self.chunk]], self.device) for c0 in range(0, len(blobs), self.chunk)]
 
     def decompress_device(self, blobs, want_points=True, uploaded=None):
         """blobs: .rpcc byte strings of one geometry and configuration (uploaded: what upload(blobs) returned, else they are copied up here).  -> (status i32 [B]: 0 or _lib.STREAM_E_*, seg [B,H,W], ri_rec f32 [B,H,W],

@@ -30,6 +30,7 @@ INFLATE_SRC, INFLATE_DEPS, INFLATE_LIB = _side_library("csrc_inflate", "inflate_
 BUNZIP2_SRC, BUNZIP2_DEPS, BUNZIP2_LIB = _side_library("csrc_bunzip2", "bunzip2_kernels.hip", "rpcc_bunzip2.h", "librpcc_bunzip2.so")   # bzip2 decoder
 BZIP2_SRC, BZIP2_DEPS, BZIP2_LIB = _side_library("csrc_bzip2", "bzip2_kernels.hip", "rpcc_bzip2.h", "librpcc_bzip2.so")   # bzip2 encoder
 FILTER_SRC, FILTER_DEPS, FILTER_LIB = _side_library("csrc_filter", "radius_filter.hip", "rpcc_filter.h", "librpcc_filter.so")   # radius outlier removal
+RANS_SRC, RANS_DEPS, RANS_LIB = _side_library("csrc_rans", "rans_kernels.hip", "rpcc_rans.h", "librpcc_rans.so")   # chunk-parallel rANS back-end
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -115,6 +116,11 @@ def build_filter(force=False, verbose=False):
     return _hipcc(FILTER_SRC, FILTER_LIB, FILTER_DEPS, force, verbose)
 
 
+def build_rans(force=False, verbose=False):
+    """librpcc_rans.so: the chunk-parallel rANS encode / decode kernels (csrc_rans/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(RANS_SRC, RANS_LIB, RANS_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -128,6 +134,7 @@ def build(force=False, verbose=False):
     build_bunzip2(force, verbose)
     build_bzip2(force, verbose)
     build_filter(force, verbose)
+    build_rans(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

@@ -1,5 +1,9 @@
 """Mirror of the reference's utils/compress_utils.py: QuantizationModule on the HIP path, payload
 packing, the .rpcc container and the entropy back-ends (stdlib calls, excluded from the measured path).
+
+basic_compressor 'rans' is not one of the reference's methods: it is the build's own chunk-parallel rANS format (rpcc_amd.rans_codec,
+DESIGN.md section 19), coded and read on the GPU only -- there is no host coder, the reference project cannot read such containers and
+neither can a machine without a GPU.
 """
 import bz2
 import collections
@@ -197,7 +201,8 @@ def decompress_point_cloud(compressed_data, basic_compressor, model_num, H, W):
     return residual_quantized, idx_map, salience, plane_param
 
 
-# One row per basic_compressor method: the host library's functions (None: the lz4 package, see BasicCompressor._lz4), the device encoder --
+# One row per basic_compressor method: the host library's functions (None: there is none, the device modules are used whatever the flags
+# say -- 'lz4' takes the lz4 package first where it is installed, see BasicCompressor._lz4), the device encoder --
 # module of this package, its list encoder, the BasicCompressor flag that turns it on -- and the device decoder alike; work_slots: its
 # decode_descriptors takes work slots.  The modules are imported where a row is used, not here.
 Backend = collections.namedtuple("Backend", "host_encode host_decode encoder encode_many encode_flag decoder decode_many decode_flag work_slots")
@@ -207,6 +212,7 @@ BACKENDS = {
     "bzip2": Backend(bz2.compress, bz2.decompress, "bzip2_codec", "compress_many", "device_bzip2", "bunzip2_codec", "decompress_many", "device_bunzip2", True),
     "gzip": _GZIP,
     "deflate": _GZIP,
+    "rans": Backend(None, None, "rans_codec", "compress_many", None, "rans_codec", "decompress_many", None, False),
 }
 
 
@@ -233,9 +239,10 @@ class BasicCompressor:
     device_bunzip2=True (opt-in, a flag of its own) decodes 'bzip2' streams through rpcc_amd.bunzip2_codec on the GPU, with
     bz2.decompress's bytes.  device_bzip2=True (opt-in, a flag of its own) encodes 'bzip2' through rpcc_amd.bzip2_codec on the GPU:
     valid bzip2 streams of the build's own bytes, read by the same bz2.decompress.  Without that flag 'bzip2' is
-    compressed by bz2.compress (or librpcc_host.so for a chunk of frames)."""
+    compressed by bz2.compress (or librpcc_host.so for a chunk of frames).  'rans' (the build's own format, not the reference's) is
+    rpcc_amd.rans_codec on the GPU in both directions, whatever the flags say: it has no host coder."""
 
-    METHODS = ["lz4", "bzip2", "gzip", "deflate"]
+    METHODS = ["lz4", "bzip2", "gzip", "deflate", "rans"]
 
     def __init__(self, compressor_yaml=None, method_name=None, device_entropy=False, device_bunzip2=False, device_bzip2=False):
         self.method_name = None
@@ -247,10 +254,10 @@ class BasicCompressor:
         if method_name is not None:
             self.method_name = method_name
         if self.method_name is not None:
-            assert self.method_name in self.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate)"
+            assert self.method_name in self.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate, rans)"
 
     def set_method(self, method_name):
-        assert method_name in self.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate)"
+        assert method_name in self.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate, rans)"
         self.method_name = method_name
 
     def _resolved(self):
@@ -260,9 +267,12 @@ class BasicCompressor:
         if be is None:
             return None, None, None, None
         host, on = (be.host_encode, be.host_decode), lambda flag: getattr(self, flag)
-        if be.host_encode is None:       # 'lz4': the lz4 package where it is installed, else lz4_codec on the device, whatever the flags say
-            pkg = self._lz4()
-            host, on = (lambda a: pkg.dumps(a.tobytes()), pkg.loads), lambda flag: pkg is _module(be.encoder)
+        if be.host_encode is None:       # no host function in the row: its device modules, whatever the flags say ('rans', and 'lz4' ...
+            pkg = self._lz4() if self.method_name == "lz4" else None      # ... unless the lz4 package is installed)
+            if pkg is not None and pkg is not _module(be.encoder):
+                host, on = (lambda a: pkg.dumps(a.tobytes()), pkg.loads), lambda flag: False
+            else:
+                on = lambda flag: True
         codec = (_module(be.encoder), getattr(_module(be.encoder), be.encode_many)) if on(be.encode_flag) else None
         decoder = getattr(_module(be.decoder), be.decode_many) if on(be.decode_flag) else None
         return (lambda a: codec[1]([a])[0]) if codec else host[0], (lambda s: decoder([s])[0]) if decoder else host[1], codec, decoder

@@ -1,6 +1,6 @@
-"""What the device entropy back-ends share on the host (DESIGN.md sections 11-15): staging a list of byte strings on the device, the
+"""What the device entropy back-ends share on the host (DESIGN.md sections 11-15, 19): staging a list of byte strings on the device, the
 slot layouts, the list drivers of the encoders and of the decoders, and the error of the first bad stream.  lz4_codec, deflate_codec,
-bzip2_codec, inflate_codec and bunzip2_codec keep what is their format's: bounds, status texts, sizing, retries and host fallbacks."""
+bzip2_codec, inflate_codec, bunzip2_codec and rans_codec keep what is their format's: bounds, status texts, sizing, retries and host fallbacks."""
 import numpy as np
 import torch
 

@@ -3,6 +3,7 @@ payload assembly (casts, container, entropy coder) of the reference's compress_p
 save_compressed_bitstream.  This is the counterpart of the closure body of
 tools/compress_datalist.py:91-142 for a whole batch at once.  BatchDecompressor is the way back: a list of .rpcc containers through one
 entropy launch and one fused decode call per chunk."""
+import inspect
 import struct
 
 import numpy as np
@@ -197,8 +198,9 @@ class BatchCompressor:
         return ctx
 
     def _device_containers(self, codec, B, buf, bits, nseq, sal, qp, sp):
-        """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), 'deflate' / 'gzip' with device_entropy (deflate_codec), or
-        'bzip2' with device_bzip2 (bzip2_codec):
+        """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), 'deflate' / 'gzip' with device_entropy (deflate_codec),
+        'bzip2' with device_bzip2 (bzip2_codec) or 'rans' (rans_codec, which is also told each column's element width, as the per-frame
+        path takes it from the arrays' itemsize):
         the batch's .rpcc containers are built in HBM (the codec's encode_descriptors over the arrays where they lie, then
         rpcc_lz4_pack_containers, which asks nothing of the streams' format) on the current stream.
         -> (containers, frame offsets / lengths)."""
@@ -210,16 +212,17 @@ class BatchCompressor:
         excl = lambda v: torch.cumsum(v, 0) - v
         rows = torch.arange(B, **i64)
         nb = bits.shape[1]
-        # per frame, in container order: (device address, bytes, host bound of the bytes)
-        cols = [(bits.data_ptr() + rows * nb, torch.full((B,), nb, **i64), nb),
-                (sp.data_ptr() + 2 * excl(ns), 2 * ns, 2 * P),
-                (buf.model.data_ptr() + rows * (K * 16), 16 * nrow, 16 * K),
-                (qp.data_ptr() + 2 * excl(nnz), 2 * nnz, 2 * P)]
+        # per frame, in container order: (device address, bytes, host bound of the bytes, element width)
+        cols = [(bits.data_ptr() + rows * nb, torch.full((B,), nb, **i64), nb, 1),
+                (sp.data_ptr() + 2 * excl(ns), 2 * ns, 2 * P, 2),
+                (buf.model.data_ptr() + rows * (K * 16), 16 * nrow, 16 * K, 4),
+                (qp.data_ptr() + 2 * excl(nnz), 2 * nnz, 2 * P, 2)]
         if sal is not None:
-            cols.insert(0, (sal.data_ptr() + rows * K, nrow, K))
+            cols.insert(0, (sal.data_ptr() + rows * K, nrow, K, 1))
         addr = torch.stack([c[0] for c in cols], 1).reshape(-1)
         lens = torch.stack([c[1] for c in cols], 1).reshape(-1)
-        slots, dst_off, dst_len, _ = codec.encode_descriptors(addr, lens, [c[2] for c in cols] * B)
+        kw = dict(widths=[c[3] for c in cols] * B) if "widths" in inspect.signature(codec.encode_descriptors).parameters else {}
+        slots, dst_off, dst_len, _ = codec.encode_descriptors(addr, lens, [c[2] for c in cols] * B, **kw)
         cap = int(slots.numel()) + 4 * len(cols) * B
         out, frame = lz4_codec.pack_containers(slots, dst_off, dst_len, B, len(cols), cap)
         return out, frame, (addr, lens, slots, dst_off, dst_len)
@@ -411,7 +414,7 @@ class BatchDecompressor:
             raise ValueError("BatchDecompressor: the non-uniform framework needs level_acc")
         self.level_acc = None if level_acc is None else [float(a) for a in level_acc]
         self.method = basic_compressor.method_name if isinstance(basic_compressor, BasicCompressor) else basic_compressor
-        assert self.method in BasicCompressor.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate)"
+        assert self.method in BasicCompressor.METHODS, "Compression method is not existed. (lz4, bzip2, gzip, deflate, rans)"
         self.host_bc = BasicCompressor(method_name=self.method)   # the E_ENTROPY fallback: the host library's decoder
         self.work_bytes, self.decode_slots = device_decoder(self.method)   # the device decoder, whatever the flags say
         P, K = transformer.H * transformer.W, self.M + 2

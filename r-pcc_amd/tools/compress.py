@@ -56,7 +56,8 @@ def make_parser(datalist=False):
                    help="per-beam elevation table of the lidar (columns channel, vertical_angle in degrees; row h of the range image = line h), "
                         "for beams that are not evenly spaced: e.g. lidar_cfg/Velodyne_HDL_64E_beams.csv with --lidar Velodyne64E.")
     p.add_argument("--compressor_yaml", default=os.path.join(PKG, "cfgs/compressor.yaml"))
-    p.add_argument("--basic_compressor", type=str, default=None, help="for manual setting.")
+    p.add_argument("--basic_compressor", type=str, default=None,
+                   help="for manual setting: lz4, bzip2, gzip, deflate, or rans (this build's chunk-parallel GPU format; the reference cannot read it).")
     p.add_argument("--device_entropy", action="store_true",
                    help="basic_compressor deflate / gzip: code the gzip members on the GPU (this build; other bytes, the same decoder).")
     p.add_argument("--device_bzip2", action="store_true",

@@ -12,6 +12,13 @@ ABI_VERSION = 1              # RPCC_RANS_ABI_VERSION
 MAX_INPUT = 0x7E000000       # RPCC_RANS_MAX_INPUT
 DEFAULT_CHUNK_LOG2 = 15      # RPCC_RANS_DEFAULT_CHUNK_LOG2
 OK, E_CAPACITY, E_HEADER, E_TRUNCATED, E_TABLE, E_DIRECTORY, E_STATE, E_PAYLOAD = 0, -1, -2, -3, -4, -5, -6, -7   # RPCC_RANS_OK / RPCC_RANS_E_*
+FILTER_NONE, FILTER_DELTA = 0, 1   # RPCC_RANS_FILTER_*
+
+
+def width_word(width, filter=FILTER_NONE):
+    """RPCC_RANS_WIDTH_WORD: the per-stream width word of rpcc_rans_encode -- the element size in bits 0-7, the filter in bits 8-15."""
+    return int(width) | int(filter) << 8
+
 
 _VP, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
 _SIGS = {

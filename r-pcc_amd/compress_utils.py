@@ -240,15 +240,18 @@ class BasicCompressor:
     bz2.decompress's bytes.  device_bzip2=True (opt-in, a flag of its own) encodes 'bzip2' through rpcc_amd.bzip2_codec on the GPU:
     valid bzip2 streams of the build's own bytes, read by the same bz2.decompress.  Without that flag 'bzip2' is
     compressed by bz2.compress (or librpcc_host.so for a chunk of frames).  'rans' (the build's own format, not the reference's) is
-    rpcc_amd.rans_codec on the GPU in both directions, whatever the flags say: it has no host coder."""
+    rpcc_amd.rans_codec on the GPU in both directions, whatever the flags say: it has no host coder.  rans_delta=True (opt-in, 'rans'
+    only; nothing with any other method) codes the arrays rans_codec.delta_filter names -- the int16 residuals -- through the delta
+    filter (format version 2); decoding takes no flag, both versions are read."""
 
     METHODS = ["lz4", "bzip2", "gzip", "deflate", "rans"]
 
-    def __init__(self, compressor_yaml=None, method_name=None, device_entropy=False, device_bunzip2=False, device_bzip2=False):
+    def __init__(self, compressor_yaml=None, method_name=None, device_entropy=False, device_bunzip2=False, device_bzip2=False, rans_delta=False):
         self.method_name = None
         self.device_entropy = bool(device_entropy)
         self.device_bunzip2 = bool(device_bunzip2)
         self.device_bzip2 = bool(device_bzip2)
+        self.rans_delta = bool(rans_delta)
         if compressor_yaml is not None:
             self.method_name = load_yaml(compressor_yaml)["basic_compressor"]
         if method_name is not None:
@@ -274,6 +277,8 @@ class BasicCompressor:
             else:
                 on = lambda flag: True
         codec = (_module(be.encoder), getattr(_module(be.encoder), be.encode_many)) if on(be.encode_flag) else None
+        if self.method_name == "rans" and self.rans_delta:    # the same module's list encoder with the delta filter where its rule gives one
+            codec = (codec[0], codec[0].compress_many_delta)
         decoder = getattr(_module(be.decoder), be.decode_many) if on(be.decode_flag) else None
         return (lambda a: codec[1]([a])[0]) if codec else host[0], (lambda s: decoder([s])[0]) if decoder else host[1], codec, decoder
 

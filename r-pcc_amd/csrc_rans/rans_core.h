@@ -1,5 +1,5 @@
-// rans_core.h -- the 'rans' stream format, version 1 (tests/rans_ref.py is its statement in Python): the
-// normalisation rule, the parsing of header, tables and directory, and the coding of one chunk by one wavefront.  rans_kernels.hip includes
+// rans_core.h -- the 'rans' stream format, versions 1 and 2 (tests/rans_ref.py and tests/rans_filter_ref.py are
+// its statements in Python; version 2 is version 1's coded form over filtered bytes, rans_filter.h): the normalisation rule, the parsing of header, tables and directory, and the coding of one chunk by one wavefront.  rans_kernels.hip includes
 // it for gfx950 and tests/rans_host_main.cpp for the host; the including file defines how the 64 lanes are spoken to:
 //   RANS_FN             function qualifiers
 //   RANS_NL             lanes one thread of control carries: 1 on the device (the hardware runs the 64), 64 on the host
@@ -42,10 +42,17 @@ RANS_FN void rans_st16(uint8_t *p, uint32_t v) {
 }
 RANS_FN void rans_st32(uint8_t *p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
 
+#include "rans_filter.h"
+
 RANS_FN void rans_put_header(uint8_t *o, uint32_t mode, uint32_t width, uint32_t n, uint32_t chunk_log2) {
     o[0] = 'R', o[1] = 'A', o[2] = (uint8_t)mode, o[3] = (uint8_t)width;
     rans_st32(o + 4, n);
     o[8] = (uint8_t)chunk_log2, o[9] = 0, o[10] = 0, o[11] = 0;
+}
+// The version-2 header: magic 'R' 'B', always coded (mode 1), the filter in byte 9.
+RANS_FN void rans_put_header_filtered(uint8_t *o, uint32_t width, uint32_t n, uint32_t chunk_log2, uint32_t filter) {
+    rans_put_header(o, 1, width, n, chunk_log2);
+    o[1] = 'B', o[9] = (uint8_t)filter;
 }
 
 // Bytes of plane p in a stream of n bytes.
@@ -130,6 +137,7 @@ RANS_FN void rans_normalise(const int lane, const uint32_t *counts, const uint64
 // ------------------------------------------------------------------------------------------------
 struct RansInfo {
     uint32_t mode, width, n, chunk_log2, nch;
+    uint32_t filter;        // RANS_FILTER_*: 0 for every 'RA' stream
     uint32_t m[4];          // symbols of each plane's table
     int64_t tab[4];         // where each plane's entries start
     int64_t dir, pay;       // where the directory and the first payload start
@@ -139,6 +147,7 @@ struct RansInfo {
 RANS_FN bool rans_read_header(const uint8_t *in, int64_t len, RansInfo &I) {
     if (len < RANS_HEADER) return false;
     I.mode = in[2], I.width = in[3], I.n = rans_ld32(in + 4), I.chunk_log2 = in[8];
+    I.filter = in[1] == 'B' ? in[9] : RANS_FILTER_NONE;
     return true;
 }
 
@@ -146,8 +155,10 @@ RANS_FN bool rans_read_header(const uint8_t *in, int64_t len, RansInfo &I) {
 RANS_FN int rans_parse(const int lane, const uint8_t *in, const int64_t len, const int64_t cap, RansInfo &I) {
     (void)lane;
     if (!rans_read_header(in, len, I)) return RPCC_RANS_E_TRUNCATED;
-    if (in[0] != 'R' || in[1] != 'A' || I.mode > 1 || !(I.width == 1 || I.width == 2 || I.width == 4) || I.chunk_log2 < RANS_MIN_CHUNK_LOG2 ||
-        I.chunk_log2 > RANS_MAX_CHUNK_LOG2 || in[9] || in[10] || in[11] || I.n > RPCC_RANS_MAX_INPUT || (I.mode == 1 && I.n == 0))
+    // 'RA': byte 9 is reserved; 'RB': byte 9 is the filter and must be 1, and the stream is coded (there is no stored form)
+    const bool v2 = in[1] == 'B';
+    if (in[0] != 'R' || (in[1] != 'A' && !v2) || I.mode > 1 || (v2 && (I.mode != 1 || in[9] != RANS_FILTER_DELTA)) || !(I.width == 1 || I.width == 2 || I.width == 4) || I.chunk_log2 < RANS_MIN_CHUNK_LOG2 ||
+        I.chunk_log2 > RANS_MAX_CHUNK_LOG2 || (!v2 && in[9]) || in[10] || in[11] || I.n > RPCC_RANS_MAX_INPUT || (I.mode == 1 && I.n == 0))
         return RPCC_RANS_E_HEADER;
     if ((int64_t)I.n > cap) return RPCC_RANS_E_CAPACITY;
     I.nch = 0;
@@ -286,8 +297,10 @@ RANS_FN int rans_decode_chunk(const int lane, const uint8_t *pay, const uint32_t
 }
 
 // Codes the k bytes at src into the payload that ends at slot_end (the words are written backwards from there, the states in front of
-// them once their count is known; at most 2 k + 256 bytes).  enc: [width][256][2] rans_enc_entry.  -> the payload's length.
-RANS_FN uint32_t rans_encode_chunk(const int lane, const uint8_t *src, const uint32_t k, const uint32_t width, const uint32_t *enc, uint8_t *slot_end) {
+// them once their count is known; at most 2 k + 256 bytes).  enc: [width][256][2] rans_enc_entry.  filter (the same in every lane):
+// RANS_FILTER_DELTA reads the bytes through the forward filter as they are loaded.  -> the payload's length.
+RANS_FN uint32_t rans_encode_chunk_filtered(const int lane, const uint8_t *src, const uint32_t k, const uint32_t width, const uint32_t filter,
+                                            const uint32_t *enc, uint8_t *slot_end) {
     (void)lane;
     const uint32_t L = k < RANS_LANES ? k : RANS_LANES, R = (k + RANS_LANES - 1) / RANS_LANES;
     uint32_t x[RANS_NL], wv[RANS_NL];
@@ -297,11 +310,32 @@ RANS_FN uint32_t rans_encode_chunk(const int lane, const uint8_t *src, const uin
     uint32_t total = 0;
     for (uint32_t r1 = R; r1 > 0;) {           // rounds [r0, r1), last to first; r0 a multiple of RANS_ENC_BLOCK
         const uint32_t r0 = (r1 - 1) / RANS_ENC_BLOCK * RANS_ENC_BLOCK;
-        RANS_EACH(l) {
+        if (filter == RANS_FILTER_NONE) {
+            RANS_EACH(l) {
 #pragma unroll
-            for (uint32_t j = 0; j < RANS_ENC_BLOCK; ++j) {
-                const uint32_t i = (r0 + j) * RANS_LANES + (uint32_t)l;
-                RANS_AT(b, l)[j] = i < k ? src[i] : 0;
+                for (uint32_t j = 0; j < RANS_ENC_BLOCK; ++j) {
+                    const uint32_t i = (r0 + j) * RANS_LANES + (uint32_t)l;
+                    RANS_AT(b, l)[j] = i < k ? src[i] : 0;
+                }
+            }
+        } else if (r0 > 0 && (r0 + RANS_ENC_BLOCK) * RANS_LANES <= k - (k & (width - 1))) {
+            // every byte of the block in a whole element behind the chunk's first: loads without conditions, the width a literal
+#define RANS_DELTA_BLOCK(W)                                                                              \
+    RANS_EACH(l) {                                                                                       \
+        _Pragma("unroll") for (uint32_t j = 0; j < RANS_ENC_BLOCK; ++j)                                  \
+            RANS_AT(b, l)[j] = (uint8_t)rans_delta_byte_inner(src, (r0 + j) * RANS_LANES + (uint32_t)l, W); \
+    }
+            if (width == 2) RANS_DELTA_BLOCK(2)
+            else if (width == 4) RANS_DELTA_BLOCK(4)
+            else RANS_DELTA_BLOCK(1)
+#undef RANS_DELTA_BLOCK
+        } else {                                      // the chunk's first block and its last
+            RANS_EACH(l) {
+#pragma unroll
+                for (uint32_t j = 0; j < RANS_ENC_BLOCK; ++j) {
+                    const uint32_t i = (r0 + j) * RANS_LANES + (uint32_t)l;
+                    RANS_AT(b, l)[j] = i < k ? (uint8_t)rans_delta_byte(src, i, k, width) : 0;
+                }
             }
         }
 #pragma unroll
@@ -337,6 +371,9 @@ RANS_FN uint32_t rans_encode_chunk(const int lane, const uint8_t *src, const uin
         if ((uint32_t)l < L) rans_st32(slot_end - 2 * (int64_t)total - 4 * (int64_t)L + 4 * l, RANS_AT(x, l));
     }
     return 4 * L + 2 * total;
+}
+RANS_FN uint32_t rans_encode_chunk(const int lane, const uint8_t *src, const uint32_t k, const uint32_t width, const uint32_t *enc, uint8_t *slot_end) {
+    return rans_encode_chunk_filtered(lane, src, k, width, RANS_FILTER_NONE, enc, slot_end);
 }
 
 #endif  // RPCC_RANS_CORE_H

@@ -13,6 +13,11 @@
 // status of a stream's chunks joining its status, then decoded again with stores for the streams that are still OK -- so a refused stream
 // writes nothing.  The entry has rpcc_lz4_decode's signature and so no capacity the host knows: the grid is DEC_GROUPS workgroups by
 // nstreams, a workgroup leaves at once when its stream has no group for it and strides on when the stream has more.
+//
+// Version 2 (the delta filter, csrc_rans/rans_filter.h) keeps every launch and the work buffer: the histogram and the chunk encoder read
+// their input through the forward filter as they load it (a lane's element and the one before it: no filtered copy exists anywhere), the
+// assembly writes the 'RB' header where such a stream is coded, and the decoder's storing pass has the wave that stored a chunk undo
+// the filter over it in place (a scan per 256 bytes); the checking pass and the validation read both versions alike.
 #include "../../include/rpcc_rans.h"
 #include "../csrc_tile/tiles.h"
 
@@ -26,6 +31,18 @@ __device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
     return v;
 }
+// Inclusive sum over lanes 0 .. lane, all 64 lanes active.  DPP: four shifts within the rows of 16 (lanes shifted in from outside a row
+// read 0), then lane 15 of rows 0 and 2 added to rows 1 and 3 (row_bcast:15, row mask 0xA) and lane 31 to rows 2 and 3 (row_bcast:31,
+// row mask 0xC); a row that is masked out adds the `old` operand, 0.
+__device__ __forceinline__ uint32_t wave_scan32(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31
+    return v;
+}
 
 #define RANS_FN __device__ __forceinline__
 #define RANS_NL 1
@@ -34,7 +51,9 @@ __device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
 #define RANS_BALLOT(a) ((uint64_t)__ballot((a)[0] != 0))
 #define RANS_SUM64(a) wave_sum64((a)[0])
 #define RANS_MAX32(a) wave_max32((a)[0])
-#define RANS_SYNC()                                          \
+#define RANS_SCAN32(a) ((a)[0] = wave_scan32((a)[0]))
+#define RANS_LAST32(a) ((uint32_t)__shfl((int)(a)[0], 63))
+#define RANS_SYNC()                                         \
     do {                                                     \
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); \
         __builtin_amdgcn_wave_barrier();                     \
@@ -110,7 +129,10 @@ static EncWs enc_layout(void *ws, int64_t nstreams, int64_t total, int clog) {
     return W;
 }
 
-__device__ __forceinline__ int32_t width_of(const int32_t *width, int64_t s) { return width ? width[s] : 1; }
+// A stream's width word (rpcc_rans.h): bits 0-7 the element size, bits 8-15 the filter; plan_kernel takes only words whose other bits are 0.
+__device__ __forceinline__ int32_t word_of(const int32_t *width, int64_t s) { return width ? width[s] : 1; }
+__device__ __forceinline__ int32_t width_of(const int32_t *width, int64_t s) { return RPCC_RANS_WIDTH_OF(word_of(width, s)); }
+__device__ __forceinline__ uint32_t filter_of(const int32_t *width, int64_t s) { return (uint32_t)RPCC_RANS_FILTER_OF(word_of(width, s)); }
 __device__ __forceinline__ uint32_t chunks_of(uint32_t n, int clog) { return (uint32_t)(((uint64_t)n + (1u << clog) - 1) >> clog); }
 
 // One workgroup: mode[s] = -1 and dst_len[s] = E_CAPACITY for a stream that is not taken; gbase = the exclusive scan of the taken streams'
@@ -128,8 +150,9 @@ __global__ __launch_bounds__(1024) void plan_kernel(const int64_t *__restrict__ 
         bool ok = false;
         if (s < nstreams) {
             const int64_t n = src_len[s];
-            const int32_t w = width_of(width, s);
-            ok = n >= 0 && n <= RPCC_RANS_MAX_INPUT && (w == 1 || w == 2 || w == 4) && dst_cap[s] >= RANS_HEADER + n;
+            const int32_t word = word_of(width, s), w = RPCC_RANS_WIDTH_OF(word), f = RPCC_RANS_FILTER_OF(word);
+            ok = n >= 0 && n <= RPCC_RANS_MAX_INPUT && word == RPCC_RANS_WIDTH_WORD(w, f) && (w == 1 || w == 2 || w == 4) &&
+                 (f == RPCC_RANS_FILTER_NONE || f == RPCC_RANS_FILTER_DELTA) && dst_cap[s] >= RANS_HEADER + n;
             if (ok) g = (chunks_of((uint32_t)n, clog) + GROUP - 1) / GROUP;
         }
         part[threadIdx.x] = g;
@@ -179,12 +202,14 @@ __global__ __launch_bounds__(THREADS) void hist_kernel(const uint64_t *__restric
     if (c < chunks_of(n, clog)) {
         const uint8_t *__restrict__ src = (const uint8_t *)src_ptr[s] + ((size_t)c << clog);
         const uint32_t k = min(1u << clog, n - (c << clog));
+        const bool delta = filter_of(width, s) == RANS_FILTER_DELTA;   // the bytes are counted as the coder will see them: through the filter
         for (uint32_t x = 4 * lane; x + 4 <= k; x += 256) {     // x is a multiple of 4: byte x + j is in plane j mod width
-            const uint32_t v = rans_ld32(src + x);
+            uint32_t v = rans_ld32(src + x);
+            if (delta) v = rans_delta_dword(v, x ? rans_ld_elem(src + x - wd, wd) : 0u, wd);
             for (uint32_t j = 0; j < 4; ++j) atomicAdd(&h[j & (wd - 1)][(v >> (8 * j)) & 255u], 1u);
         }
         const uint32_t x = (k & ~3u) + lane;
-        if (x < k) atomicAdd(&h[x & (wd - 1)][src[x]], 1u);
+        if (x < k) atomicAdd(&h[x & (wd - 1)][delta ? rans_delta_byte(src, x, k, wd) : src[x]], 1u);
     }
     __syncthreads();
     for (uint32_t p = 0; p < wd; ++p)
@@ -222,7 +247,8 @@ __global__ __launch_bounds__(THREADS) void enc_kernel(const uint64_t *__restrict
     if (c >= chunks_of(n, clog)) return;
     const size_t slot = (size_t)blockIdx.x * GROUP + wave;
     const uint32_t k = min(1u << clog, n - (c << clog));
-    const uint32_t len = rans_encode_chunk(lane, (const uint8_t *)src_ptr[s] + ((size_t)c << clog), k, wd, enc, W.scratch + (slot + 1) * SLOT_BYTES(clog));
+    const uint32_t len = rans_encode_chunk_filtered(lane, (const uint8_t *)src_ptr[s] + ((size_t)c << clog), k, wd, filter_of(width, s), enc,
+                                                    W.scratch + (slot + 1) * SLOT_BYTES(clog));
     if (lane == 0) W.clen[slot] = len;
 }
 
@@ -254,7 +280,9 @@ __global__ __launch_bounds__(THREADS) void assemble_kernel(const int64_t *__rest
     }
     const bool coded = n > 0 && head + paid < RANS_HEADER + (uint64_t)n;
     if (tid == 0) {
-        rans_put_header(out, coded, wd, n, clog);
+        const uint32_t filter = filter_of(width, s);      // a filtered stream that does not shrink is the version-1 stored stream
+        if (coded && filter != RANS_FILTER_NONE) rans_put_header_filtered(out, wd, n, clog, filter);
+        else rans_put_header(out, coded, wd, n, clog);
         W.mode[s] = coded;
         W.pay[s] = (uint32_t)head;
         dst_len[s] = coded ? (int64_t)(head + paid) : RANS_HEADER + (int64_t)n;
@@ -375,8 +403,13 @@ __global__ __launch_bounds__(THREADS) void dec_kernel(const uint64_t *__restrict
     __syncthreads();
     for (uint32_t c = blockIdx.x * GROUP + wave; c < nch; c += DEC_GROUPS * GROUP) {
         const int64_t at = rans_chunk_offset(lane, in, I, c);
-        const int st = rans_decode_chunk(lane, in + at, rans_ld32(in + I.dir + 4 * (int64_t)c), min(size, I.n - c * size), I.width, S.lookup, S.fc,
-                                         S.ring[wave], WRITE ? out + (size_t)c * size : nullptr);
+        const uint32_t k = min(size, I.n - c * size);
+        const int st = rans_decode_chunk(lane, in + at, rans_ld32(in + I.dir + 4 * (int64_t)c), k, I.width, S.lookup, S.fc, S.ring[wave],
+                                         WRITE ? out + (size_t)c * size : nullptr);
+        if (WRITE && I.filter == RANS_FILTER_DELTA) {   // version 2: the wave undoes the filter over the chunk it has just stored
+            RANS_SYNC();
+            rans_unfilter_chunk(lane, out + (size_t)c * size, k, I.width);
+        }
         if (!WRITE && st != RPCC_RANS_OK && lane == 0) {
             atomicMin(&status[s], st);
             dst_len[s] = 0;

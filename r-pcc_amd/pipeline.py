@@ -20,8 +20,10 @@ class BatchCompressor:
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
                  model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
                  device_entropy=False, device_bzip2=False, segment_method="FPS", DBSCAN_eps=1.5, max_labels=None,
-                 radius_outlier_removal=None):
-        """segment_method "DBSCAN" (cfgs/compressor.yaml: segment_method, DBSCAN_eps): the frames are segmented by dbscan.dbscan_segment and
+                 radius_outlier_removal=None, rans_delta=False):
+        """rans_delta (basic_compressor 'rans' only): the residual stream goes through the delta filter, as BasicCompressor(rans_delta=True)
+        codes it on the per-frame path.
+        segment_method "DBSCAN" (cfgs/compressor.yaml: segment_method, DBSCAN_eps): the frames are segmented by dbscan.dbscan_segment and
         enter the batch kernels through ops.compress_batch_labels; cluster_num does not apply (tools/compress.py).  max_labels: the labels a
         frame may use, 0 .. max_labels (default RPCC_MAX_CLUSTERS_MID + 1 = 1023, where the per-frame path raises too; up to 255: byte labels
         on the device); a frame with more makes collect() raise.
@@ -57,7 +59,8 @@ class BatchCompressor:
         self.uniform = uniform
         self.model_method = model_method
         self.cfg = compressor_cfg or {}
-        self.bc = BasicCompressor(method_name=basic_compressor, device_entropy=device_entropy, device_bzip2=device_bzip2)
+        self.bc = BasicCompressor(method_name=basic_compressor, device_entropy=device_entropy, device_bzip2=device_bzip2,
+                                  rans_delta=rans_delta)
         self.seed = int(seed)
         self._buf = None        # the buffers of the most recent call (tests read them after compress())
         self._codec_ws = None
@@ -200,7 +203,7 @@ class BatchCompressor:
     def _device_containers(self, codec, B, buf, bits, nseq, sal, qp, sp):
         """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), 'deflate' / 'gzip' with device_entropy (deflate_codec),
         'bzip2' with device_bzip2 (bzip2_codec) or 'rans' (rans_codec, which is also told each column's element width, as the per-frame
-        path takes it from the arrays' itemsize):
+        path takes it from the arrays' itemsize, and -- with rans_delta -- each column's filter, by the same rule from its dtype):
         the batch's .rpcc containers are built in HBM (the codec's encode_descriptors over the arrays where they lie, then
         rpcc_lz4_pack_containers, which asks nothing of the streams' format) on the current stream.
         -> (containers, frame offsets / lengths)."""
@@ -212,16 +215,19 @@ class BatchCompressor:
         excl = lambda v: torch.cumsum(v, 0) - v
         rows = torch.arange(B, **i64)
         nb = bits.shape[1]
-        # per frame, in container order: (device address, bytes, host bound of the bytes, element width)
-        cols = [(bits.data_ptr() + rows * nb, torch.full((B,), nb, **i64), nb, 1),
-                (sp.data_ptr() + 2 * excl(ns), 2 * ns, 2 * P, 2),
-                (buf.model.data_ptr() + rows * (K * 16), 16 * nrow, 16 * K, 4),
-                (qp.data_ptr() + 2 * excl(nnz), 2 * nnz, 2 * P, 2)]
+        # per frame, in container order: (device address, bytes, host bound of the bytes, element width, dtype as the per-frame path codes it)
+        cols = [(bits.data_ptr() + rows * nb, torch.full((B,), nb, **i64), nb, 1, np.uint8),
+                (sp.data_ptr() + 2 * excl(ns), 2 * ns, 2 * P, 2, np.uint16),
+                (buf.model.data_ptr() + rows * (K * 16), 16 * nrow, 16 * K, 4, np.float32),
+                (qp.data_ptr() + 2 * excl(nnz), 2 * nnz, 2 * P, 2, np.int16)]
         if sal is not None:
-            cols.insert(0, (sal.data_ptr() + rows * K, nrow, K, 1))
+            cols.insert(0, (sal.data_ptr() + rows * K, nrow, K, 1, np.uint8))
         addr = torch.stack([c[0] for c in cols], 1).reshape(-1)
         lens = torch.stack([c[1] for c in cols], 1).reshape(-1)
-        kw = dict(widths=[c[3] for c in cols] * B) if "widths" in inspect.signature(codec.encode_descriptors).parameters else {}
+        takes = inspect.signature(codec.encode_descriptors).parameters
+        kw = dict(widths=[c[3] for c in cols] * B) if "widths" in takes else {}
+        if "filters" in takes and self.bc.rans_delta:      # delta for the residual column only (rans_codec.delta_filter)
+            kw["filters"] = [codec.delta_filter(c[4]) for c in cols] * B
         slots, dst_off, dst_len, _ = codec.encode_descriptors(addr, lens, [c[2] for c in cols] * B, **kw)
         cap = int(slots.numel()) + 4 * len(cols) * B
         out, frame = lz4_codec.pack_containers(slots, dst_off, dst_len, B, len(cols), cap)

@@ -62,6 +62,9 @@ def make_parser(datalist=False):
                    help="basic_compressor deflate / gzip: code the gzip members on the GPU (this build; other bytes, the same decoder).")
     p.add_argument("--device_bzip2", action="store_true",
                    help="basic_compressor bzip2: code the bzip2 streams on the GPU (this build; other bytes, the same decoder).")
+    p.add_argument("--rans_delta", action="store_true",
+                   help="compress tools, basic_compressor rans: code the residuals through the delta filter (format version 2: a container "
+                        "about 0.4 times the size; the decompress tools read both versions and need no flag).")
     p.add_argument("--device_bunzip2", action="store_true",
                    help="decompress tools, basic_compressor bzip2: decode the bzip2 streams on the GPU (this build; bz2.decompress's bytes).")
     p.add_argument("--accuracy", type=float, default=None, help="for manual setting.")
@@ -103,7 +106,8 @@ def resolve_cfg(args):
                    "cluster_num": cfg["cluster_num"], "DBSCAN_eps": cfg["DBSCAN_eps"]}
     model_cfg = {"model_method": cfg["modeling_method"], "angle_threshold": cfg["plane_angle_threshold"]}
     bc = BasicCompressor(compressor_yaml=args.compressor_yaml, device_entropy=getattr(args, "device_entropy", False),
-                         device_bunzip2=getattr(args, "device_bunzip2", False), device_bzip2=getattr(args, "device_bzip2", False))
+                         device_bunzip2=getattr(args, "device_bunzip2", False), device_bzip2=getattr(args, "device_bzip2", False),
+                         rans_delta=getattr(args, "rans_delta", False))
     if args.basic_compressor is not None:
         bc.set_method(args.basic_compressor)
     if args.accuracy is not None:
@@ -150,7 +154,8 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
     bc = BatchCompressor(dataset.PCTransformer, cluster_num=segment_cfg["cluster_num"], accuracy=accuracy / 2,
                          ground_threshold=segment_cfg["ground_vertical_threshold"], uniform=uniform, model_method=model_cfg["model_method"],
                          compressor_cfg=dict(cfg), basic_compressor=basic_compressor.method_name, seed=args.seed,
-                         device_entropy=basic_compressor.device_entropy, device_bzip2=basic_compressor.device_bzip2)
+                         device_entropy=basic_compressor.device_entropy, device_bzip2=basic_compressor.device_bzip2,
+                         rans_delta=basic_compressor.rans_delta)
     blob = bc.compress([frame], frame_ids=[frame_identity(args.input)])[0]
     with open(args.output, "wb") as f:
         f.write(blob)

@@ -106,6 +106,7 @@ def compress(args, streaming_factory=None):
                          model_method=model_cfg["model_method"], compressor_cfg=dict(cfg),
                          basic_compressor=basic_compressor.method_name, seed=args.seed,
                          device_entropy=basic_compressor.device_entropy, device_bzip2=basic_compressor.device_bzip2,
+                         rans_delta=basic_compressor.rans_delta,
                          segment_method=segment_cfg["segment_method"], DBSCAN_eps=segment_cfg["DBSCAN_eps"],
                          max_labels=getattr(args, "max_labels", None),
                          radius_outlier_removal=(3, 1.0) if getattr(args, "use_radius_outlier_removal", False) else None)

@@ -1,12 +1,12 @@
-"""GPU: basic_compressor 'rans' beside 'lz4' (the fastest of the other device back-ends in every row, and untouched by the rans work), in one
-process on one GPU.  Inputs as in tools_dev/codec_times.py and tools_dev/decode_times.py: the four payload arrays and the containers of 256
+"""GPU: basic_compressor 'rans', without and with rans_delta (the delta filter on the int16 residuals, format version 2), beside 'lz4' (the
+fastest of the other device back-ends in every row, and untouched by the rans work), in one process on one GPU.  Inputs as in tools_dev/codec_times.py and tools_dev/decode_times.py: the four payload arrays and the containers of 256
 copies of the example sweep (tests/golden/example_64E.npz: 64 x 2000, 100 clusters, uniform framework) -- 1024 streams.
   1. encode and decode of the 1024 streams with everything resident in HBM (encode_tensors; decode_descriptors into a buffer made before);
   2. compress_many / decompress_many (lz4: dumps_many / loads_many), host bytes in, host bytes out;
   3. BatchCompressor and BatchDecompressor, frames/s, host to host and resident (points / containers uploaded before the clock starts);
   4. one frame's four streams alone, resident, beside bz2 and zlib on the host for the same four arrays;
-  5. container bytes of the example sweep under lz4, deflate, bzip2 and rans at chunk_log2 14 / 15 / 16.
-Wall clock from the call to a device synchronise, one warm-up, then RUNS runs with the two back-ends taking turns: median (min - max).
+  5. container bytes of the example sweep under lz4, deflate, bzip2 and rans without and with the filter at chunk_log2 14 / 15 / 16.
+Wall clock from the call to a device synchronise, one warm-up, then RUNS runs with the back-ends taking turns: median (min - max).
 Usage: python tools_dev/rans_times.py [--frames 256] [--runs 3]"""
 import argparse
 import bz2
@@ -14,6 +14,8 @@ import os
 import sys
 import time
 import zlib
+
+import types
 
 import numpy as np
 import torch
@@ -70,11 +72,19 @@ frame = [np.frombuffer(bz2.decompress(v), DTYPES[k]) for k, v in unpack_bitstrea
 arrays = frame * B
 raw = sum(a.nbytes for a in frame)
 print("one frame: %d streams, %d bytes (%s); %d streams in all" % (len(frame), raw, ", ".join("%s %d" % (k, a.nbytes) for k, a in zip(DTYPES, frame)), len(arrays)))
-CODECS = {"rans": (rans_codec, rans_codec.compress_many, rans_codec.decompress_many), "lz4": (lz4_codec, lz4_codec.dumps_many, lz4_codec.loads_many)}
+# 'rans delta': rans_codec with the filter where its rule gives one (the arrays' dtypes: the tensors below are made from them)
+_NP = {torch.uint8: np.uint8, torch.int16: np.int16, torch.uint16: np.uint16, torch.float32: np.float32}
+rans_delta = types.SimpleNamespace(
+    encode_tensors=lambda ts: rans_codec.encode_tensors(ts, filters=[rans_codec.delta_filter(_NP[t.dtype]) for t in ts]),
+    decode_descriptors=rans_codec.decode_descriptors)
+CODECS = {"rans": (rans_codec, rans_codec.compress_many, rans_codec.decompress_many),
+          "rans delta": (rans_delta, rans_codec.compress_many_delta, rans_codec.decompress_many),
+          "lz4": (lz4_codec, lz4_codec.dumps_many, lz4_codec.loads_many)}
+METHOD = {"rans": ("rans", {}), "rans delta": ("rans", dict(rans_delta=True)), "lz4": ("lz4", {})}     # BatchCompressor's arguments
 
 
 def resident(arrs):
-    """-> {name: callable} of the resident encode and decode of arrs for both back-ends (checked once against the arrays)."""
+    """-> {name: callable} of the resident encode and decode of arrs for every back-end (checked once against the arrays)."""
     paths, keep = {}, []
     tensors = [torch.from_numpy(a.copy()).to(dev) for a in arrs]
     for name, (codec, comp, decomp) in CODECS.items():
@@ -113,8 +123,8 @@ print("\n## 3. batch pipelines, %d frames" % B)
 frames, ids = [xyz] * B, list(range(B))
 paths, blobs, keep = {}, {}, []
 for name in CODECS:
-    bc = pipeline.BatchCompressor(T, cluster_num=M, accuracy=ACC, basic_compressor=name, seed=1)
-    bd = pipeline.BatchDecompressor(T, M, 2 * ACC, basic_compressor=name)
+    bc = pipeline.BatchCompressor(T, cluster_num=M, accuracy=ACC, basic_compressor=METHOD[name][0], seed=1, **METHOD[name][1])
+    bd = pipeline.BatchDecompressor(T, M, 2 * ACC, basic_compressor=METHOD[name][0])
     blobs[name] = bc.compress(frames, frame_ids=ids)
     gx, goffs, _, npts = bc._upload(frames)
     up = bd.upload(blobs[name])
@@ -153,8 +163,12 @@ for name, flags in (("lz4", {}), ("deflate", {}), ("bzip2", {})):
 for clog in (14, 15, 16):
     parts = rans_codec.compress_many(frame, chunk_log2=clog)
     sizes["rans, chunk_log2 %d" % clog] = sum(4 + len(s) for s in parts)
+    delta = rans_codec.compress_many_delta(frame, chunk_log2=clog)
+    sizes["rans delta, chunk_log2 %d" % clog] = sum(4 + len(s) for s in delta)
     if clog == 15:
-        print("rans streams at chunk_log2 15:", ", ".join("%s %d (%s)" % (k, len(s), "coded" if s[2] else "stored") for k, s in zip(DTYPES, parts)))
-        assert sizes["rans, chunk_log2 15"] == len(blobs["rans"][0])
+        for what, ps in (("rans", parts), ("rans delta", delta)):
+            print("%s streams at chunk_log2 15:" % what, ", ".join("%s %d (%s %s)" % (k, len(s), s[:2].decode(), "coded" if s[2] else "stored")
+                                                                     for k, s in zip(DTYPES, ps)))
+        assert sizes["rans, chunk_log2 15"] == len(blobs["rans"][0]) and sizes["rans delta, chunk_log2 15"] == len(blobs["rans delta"][0])
 for k, v in sizes.items():
     print("| %s | %d | %.3f of bzip2 |" % (k, v, v / sizes["bzip2"]), flush=True)

@@ -145,6 +145,38 @@ int rpcc_project_beams(const float *points, int point_stride_bytes, const int64_
                        const void *beams_dev, float *ri, void *scratch, size_t scratch_bytes, void *stream);
 int rpcc_project_beams_check(const float *xyz, int64_t total, rpcc_geom g, const void *beams_dev, uint64_t *counts, void *stream);
 
+/* ---- intensity: the fourth column of the stored rows, one byte per non-empty pixel ------------- *
+ * The reference drops the column (dataset/dataset.py:62); these entries carry it beside the geometry.  The specification is stated
+ * once, in tests/intensity_ref.py (added under interface version 105: new exports only, no existing struct or argument changes):
+ *   owner     per frame, rows i = 0 .. N-1 in input order: d_i = sqrtf(x*x + y*y + z*z) un-fused, rows of non-finite d_i skipped, pix_i the
+ *             pixel of rpcc_project.  The reference's loop `if (ri[pix] == 0 || d < ri[pix]) ri[pix] = d` gains `own[pix] = i`; a pixel is
+ *             non-empty iff its final ri != 0 and its owner is the final own.  In closed form: z = the last i with pix_i == pix and
+ *             d_i == 0 (or -1); the owner is the smallest i > z with pix_i == pix and the bits of d_i equal to the bits of ri[pix].
+ *   quantise  r = rintf(w * scale) (one fp32 multiply, half to even); q = 0 unless r >= 0 (NaN, negatives), 255 if r > 255, else (uint8)r
+ *   dequant   w' = (float)q / scale, one correctly rounded fp32 division (scale 100 returns a KITTI sweep's k / 100 bit for bit)
+ *   payload   8 + n bytes: "RPI1", scale as little-endian f32, then q of the non-empty pixels in ascending pixel index; n = pixels with
+ *             ri != 0 = pixels whose label is not 1, which is what the decoder has
+ * rpcc_intensity_encode: rows dev f32 [total,4] (16-byte aligned), offsets dev i64 [B+1], ri dev f32 [B,P] the image rpcc_project made of
+ * these rows; scale finite and > 0.  Out: payload dev u8 rows of payload_stride >= 8 + P bytes (frame b: 8 + n_b bytes are written, the rest
+ * is left as it is), nbytes dev i32 [B] = 8 + n_b, image dev u8 [B,P] or NULL (q per pixel, 0 where empty), owner_intensity dev f32 [B,P] or NULL (the owner's fourth float as stored, 0
+ * where empty: what --eval compares the decoded values with), orphans dev i32 [B] = non-empty
+ * pixels no row owns (0 whenever ri is the image of these rows; such a pixel is coded as 0).  scratch: rpcc_intensity_scratch_bytes(B, P)
+ * bytes (8 per pixel + flags; needs no initialisation).  One device atomic per candidate owner; minima only, so the result does not depend
+ * on scheduling.
+ * rpcc_intensity_decode: payload rows / nbytes as above, labels dev [B,P] of label_bytes 1 (uint8) or 2 (uint16).  Out: intensity dev f32
+ * [B,P], 0 where the label is 1; status dev i32 [B] = RPCC_STREAM_OK, or RPCC_STREAM_E_INTENSITY when nbytes[b] is outside 8 .. the row,
+ * the magic is missing, the scale is not finite and > 0, or nbytes[b] - 8 is not the number of labels != 1: that frame's row is zeros and
+ * its payload is never used as an index.
+ * Both queue on `stream` and do not synchronise; argument errors (NULL, unaligned rows, total outside 0 .. 2^31 - 1, B outside
+ * 1 .. RPCC_MAX_BATCH, a geometry the projection refuses, a bad scale, a small scratch or row stride, another label_bytes) return
+ * RPCC_ERR_ARG before the device is touched. */
+size_t rpcc_intensity_scratch_bytes(int B, int P);
+int rpcc_intensity_encode(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, float scale,
+                          uint8_t *payload, int64_t payload_stride, int32_t *nbytes, uint8_t *image, float *owner_intensity, int32_t *orphans,
+                          void *scratch, size_t scratch_bytes, void *stream);
+int rpcc_intensity_decode(const uint8_t *payload, int64_t payload_stride, const int32_t *nbytes, const void *labels, int label_bytes, int B,
+                          int P, float *intensity, int32_t *status, void *stream);
+
 /* ---- a4: ground plane ----------------------------------------------------------------------- *
  * replaces the ground branch of PointCloudSegment.segment: candidate selection + RANSAC
  * (utils/segment_utils.py:74-82,101-108).  The reference uses Open3D segment_plane on an unseeded
@@ -524,6 +556,7 @@ int rpcc_compress_batch_labels(const rpcc_labels_io *io, int B, rpcc_geom g, int
 #define RPCC_STREAM_E_SALIENCE 7
 #define RPCC_STREAM_E_RESIDUAL 8
 #define RPCC_STREAM_E_CONTAINER 9
+#define RPCC_STREAM_E_INTENSITY 10 /* rpcc_intensity_decode; callers that asked for intensity and found no (valid) trailer */
 size_t rpcc_decompress_workspace_bytes(int B, int P, int M);
 int rpcc_decompress_batch(const uint8_t *contour_bits, const uint16_t *idx_sequence, const float *model, const int16_t *q16, const uint8_t *salience,
                           const int64_t *payload_len, const int32_t *entropy_status, const float *tm, const double *level_acc, int levels, int B,

@@ -97,9 +97,12 @@ class QuantizationModule:
 
 def compress_point_cloud(basic_compressor, plane_param, cluster_idx, salience_level, nonzero_residual_quantized,
                          ground_residual_quantized=None, cluster_residual_quantized=None, point_cloud=None,
-                         range_image=None, full=False):
-    """utils/compress_utils.py:138-164: casts + contour + packbits + per-array entropy coding."""
+                         range_image=None, full=False, intensity=None):
+    """utils/compress_utils.py:138-164: casts + contour + packbits + per-array entropy coding.  intensity (not the reference's): the
+    uint8 payload of ops.intensity_encode, coded like any other array and appended to the container by pack_bitstream."""
     original_data = {"residual_quantized": np.asarray(nonzero_residual_quantized).astype(np.int16)}
+    if intensity is not None:
+        original_data["intensity"] = np.ascontiguousarray(intensity, dtype=np.uint8)
     if full:
         if point_cloud is not None:
             original_data["point_cloud"] = point_cloud.astype(np.float32)
@@ -119,11 +122,75 @@ def compress_point_cloud(basic_compressor, plane_param, cluster_idx, salience_le
 
 
 _ORDER = ("contour_map", "idx_sequence", "plane_param", "residual_quantized")
+INTENSITY_MAGIC = b"RPI1"
+
+
+def _keys(uniform, data=()):
+    """The arrays of a container in file order; 'intensity' (the trailer no reference reader looks at) where the frame holds it."""
+    return (() if uniform else ("salience_level",)) + _ORDER + (("intensity",) if "intensity" in data else ())
+
+
+def intensity_payload(q, scale):
+    """The 'intensity' array of a frame: b"RPI1" | scale as little-endian float32 | q uint8 [n] of the non-empty pixels in raster order."""
+    return np.frombuffer(INTENSITY_MAGIC + struct.pack("<f", scale) + np.ascontiguousarray(q, dtype=np.uint8).tobytes(), dtype=np.uint8)
+
+
+def parse_intensity_payload(data, n):
+    """-> (scale, q uint8 [n]) of a decoded 'intensity' array; ValueError unless it starts with the magic, carries a finite scale > 0 and
+    holds exactly 8 + n bytes (n: the pixels whose label is not 1)."""
+    data = bytes(data)
+    if len(data) < 8 or data[:4] != INTENSITY_MAGIC:
+        raise ValueError("intensity payload: no %r header (%d bytes)" % (INTENSITY_MAGIC, len(data)))
+    scale = np.frombuffer(data, dtype="<f4", count=1, offset=4)[0]
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError("intensity payload: scale %r is not finite and > 0" % float(scale))
+    if len(data) != 8 + n:
+        raise ValueError("intensity payload: %d bytes for %d non-empty pixels (8 + %d expected)" % (len(data), n, n))
+    return np.float32(scale), np.frombuffer(data, dtype=np.uint8, offset=8)
+
+
+def intensity_trailer_span(blob, uniform=True):
+    """(start, end) of the coded 'intensity' bytes of a container, or None: what follows the known payloads must be exactly one
+    [int32 length | bytes] that ends the blob."""
+    off = 0
+    for _ in _keys(uniform):
+        if off + 4 > len(blob):
+            return None
+        (n,) = struct.unpack_from("i", blob, off)
+        if n < 0 or off + 4 + n > len(blob):
+            return None
+        off += 4 + n
+    if off + 4 > len(blob):
+        return None
+    (n,) = struct.unpack_from("i", blob, off)
+    return (off + 4, off + 4 + n) if n >= 0 and off + 4 + n == len(blob) else None
+
+
+BEAM_TABLE_INTENSITY = ("intensity with a per-beam elevation table (channel_distribute_csv): that projection's rule is 'the last point wins', "
+                        "another owner rule than the intensity kernels'; use a lidar configuration with evenly spaced beams")
+
+
+def encode_intensity(transformer, rows, range_image, scale, want_image=False):
+    """One frame's 'intensity' array on the per-frame path: rows [N,>=4] (host), range_image [H,W] the image of these rows (host array or
+    device tensor) -> (uint8 [8 + n], the u8 [H,W] image of quantised values or None), by ops.intensity_encode."""
+    if getattr(transformer, "even_dist", True) is False:
+        raise NotImplementedError(BEAM_TABLE_INTENSITY)
+    dev, H, W = transformer.device, transformer.H, transformer.W
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] < 4:
+        raise ValueError("intensity: the frame holds %s values per point, no intensity column" % (rows.shape[1] if rows.ndim == 2 else "?"))
+    rows_d = torch.from_numpy(np.ascontiguousarray(rows[:, :4], dtype=np.float32)).to(dev)
+    ri = range_image if torch.is_tensor(range_image) else torch.from_numpy(np.ascontiguousarray(range_image, dtype=np.float32)).to(dev)
+    offs = torch.tensor([0, rows_d.shape[0]], dtype=torch.int64, device=dev)
+    payload, nbytes, image, orphans = ops.intensity_encode(rows_d, offs, transformer.geom, ri.reshape(1, H, W).contiguous(), scale, want_image=want_image)
+    if int(orphans[0]):
+        raise RuntimeError("intensity: %d non-empty pixels have no owner -- the range image is not the image of these rows" % int(orphans[0]))
+    return payload[0, : int(nbytes[0])].cpu().numpy(), (image[0].cpu().numpy() if want_image else None)
 
 
 def pack_bitstream(compressed_data, uniform=True):
-    """The .rpcc container (utils/compress_utils.py:167-179): [int32 length | bytes] per array."""
-    keys = (() if uniform else ("salience_level",)) + _ORDER
+    """The .rpcc container (utils/compress_utils.py:167-179): [int32 length | bytes] per array; 'intensity' last where the dictionary holds it."""
+    keys = _keys(uniform, compressed_data)
     return b"".join(struct.pack("i", len(compressed_data[k])) + bytes(compressed_data[k]) for k in keys)
 
 
@@ -139,13 +206,11 @@ def pack_frames(basic_compressor, frames, uniform=True):
         except _lib.RpccError:
             host = None
     if basic_compressor.batch_codec() and frames:   # every array of the chunk in one dumps_many / compress_many
-        keys = (() if uniform else ("salience_level",)) + _ORDER
-        blobs = basic_compressor.batch_codec()[1]([np.ascontiguousarray(od[k]) for od in frames for k in keys])
-        na = len(keys)
-        return [b"".join(struct.pack("i", len(b)) + b for b in blobs[i * na: (i + 1) * na]) for i in range(len(frames))]
-    if host is None:
-        return [pack_bitstream(basic_compressor.compress_dict(od), uniform=uniform) for od in frames]
-    keys = (() if uniform else ("salience_level",)) + _ORDER
+        blobs = iter(basic_compressor.batch_codec()[1]([np.ascontiguousarray(od[k]) for od in frames for k in _keys(uniform, od)]))
+        return [b"".join(struct.pack("i", len(b)) + b for b in (next(blobs) for _ in _keys(uniform, od))) for od in frames]
+    if host is None or len({"intensity" in od for od in frames}) > 1:   # (the host call takes one array count for the whole chunk)
+        return [pack_bitstream(basic_compressor.compress_dict({k: od[k] for k in _keys(uniform, od)}), uniform=uniform) for od in frames]
+    keys = _keys(uniform, frames[0])
     arrs = [np.ascontiguousarray(od[k]) for od in frames for k in keys]
     n, na = len(frames), len(keys)
     ptrs = np.fromiter((a.ctypes.data for a in arrs), dtype=np.uint64, count=n * na)
@@ -164,7 +229,9 @@ def pack_frames(basic_compressor, frames, uniform=True):
     return [out[int(offs[i]): int(offs[i]) + int(out_len[i])].tobytes() for i in range(n)]
 
 
-def unpack_bitstream(blob, uniform=True):
+def unpack_bitstream(blob, uniform=True, intensity=False):
+    """intensity=True (a caller that asks for it): the dictionary also holds 'intensity', the coded trailer -- ValueError unless what
+    follows the known payloads is exactly one length-prefixed payload that ends the blob.  Without it: trailing bytes are ignored, as ever."""
     out, off = {}, 0
     for k in (() if uniform else ("salience_level",)) + _ORDER:
         # (the reference reads whatever f.read(n) returns; a truncated or foreign file then fails somewhere inside the entropy decoder)
@@ -176,6 +243,12 @@ def unpack_bitstream(blob, uniform=True):
             raise ValueError("bitstream: payload '%s' claims %d bytes, %d are left" % (k, n, len(blob) - off - 4))
         out[k] = blob[off + 4: off + 4 + n]
         off += 4 + n
+    if intensity:
+        span = intensity_trailer_span(blob, uniform)
+        if span is None:
+            raise ValueError("bitstream: no intensity trailer after its %d payloads (%d bytes follow them; compressed without --intensity?)"
+                             % (len(out), len(blob) - off))
+        out["intensity"] = blob[span[0]: span[1]]
     return out
 
 
@@ -184,9 +257,9 @@ def save_compressed_bitstream(file, compressed_data, uniform=True):
         f.write(pack_bitstream(compressed_data, uniform))
 
 
-def read_compressed_bitstream(file, uniform=True):
+def read_compressed_bitstream(file, uniform=True, intensity=False):
     with open(file, "rb") as f:
-        return unpack_bitstream(f.read(), uniform)
+        return unpack_bitstream(f.read(), uniform, intensity=intensity)
 
 
 def decompress_point_cloud(compressed_data, basic_compressor, model_num, H, W):

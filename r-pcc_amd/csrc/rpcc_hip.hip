@@ -1030,6 +1030,61 @@ extern "C" int rpcc_project(const float *xyz, const int64_t *offsets, int64_t to
     return rpcc_project_strided(xyz, 12, offsets, total, B, g, ri, scratch, scratch_bytes, stream);
 }
 
+// ---- intensity: the owner of every pixel, its fourth float as one byte ----------------------------------
+#include "intensity_kernels.h"
+
+static inline bool intensity_shape_ok(int B, int64_t H, int64_t W) { return B > 0 && B <= RPCC_MAX_BATCH && H > 1 && W > 0 && H * W < ((int64_t)1 << 31); }
+
+extern "C" size_t rpcc_intensity_scratch_bytes(int B, int P) { return B > 0 && B <= RPCC_MAX_BATCH && P > 0 ? intensity_layout(nullptr, B, P).bytes : 0; }
+
+extern "C" int rpcc_intensity_encode(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, float scale,
+                                     uint8_t *payload, int64_t payload_stride, int32_t *nbytes, uint8_t *image, float *owner_intensity, int32_t *orphans,
+                                     void *scratch, size_t scratch_bytes, void *stream) {
+    ARG_TRY(intensity_shape_ok(B, g.H, g.W) && total >= 0 && total < ((int64_t)1 << 31));
+    ARG_TRY(g.horizontal_fov > 0.0f);   // (a column index is never negative)
+    ARG_TRY(offsets != nullptr && ri != nullptr && payload != nullptr && nbytes != nullptr && orphans != nullptr && scratch != nullptr);
+    ARG_TRY(total == 0 || rows != nullptr);
+    ARG_TRY((reinterpret_cast<uintptr_t>(rows) & 15u) == 0);   // rows are read with 16-byte loads
+    ARG_TRY(scale > 0.0f && scale <= 3.402823466e+38f);        // (false for NaN)
+    const int P = g.H * g.W;
+    ARG_TRY(payload_stride >= (int64_t)8 + P);
+    const IntensityLayout l = intensity_layout(scratch, B, P);
+    ARG_TRY(scratch_bytes >= l.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t px = (int64_t)B * P;
+    const unsigned fill_wgs = (unsigned)std::min<int64_t>((px + 255) / 256, 4096);
+    intensity_fill_kernel<<<fill_wgs, 256, 0, st>>>(l.owner, l.lastz, l.flags, px, B, false, P);
+    LAUNCH_CHECK();
+    if (total > 0) {
+        const unsigned wgs = (unsigned)std::min<int64_t>((total + INT_THREADS - 1) / INT_THREADS, 256 * 16);
+        const float4 *r4 = reinterpret_cast<const float4 *>(rows);
+        const uint32_t *rb = reinterpret_cast<const uint32_t *>(ri);
+        intensity_owner_kernel<false><<<wgs, INT_THREADS, 0, st>>>(r4, offsets, total, B, g, pix_fast_cfg(g), rb, l.owner, l.lastz, l.flags);
+        // frames that hold a depth-0 point: again, restricted to the positions after the pixel's last one (both leave at once when no frame is flagged)
+        intensity_fill_kernel<<<fill_wgs, 256, 0, st>>>(l.owner, l.lastz, l.flags, px, B, true, P);
+        intensity_owner_kernel<true><<<std::min(wgs, 2048u), INT_THREADS, 0, st>>>(r4, offsets, total, B, g, pix_fast_cfg(g), rb, l.owner, l.lastz, l.flags);
+        LAUNCH_CHECK();
+    }
+    intensity_pack_kernel<<<B, INT_FRAME_THREADS, 0, st>>>(rows, offsets, total, P, ri, l.owner, scale, payload, payload_stride, nbytes, image, owner_intensity, orphans);
+    LAUNCH_CHECK();
+    return RPCC_OK;
+}
+
+extern "C" int rpcc_intensity_decode(const uint8_t *payload, int64_t payload_stride, const int32_t *nbytes, const void *labels, int label_bytes, int B,
+                                     int P, float *intensity, int32_t *status, void *stream) {
+    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0);
+    ARG_TRY(payload != nullptr && nbytes != nullptr && labels != nullptr && intensity != nullptr && status != nullptr);
+    ARG_TRY(label_bytes == 1 || label_bytes == 2);
+    ARG_TRY(payload_stride >= (int64_t)8 + P);
+    hipStream_t st = (hipStream_t)stream;
+    if (label_bytes == 1)
+        intensity_decode_kernel<uint8_t><<<B, INT_FRAME_THREADS, 0, st>>>(payload, payload_stride, nbytes, static_cast<const uint8_t *>(labels), P, intensity, status);
+    else
+        intensity_decode_kernel<uint16_t><<<B, INT_FRAME_THREADS, 0, st>>>(payload, payload_stride, nbytes, static_cast<const uint16_t *>(labels), P, intensity, status);
+    LAUNCH_CHECK();
+    return RPCC_OK;
+}
+
 #include "beam_index.h"
 #include "beams_kernels.h"
 

@@ -71,6 +71,23 @@ class DatasetTemplate:
             assert False, "File type not correct: " + file
         return pc[:, :3]
 
+    @staticmethod
+    def load_rows(file):
+        """The sweep as stored, with its fourth column (not the reference's: load_data drops it) -> f32 [N,4] rows (x, y, z, intensity),
+        from a .bin, or from a .txt / .npy with at least 4 columns."""
+        ext = file.split(".")[-1]
+        if ext == "bin":
+            return np.fromfile(file, dtype=np.float32).reshape((-1, 4))
+        if ext == "txt":
+            pc = np.loadtxt(file, ndmin=2)
+        elif ext == "npy":
+            pc = np.load(file)
+        else:
+            raise ValueError("load_rows: %s -- intensity is read from .bin, .txt or .npy files" % file)
+        if pc.ndim != 2 or pc.shape[1] < 4:
+            raise ValueError("load_rows: %s holds %s values per point, no intensity column" % (file, pc.shape[1] if pc.ndim == 2 else "?"))
+        return np.ascontiguousarray(pc[:, :4], dtype=np.float32)
+
     def load_range_image_points_from_file(self, file):
         """dataset/dataset.py:65-70."""
         original = self.load_data(file)
@@ -79,12 +96,17 @@ class DatasetTemplate:
         return point_cloud, range_image, original
 
     @staticmethod
-    def save_point_cloud_to_file(file, point_cloud, color=None):
-        """dataset/dataset.py:72-107 (txt / bin / npy / ply)."""
+    def save_point_cloud_to_file(file, point_cloud, color=None, intensity=None):
+        """dataset/dataset.py:72-107 (txt / bin / npy / ply).  intensity (one value per point, not the reference's): the fourth column of
+        txt / bin / npy instead of zeros, a fourth float property `intensity` of a ply; it goes through the same sum != 0 filter."""
         ext = file.split(".")[-1]
-        point_cloud = point_cloud[np.where(np.sum(point_cloud, -1) != 0)]
+        keep = np.where(np.sum(point_cloud, -1) != 0)
+        point_cloud = point_cloud[keep]
+        if intensity is not None:
+            intensity = np.asarray(intensity).reshape(-1)[keep[0]].astype(point_cloud.dtype)
         if ext in ("txt", "bin", "npy", "npz"):
-            pc4 = np.concatenate((point_cloud, np.zeros((point_cloud.shape[0], 1))), -1)
+            col4 = np.zeros((point_cloud.shape[0], 1)) if intensity is None else intensity[:, None]
+            pc4 = np.concatenate((point_cloud, col4), -1)
             if ext == "txt":
                 np.savetxt(file, pc4)
             elif ext == "bin":
@@ -94,8 +116,10 @@ class DatasetTemplate:
         elif ext == "ply":
             with open(file, "wb") as fid:
                 fid.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\n"
-                           "property float y\nproperty float z\nend_header\n" % point_cloud.shape[0]).encode())
-                fid.write(np.ascontiguousarray(point_cloud[:, :3], dtype="<f4").tobytes())
+                           "property float y\nproperty float z\n%send_header\n"
+                           % (point_cloud.shape[0], "" if intensity is None else "property float intensity\n")).encode())
+                body = point_cloud[:, :3] if intensity is None else np.concatenate((point_cloud[:, :3], intensity[:, None]), -1)
+                fid.write(np.ascontiguousarray(body, dtype="<f4").tobytes())
         else:
             assert False, "File type not correct."
 

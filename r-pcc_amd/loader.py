@@ -53,6 +53,9 @@ class _Slot:
         self.sal_pin = torch.empty((B, K), dtype=torch.uint8).pin_memory() if bc.general else None
         self.tot_pin = torch.zeros((2,), dtype=torch.int64).pin_memory()
         self.status_pin = torch.zeros((B,), dtype=torch.int32).pin_memory() if bc.dbscan else None   # (rpcc_compress_batch_labels: refused frames)
+        # bc.intensity_scale: the intensity payload rows (8 + n bytes of 8 + P each are meaningful), their lengths and orphan counts
+        self.int_pin = torch.empty((B, 8 + P), dtype=torch.uint8).pin_memory() if bc.intensity_scale is not None else None
+        self.int_n_pin = torch.zeros((2, B), dtype=torch.int32).pin_memory() if bc.intensity_scale is not None else None
         self.h2d_done = torch.cuda.Event()
         self.done = torch.cuda.Event()
         self.n = 0
@@ -82,6 +85,7 @@ class BatchPayload:
         K = counts.shape[1]
         self.nrow = np.where(counts.any(1), K - np.argmax(counts[:, ::-1] != 0, axis=1), 2)   # max(seg)+1 rows (tools/compress.py:102)
         self.sal = slot.sal_pin.numpy() if (slot.sal_pin is not None and not uniform) else None
+        self.intensity = None if slot.int_pin is None else (slot.int_pin.numpy(), slot.int_n_pin.numpy()[0])
 
     def frame(self, b):
         nrow = int(self.nrow[b])
@@ -91,6 +95,8 @@ class BatchPayload:
         od["contour_map"] = self.bits[b]
         od["idx_sequence"] = self.seq[self.so[b]: self.so[b + 1]]
         od["plane_param"] = self.model[b, :nrow]
+        if self.intensity is not None:
+            od["intensity"] = self.intensity[0][b, : self.intensity[1][b]]
         return od
 
     def __len__(self):
@@ -110,6 +116,9 @@ class StreamingCompressor:
                              the rows with a 16-byte stride (rpcc_batch_io.point_stride_bytes = 16).  16 bytes per point
                              cross the link instead of 12."""
         assert ingest in ("xyz", "rows")
+        if bc.intensity_scale is not None and ingest != "rows":
+            raise ValueError('StreamingCompressor: a BatchCompressor with intensity_scale needs ingest="rows" (the fourth column must reach the device); '
+                             'ingest="xyz" drops it')
         self.ingest = ingest
         self.bc, self.B, self.depth = bc, int(batch), int(depth)
         self.device = bc.device
@@ -159,7 +168,7 @@ class StreamingCompressor:
             for i in range(lo, hi):
                 f = frames[i]
                 if not rows:
-                    dst[offs[i]:offs[i + 1]] = f[:, :3]   # .bin rows are (x, y, z, intensity): the strided copy drops the 4th column
+                    dst[offs[i]:offs[i + 1]] = f[:, :3]   # .bin rows are (x, y, z, intensity): the strided copy drops the 4th column (ingest="rows" keeps it)
                 elif isinstance(f, (str, os.PathLike)):       # the file's bytes land in the pinned slot: no pass over the points at all
                     with open(f, "rb", buffering=0) as fh:
                         if os.fstat(fh.fileno()).st_size != 16 * int(offs[i + 1] - offs[i]):   # grew or shrank since it was sized
@@ -217,6 +226,11 @@ class StreamingCompressor:
                 slot.status_pin.copy_(slot.buf.status, non_blocking=True)
             if slot.sal_pin is not None and slot.buf.salience is not None:
                 slot.sal_pin.copy_(slot.buf.salience, non_blocking=True)
+            if slot.int_pin is not None:      # (run_batch has run ops.intensity_encode on the same rows)
+                pay, nb, orphans = slot.buf.intensity
+                slot.int_pin.copy_(pay, non_blocking=True)
+                slot.int_n_pin[0].copy_(nb, non_blocking=True)
+                slot.int_n_pin[1].copy_(orphans, non_blocking=True)
             slot.keep = (bits, seq, nseq)
             slot.done.record(self.compute_stream)
 
@@ -226,6 +240,8 @@ class StreamingCompressor:
         slot.done.synchronize()
         if slot.status_pin is not None:   # a frame DBSCAN gave more labels than max_labels (or a capped union-find): raise as collect() does
             self.bc.check_status(slot.status_pin.numpy()[:slot.n])
+        if slot.int_pin is not None:
+            self.bc.check_orphans(slot.int_n_pin.numpy()[1, :slot.n])
         stot = int(slot.tot_pin[1])
         if stot > self.seq_eager:
             # an unusually long index sequence: the rest is fetched now, on a stream of its own (the compute stream already

@@ -133,6 +133,62 @@ def project_beams_check(xyz, geom, beams):
     return tuple(int(v) for v in counts.cpu())
 
 
+def check_intensity_scale(scale):
+    """An intensity scale as the kernels take it: an fp32 value, finite and > 0."""
+    with np.errstate(over="ignore"):
+        s = float(np.float32(scale))
+    if not (math.isfinite(s) and s > 0):
+        raise ValueError("intensity scale %r: a finite float32 value > 0 is needed" % (scale,))
+    return s
+
+
+def intensity_encode(rows, offsets, geom, ri, scale, want_image=False, payload=None, nbytes=None, image=None, orphans=None, scratch=None,
+                     owner_intensity=None):
+    """The intensity payloads of a batch (rpcc_intensity_encode; specification: tests/intensity_ref.py).  rows f32 [total,4] (x, y, z,
+    intensity), offsets i64 [B+1], ri f32 [B,H,W] the range image ops.project / the batch call made of THESE rows, scale finite > 0
+    -> (payload u8 [B, 8+P]: b"RPI1" | scale f32 | one byte per non-empty pixel in raster order, nbytes i32 [B] = 8 + n,
+    image u8 [B,H,W] or None, orphans i32 [B]: non-empty pixels no row owns -- 0 whenever ri is the image of these rows).
+    The bytes of a payload row past nbytes are left as they were.  payload .. scratch: the caller's buffers.  owner_intensity: a caller's
+    f32 [B,H,W] tensor that receives every pixel's owner's intensity as stored (0 where empty)."""
+    if rows.dim() != 2 or rows.shape[1] != 4:
+        raise ValueError("intensity_encode: rows [total,%s] hold no intensity column; the stored (x, y, z, intensity) rows [total,4] are needed"
+                         % (rows.shape[1] if rows.dim() == 2 else "?"))
+    assert rows.dtype == torch.float32 and ri.dtype == torch.float32
+    scale = check_intensity_scale(scale)
+    B, P, dev = offsets.numel() - 1, geom.H * geom.W, _dev(offsets)
+    rows = rows.contiguous()
+    if payload is None:
+        payload = torch.empty((B, 8 + P), dtype=torch.uint8, device=dev)
+    if nbytes is None:
+        nbytes = torch.empty((B,), dtype=torch.int32, device=dev)
+    if orphans is None:
+        orphans = torch.empty((B,), dtype=torch.int32, device=dev)
+    if want_image and image is None:
+        image = torch.empty((B, geom.H, geom.W), dtype=torch.uint8, device=dev)
+    if scratch is None:
+        scratch = torch.empty(_lib.lib().rpcc_intensity_scratch_bytes(B, P), dtype=torch.uint8, device=dev)
+    check(_lib.lib().rpcc_intensity_encode(ptr(rows) if rows.numel() else None, ptr(offsets), rows.shape[0], B, geom, ptr(ri), scale, ptr(payload),
+                                           payload.stride(0), ptr(nbytes), ptr(image) if want_image else None, ptr(owner_intensity), ptr(orphans), ptr(scratch),
+                                           scratch.numel(), stream()))
+    return payload, nbytes, (image if want_image else None), orphans
+
+
+def intensity_decode(payload, nbytes, seg, out=None, status=None):
+    """The way back (rpcc_intensity_decode): payload u8 [B, >= 8+P] rows, nbytes i32 [B], seg [B,H,W] uint8 or uint16 label maps (label 1:
+    an empty pixel) -> (intensity f32 [B,H,W], 0 where the label is 1; status i32 [B]: _lib.STREAM_OK, or _lib.STREAM_E_INTENSITY for a
+    row without the magic, with a scale that is not finite and > 0 or with another byte count than 8 + (labels != 1): zeros)."""
+    B, H, W = seg.shape
+    assert payload.dtype == torch.uint8 and payload.dim() == 2 and payload.shape[0] == B and payload.stride(1) == 1
+    assert seg.dtype in (torch.uint8, torch.uint16) and nbytes.dtype == torch.int32 and nbytes.numel() == B
+    if out is None:
+        out = torch.empty((B, H, W), dtype=torch.float32, device=_dev(seg))
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=_dev(seg))
+    check(_lib.lib().rpcc_intensity_decode(C.c_void_p(payload.data_ptr()), payload.stride(0), ptr(nbytes), ptr(seg), seg.element_size(), B, H * W,
+                                           ptr(out), ptr(status), stream()))
+    return out, status
+
+
 def _frame_ids(frame_ids, B, device):
     """Stable per-frame identities (datalist indices) as a device i64 [B] tensor, or None."""
     if frame_ids is None:

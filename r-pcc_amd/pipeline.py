@@ -11,7 +11,7 @@ import torch
 
 from . import entropy, ops
 from . import _lib
-from .compress_utils import _ORDER, BasicCompressor, device_decoder, pack_bitstream, pack_frames, unpack_bitstream  # noqa: F401
+from .compress_utils import _ORDER, BEAM_TABLE_INTENSITY, BasicCompressor, intensity_trailer_span, device_decoder, pack_bitstream, pack_frames, unpack_bitstream  # noqa: F401
 
 
 class BatchCompressor:
@@ -20,8 +20,11 @@ class BatchCompressor:
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
                  model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
                  device_entropy=False, device_bzip2=False, segment_method="FPS", DBSCAN_eps=1.5, max_labels=None,
-                 radius_outlier_removal=None, rans_delta=False):
-        """rans_delta (basic_compressor 'rans' only): the residual stream goes through the delta filter, as BasicCompressor(rans_delta=True)
+                 radius_outlier_removal=None, rans_delta=False, intensity_scale=None):
+        """intensity_scale (None: off, and no byte of any container changes): frames are [N,>=4] rows (x, y, z, intensity); after the
+        batch call one ops.intensity_encode runs on the same point tensor and the batch's range images, and every container gets the
+        'intensity' trailer (compress_utils.pack_bitstream), byte for byte the per-frame path's.  Independent of the segmentation.
+        rans_delta (basic_compressor 'rans' only): the residual stream goes through the delta filter, as BasicCompressor(rans_delta=True)
         codes it on the per-frame path.
         segment_method "DBSCAN" (cfgs/compressor.yaml: segment_method, DBSCAN_eps): the frames are segmented by dbscan.dbscan_segment and
         enter the batch kernels through ops.compress_batch_labels; cluster_num does not apply (tools/compress.py).  max_labels: the labels a
@@ -48,6 +51,9 @@ class BatchCompressor:
         else:
             self.M = ops.check_cluster_num(cluster_num)   # (above 254: uint16 labels through the rpcc_*_wide entries; above 65533: refused by name)
         self.T = transformer
+        self.intensity_scale = None if intensity_scale is None else ops.check_intensity_scale(intensity_scale)
+        if self.intensity_scale is not None and getattr(transformer, "even_dist", True) is False:
+            raise NotImplementedError("BatchCompressor: " + BEAM_TABLE_INTENSITY)
         # a transformer built from a per-beam elevation table (channel_distribute_csv): the projection goes through its index -- the fused
         # call's, the DBSCAN path's and the streaming loader's alike (all run_batch / _group_args); nothing behind the projection changes
         if getattr(transformer, "even_dist", True) is False and not self.dbscan and self.M > _lib.MAX_CLUSTERS_MID:
@@ -91,6 +97,26 @@ class BatchCompressor:
         from .outlier import radius_outlier_mask
         return radius_outlier_mask(xyz, offsets, self.outlier[0], self.outlier[1], masked=True).masked
 
+    def run_intensity(self, rows, offsets, buf):
+        """intensity_scale: the batch's intensity payloads into buf.intensity = (payload u8 [B, 8+P], nbytes i32 [B], orphans i32 [B]), on
+        the current stream.  rows: the point tensor the range images in buf.ri were made of (the NaN-masked one with the radius filter)."""
+        if self.intensity_scale is None:
+            return
+        if getattr(buf, "intensity", None) is None:
+            B, P = buf.B, buf.P
+            buf.intensity = (torch.empty((B, 8 + P), dtype=torch.uint8, device=self.device), torch.empty((B,), dtype=torch.int32, device=self.device),
+                             torch.empty((B,), dtype=torch.int32, device=self.device))
+            buf.intensity_scratch = torch.empty(_lib.lib().rpcc_intensity_scratch_bytes(B, P), dtype=torch.uint8, device=self.device)
+        pay, nb, orphans = buf.intensity
+        ops.intensity_encode(rows, offsets, self.T.geom, buf.ri, self.intensity_scale, payload=pay, nbytes=nb, orphans=orphans,
+                             scratch=buf.intensity_scratch)
+
+    @staticmethod
+    def check_orphans(orphans):
+        if np.any(orphans):
+            raise _lib.RpccError("intensity: frames %s have non-empty pixels no row owns (the range image is not the image of these rows)"
+                                 % np.flatnonzero(orphans).tolist())
+
     def run_batch(self, xyz, offsets, ground, buf, frame_ids=None, fit_ground=True):
         """The device work of one batch into buf, on the current stream, nothing waited for.  ground f64 [B,4]: fitted here (fit_ground: the
         seeded RANSAC, frame b drawing with seed + frame_ids[b]) or the caller's.  FPS: one ops.compress_batch.  DBSCAN: ops.project (packed
@@ -104,6 +130,7 @@ class BatchCompressor:
             ops.compress_batch(xyz, offsets, self.T.tm_dev, ground, buf, self.ground_threshold, self.acc,
                                ground_seed=self.seed if fit_ground else -1, frame_ids=frame_ids, model_method=self.model_method,
                                angle_threshold=angle, plane_seed=self.seed, nonuniform=nu, beams=self.beams)
+            self.run_intensity(xyz, offsets, buf)
             return
         from .dbscan import dbscan_segment
         tm = self.T.tm_dev
@@ -114,6 +141,7 @@ class BatchCompressor:
         labels, top = dbscan_segment(buf.ri, tm, ground, self.eps, min_points=10, check=False)
         ops.compress_batch_labels(buf.ri, tm, ground, labels, top, buf, self.acc, model_method=self.model_method, angle_threshold=angle,
                                   plane_seed=self.seed, frame_ids=frame_ids, nonuniform=nu)
+        self.run_intensity(xyz, offsets, buf)
 
     def check_status(self, status):
         """status: a batch's buf.status on the host (None for FPS).  Raises RpccError naming the refused frames (their places in the batch)
@@ -176,13 +204,17 @@ class BatchCompressor:
             return self._encode(dict(buf=buf, ground=g))
         args = self._group_args(self._filtered(xyz, offsets), offsets, ground, frame_ids)
         ops.compress_batch(ground_threshold=self.ground_threshold, acc=self.acc, **args)
+        self.run_intensity(args["xyz"], offsets, args["buf"])
         return self._encode(args)
 
     def _upload(self, frames, ground=None):
         """Host arrays of a batch -> device (xyz, offsets, ground or None) on the current stream."""
         offs = np.zeros(len(frames) + 1, np.int64)
         offs[1:] = np.cumsum([f.shape[0] for f in frames])
-        xyz = torch.from_numpy(np.ascontiguousarray(np.concatenate([f[:, :3] for f in frames]), dtype=np.float32)).to(self.device)
+        cols = 3 if self.intensity_scale is None else 4     # (with intensity the rows go up as stored: the kernels read them with stride 16)
+        if cols == 4 and any(f.ndim != 2 or f.shape[1] < 4 for f in frames):
+            raise ValueError("BatchCompressor(intensity_scale=...): frames must be [N,>=4] rows (x, y, z, intensity)")
+        xyz = torch.from_numpy(np.ascontiguousarray(np.concatenate([f[:, :cols] for f in frames]), dtype=np.float32)).to(self.device)
         gnd = None if ground is None else torch.from_numpy(np.asarray(ground, np.float64).reshape(-1, 4)).to(self.device)
         return xyz, torch.from_numpy(offs).to(self.device), gnd, int(offs[-1])
 
@@ -222,6 +254,9 @@ class BatchCompressor:
                 (qp.data_ptr() + 2 * excl(nnz), 2 * nnz, 2 * P, 2, np.int16)]
         if sal is not None:
             cols.insert(0, (sal.data_ptr() + rows * K, nrow, K, 1, np.uint8))
+        if self.intensity_scale is not None:     # the trailer: a payload row each, its 8 + n bytes
+            pay, nbytes, _ = buf.intensity
+            cols.append((pay.data_ptr() + rows * pay.stride(0), nbytes.to(torch.int64), 8 + P, 1, np.uint8))
         addr = torch.stack([c[0] for c in cols], 1).reshape(-1)
         lens = torch.stack([c[1] for c in cols], 1).reshape(-1)
         takes = inspect.signature(codec.encode_descriptors).parameters
@@ -256,9 +291,13 @@ class BatchCompressor:
             bits_h, model = bits.cpu().numpy(), buf.model.cpu().numpy()
             sal_h = None if sal is None else sal.cpu().numpy()
             status = buf.status.cpu().numpy() if self.dbscan else None
+            if self.intensity_scale is not None:
+                pay_h, pay_n, orphans = (t.cpu().numpy() for t in buf.intensity)
         finally:
             buf.in_flight = False   # everything collect() needs is on the host -- or the call failed: either way the slot is free again
         self.check_status(status)
+        if self.intensity_scale is not None:
+            self.check_orphans(orphans[: ctx["n"]])
         def assemble(b):
             nrow = int(np.flatnonzero(seg_max[b])[-1]) + 1          # max(seg)+1 rows (tools/compress.py:102)
             od = {"residual_quantized": q16[qo[b]: qo[b + 1]]}
@@ -267,6 +306,8 @@ class BatchCompressor:
             od["contour_map"] = bits_h[b]
             od["idx_sequence"] = seq_h[so[b]: so[b + 1]]
             od["plane_param"] = model[b, :nrow]
+            if self.intensity_scale is not None:
+                od["intensity"] = pay_h[b, : pay_n[b]]
             return od
         # a few frames per task: one call into the host library per chunk (compress_utils.pack_frames)
         n = ctx["n"]
@@ -282,9 +323,12 @@ class BatchCompressor:
             ctx["stream"].synchronize()
             fr = frame.cpu().numpy()
             status = ctx["buf"].status.cpu().numpy() if self.dbscan else None
+            orphans = ctx["buf"].intensity[2].cpu().numpy() if self.intensity_scale is not None else None
         finally:
             ctx["buf"].in_flight = False
         self.check_status(status)
+        if orphans is not None:
+            self.check_orphans(orphans[: ctx["n"]])
         n = ctx["n"]
         if (fr[1, :n] < 0).any():
             raise RuntimeError("rpcc_lz4: the containers of frames %s were not built" % np.flatnonzero(fr[1, :n] < 0).tolist())
@@ -320,6 +364,9 @@ class MixedBatchCompressor:
         if kw.get("segment_method", "FPS") != "FPS":
             raise NotImplementedError("MixedBatchCompressor: segment_method %r -- the mixed-geometry call runs FPS only; DBSCAN: one "
                                       "BatchCompressor(segment_method='DBSCAN') per lidar" % (kw["segment_method"],))
+        if kw.get("intensity_scale") is not None:
+            raise NotImplementedError("MixedBatchCompressor: intensity_scale -- the mixed-geometry call carries no intensity; use one "
+                                      "BatchCompressor(intensity_scale=...) per lidar")
         if kw.get("radius_outlier_removal") is not None:
             raise NotImplementedError("MixedBatchCompressor: radius_outlier_removal -- the mixed-geometry call takes the points as they are; "
                                       "filter them first (outlier.radius_outlier_mask), or use one BatchCompressor per lidar")
@@ -368,7 +415,8 @@ STREAM_TEXT = {_lib.STREAM_E_ENTROPY: "an entropy stream was refused by the devi
                _lib.STREAM_E_LABEL: "idx_sequence names a label without a stored model row",
                _lib.STREAM_E_SALIENCE: "salience_level does not fit the model rows or the configured levels",
                _lib.STREAM_E_RESIDUAL: "residual_quantized does not hold one value per non-empty pixel of the label map",
-               _lib.STREAM_E_CONTAINER: "the container's length prefixes do not fit its bytes"}
+               _lib.STREAM_E_CONTAINER: "the container's length prefixes do not fit its bytes",
+               _lib.STREAM_E_INTENSITY: "no valid intensity payload follows the geometry (compressed without intensity, or the payload does not fit the label map)"}
 
 
 def container_spans(blob, uniform=True):
@@ -403,7 +451,12 @@ class BatchDecompressor:
     CHUNK_FRAMES = 32              # frames per chunk at most, as the datalist tool reads them
     CHUNK_BUDGET_BYTES = 2 << 30   # device bytes one chunk may take: padded payloads, bzip2 work slots, work buffer and outputs
 
-    def __init__(self, transformer, cluster_num, accuracy, uniform=True, level_acc=None, basic_compressor="bzip2", max_labels=None):
+    def __init__(self, transformer, cluster_num, accuracy, uniform=True, level_acc=None, basic_compressor="bzip2", max_labels=None,
+                 intensity=False):
+        """intensity=True: every container must carry the 'intensity' trailer (BatchCompressor(intensity_scale=...), --intensity):
+        decompress_device returns a fifth tensor, f32 [B,H,W], decompress 4-tuples; a frame without a valid trailer gets
+        _lib.STREAM_E_INTENSITY (unless an earlier status applies) and a zero row.  The scale is read from each payload's header."""
+        self.intensity = bool(intensity)
         self.per_frame_rows = cluster_num is None     # DBSCAN streams
         if cluster_num is None:
             if max_labels is None:
@@ -439,7 +492,8 @@ class BatchDecompressor:
         work = sum(self._work_caps([b"BZh9"] * self.ns))
         outs = P * (2 if ops.is_wide(self.M) else 1) + 4 * P + 12 * P
         ws = -(-_lib.lib().rpcc_decompress_workspace_bytes(self.CHUNK_FRAMES, P, self.M) // self.CHUNK_FRAMES)
-        return sum(self.caps) + 5 * 256 + work + outs + ws
+        inten = (2 * (8 + P) + 4 * P + self.work_bytes(b"BZh9", 8 + P)) if self.intensity else 0   # coded + decoded trailer, the f32 image, its work slot
+        return sum(self.caps) + 5 * 256 + work + outs + ws + inten
 
     def _chunk_device(self, blobs, out, data=None):
         """One chunk: parse, upload, entropy launch, decode call on the current stream.  out: the chunk's rows of (status, seg, rec, pc).
@@ -497,7 +551,7 @@ class BatchDecompressor:
         sal = None if self.uniform else view(0, torch.uint8, (B, K))
         ops.decompress_batch(view(c0, torch.uint8, (B, (P + 7) // 8)), view(c0 + 1, torch.uint16, (B, P)), view(c0 + 2, torch.float32, (B, K, 4)),
                              view(c0 + 3, torch.int16, (B, P)), plen, pest, self.T.tm_dev, self.accuracy if self.uniform else self.level_acc,
-                             H, W, salience=sal, out=out)
+                             H, W, salience=sal, out=out[:4])
         if len(bad):
             out[0][meta[6 * n + len(sound): 6 * n + B]] = _lib.STREAM_E_CONTAINER
         if self.per_frame_rows and not self.uniform:
@@ -509,6 +563,38 @@ class BatchDecompressor:
             for o in out[1:]:
                 if o is not None:   # a refused frame's rows are zero (uint16 label maps: through their int16 view)
                     (o.view(torch.int16) if o.dtype == torch.uint16 else o).masked_fill_(late.view((B,) + (1,) * (o.dim() - 1)), 0)
+        if self.intensity:
+            self._chunk_intensity(blobs, arrays, base, offs, out)
+
+    def _chunk_intensity(self, blobs, arrays, base, offs, out):
+        """intensity=True: the chunk's trailers through one more decode_slots call into a [B, 8+P] array, then ops.intensity_decode on the
+        label maps just decoded.  A frame without a (valid) trailer, or whose geometry was refused, keeps its earlier status or gets
+        STREAM_E_INTENSITY, and a zero row."""
+        B, dev, P = len(blobs), self.device, self.T.H * self.T.W
+        row = 8 + P
+        spans = [intensity_trailer_span(b, self.uniform) for b in blobs]
+        have = [i for i, sp in enumerate(spans) if sp is not None]
+        n = len(have)
+        nbytes = torch.zeros((B,), dtype=torch.int32, device=dev)     # 0: no trailer, refused by rpcc_intensity_decode
+        pay = torch.empty((B, row), dtype=torch.uint8, device=dev)
+        if n:
+            fr = np.array(have, np.int64)
+            sp = np.array([spans[i] for i in have], np.int64)
+            meta_h = torch.empty((7, n), dtype=torch.int64, pin_memory=True)
+            m = meta_h.numpy()
+            m[0], m[1], m[2], m[3] = base + offs[fr] + sp[:, 0], sp[:, 1] - sp[:, 0], fr * row, row
+            wcap = np.array([self.work_bytes(arrays[i][s: s + min(e - s, 4)], row) for i, (s, e) in zip(have, sp)], np.int64)
+            m[4], wtotal = entropy.packed_slots(wcap)
+            m[5], m[6] = wcap, fr
+            meta = meta_h.to(dev, non_blocking=True)
+            work = torch.empty(wtotal, dtype=torch.uint8, device=dev) if wtotal else None
+            dst_len, est = self.decode_slots([meta[k] for k in range(6)], pay.view(-1), work)
+            nbytes[meta[6]] = torch.where(est == 0, dst_len, torch.zeros_like(dst_len)).to(torch.int32)
+        status, seg, inten = out[0], out[1], out[4]
+        _, ist = ops.intensity_decode(pay, nbytes, seg, out=inten)
+        bad = status != _lib.STREAM_OK
+        inten.masked_fill_(bad.view(B, 1, 1), 0)
+        status.copy_(torch.where(bad, status, ist))
 
     def upload(self, blobs):
         """The containers' bytes on the device, a chunk per copy, for decompress_device(blobs, uploaded=...): callers that hold the containers
@@ -522,6 +608,8 @@ class BatchDecompressor:
         B, H, W, dev = len(blobs), self.T.H, self.T.W, self.device
         out = (torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B, H, W), dtype=ops.label_dtype(self.M), device=dev),
                torch.empty((B, H, W), dtype=torch.float32, device=dev), torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_points else None)
+        if self.intensity:
+            out += (torch.empty((B, H, W), dtype=torch.float32, device=dev),)
         with torch.cuda.device(dev):
             for c0 in range(0, B, self.chunk):
                 c1 = min(c0 + self.chunk, B)
@@ -537,16 +625,16 @@ class BatchDecompressor:
         res = []
         for c0 in range(0, len(blobs), self.chunk):
             part = blobs[c0: c0 + self.chunk]
-            status, seg, rec, pc = (None if t is None else t.cpu().numpy() for t in self.decompress_device(part, want_points))
+            status, seg, rec, pc, *w = (None if t is None else t.cpu().numpy() for t in self.decompress_device(part, want_points))
             for i, st in enumerate(status):
                 if st == _lib.STREAM_OK:
-                    res.append((rec[i], pc[i] if pc is not None else None, seg[i]))
+                    res.append((rec[i], pc[i] if pc is not None else None, seg[i]) + ((w[0][i],) if self.intensity else ()))
                     continue
                 if st != _lib.STREAM_E_ENTROPY and not (st == _lib.STREAM_E_PLANE and self.per_frame_rows):   # (more rows than the cap: per frame)
                     raise ValueError("frame %d: %s (status %d)" % (c0 + i, STREAM_TEXT.get(int(st), "refused"), int(st)))
                 try:
-                    res.append(decode_frame(unpack_bitstream(part[i], self.uniform), self.host_bc, self.T, self.cluster_num, self.accuracy,
-                                            self.level_acc, self.uniform, want_points=want_points))
+                    res.append(decode_frame(unpack_bitstream(part[i], self.uniform, intensity=self.intensity), self.host_bc, self.T, self.cluster_num,
+                                            self.accuracy, self.level_acc, self.uniform, want_points=want_points, intensity=self.intensity))
                 except (ValueError, OSError, EOFError) as e:
                     raise ValueError("frame %d: %s" % (c0 + i, e)) from e
         return res

@@ -14,7 +14,7 @@ import numpy as np  # noqa: E402
 
 import rpcc_amd  # noqa: E402,F401
 from rpcc_amd.compress_utils import (BasicCompressor, QuantizationModule, compress_point_cloud,  # noqa: E402
-                                     decompress_point_cloud, read_compressed_bitstream, save_compressed_bitstream)
+                                     decompress_point_cloud, encode_intensity, read_compressed_bitstream, save_compressed_bitstream)
 from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.segment_utils import PointCloudSegment  # noqa: E402
 from rpcc_amd.utils import frame_identity, load_compressor_cfg  # noqa: E402
@@ -77,6 +77,12 @@ def make_parser(datalist=False):
     p.add_argument("--use_radius_outlier_removal", action="store_true",
                    help="remove the points with at most 3 others within 1 m before the projection (the reference's use_radius_outlier_removal, "
                         "Open3D remove_radius_outlier(nb_points=3, radius=1); here on the GPU).")
+    p.add_argument("--intensity", action="store_true",
+                   help="compress tools: carry the sweep's fourth column (lidar intensity / reflectance) as one byte per non-empty pixel, appended "
+                        "to the container where every other reader ignores it; decompress tools: read it and write (x, y, z, intensity).")
+    p.add_argument("--intensity_scale", type=float, default=255.0, metavar="S",
+                   help="--intensity when compressing: the stored byte is rint(intensity * S) clamped to 0 .. 255 (default 255; 100 returns a "
+                        "KITTI sweep's values bit for bit).  The scale is stored in the container: decompressing takes no scale.")
     p.add_argument("--eval", action="store_true", help="evaluate the reconstruction quality.")
     p.add_argument("--cpu", action="store_true", help="accepted for compatibility; the HIP path has no CPU mode.")
     p.add_argument("--seed", type=int, default=0, help="seed of the ground / plane RANSAC (this build).")
@@ -141,21 +147,50 @@ def print_quality(point_cloud, point_cloud_rec):
     print("    Point-to-Plane PSNR (r=59.7): ", point_to_plane["psnr_mean"])
 
 
+def load_intensity_rows(dataset, path, filtered):
+    """--intensity: the frame's rows (x, y, z, intensity), after the radius filter when it is on (the rows its index keeps)."""
+    rows = dataset.load_rows(path)
+    if filtered:
+        from rpcc_amd.outlier import remove_radius_outlier
+        rows = rows[remove_radius_outlier(rows, nb_points=3, radius=1)[1]]
+    return rows
+
+
+def print_intensity_error(transformer, rows, range_image, w_rec):
+    """--eval --intensity: the decoded intensities against the owners' intensities of the original, over the non-empty pixels."""
+    import torch
+    from rpcc_amd import ops
+    dev = transformer.device
+    rows_d = torch.from_numpy(np.ascontiguousarray(rows[:, :4], dtype=np.float32)).to(dev)
+    ri = torch.from_numpy(np.ascontiguousarray(range_image, dtype=np.float32).reshape(1, transformer.H, transformer.W)).to(dev)
+    own = torch.empty_like(ri)
+    offs = torch.tensor([0, rows_d.shape[0]], dtype=torch.int64, device=dev)
+    ops.intensity_encode(rows_d, offs, transformer.geom, ri, 1.0, owner_intensity=own)
+    set_ = (ri != 0)[0].cpu().numpy()
+    dif = np.abs(np.asarray(w_rec, dtype=np.float64).reshape(set_.shape) - own[0].cpu().numpy())[set_]
+    print("    Intensity Error (max): ", float(dif.max()) if dif.size else 0.0)
+    print("    Intensity Error (mean): ", float(dif.mean()) if dif.size else 0.0)
+
+
 def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform):
     """cluster_num above 254 (labels as uint16): the per-stage mirror classes keep labels in a byte, so the frame goes through the batch front-end
     (pipeline.BatchCompressor -> rpcc_compress_batch_wide) as a batch of one.  Same container, same decoder."""
     from rpcc_amd.pipeline import BatchCompressor
     dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
     t0 = time.time()
-    frame = dataset.load_data(args.input)
-    if getattr(args, "use_radius_outlier_removal", False):
-        from rpcc_amd.outlier import remove_radius_outlier
-        frame, _ = remove_radius_outlier(frame, nb_points=3, radius=1)
+    want_w = getattr(args, "intensity", False)
+    if want_w:     # the rows as stored (filtered like the points): the batch front-end makes the payload from its own range image
+        frame = load_intensity_rows(dataset, args.input, getattr(args, "use_radius_outlier_removal", False))
+    else:
+        frame = dataset.load_data(args.input)
+        if getattr(args, "use_radius_outlier_removal", False):
+            from rpcc_amd.outlier import remove_radius_outlier
+            frame, _ = remove_radius_outlier(frame, nb_points=3, radius=1)
     bc = BatchCompressor(dataset.PCTransformer, cluster_num=segment_cfg["cluster_num"], accuracy=accuracy / 2,
                          ground_threshold=segment_cfg["ground_vertical_threshold"], uniform=uniform, model_method=model_cfg["model_method"],
                          compressor_cfg=dict(cfg), basic_compressor=basic_compressor.method_name, seed=args.seed,
                          device_entropy=basic_compressor.device_entropy, device_bzip2=basic_compressor.device_bzip2,
-                         rans_delta=basic_compressor.rans_delta)
+                         rans_delta=basic_compressor.rans_delta, intensity_scale=args.intensity_scale if want_w else None)
     blob = bc.compress([frame], frame_ids=[frame_identity(args.input)])[0]
     with open(args.output, "wb") as f:
         f.write(blob)
@@ -172,8 +207,9 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
     if args.eval:
         from rpcc_amd.tools.decompress import decode_frame
         level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
-        rec, _, _ = decode_frame(read_compressed_bitstream(args.output, uniform=uniform), basic_compressor, dataset.PCTransformer,
-                                 segment_cfg["cluster_num"], accuracy, level_acc, uniform, want_points=False)
+        rec, _, _, *w = decode_frame(read_compressed_bitstream(args.output, uniform=uniform, intensity=want_w), basic_compressor,
+                                     dataset.PCTransformer, segment_cfg["cluster_num"], accuracy, level_acc, uniform, want_points=False,
+                                     intensity=want_w)
         ri = buf.ri[0].cpu().numpy()
         dif = np.abs(rec - ri)   # every pixel, empty ones included, as compress() below and tools/compress.py:172-181
         bound = accuracy + (0.0 if uniform else 0.06) + 0.00001
@@ -184,6 +220,8 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
             raise AssertionError("Reconstruction error... Please check...")
         T = dataset.PCTransformer
         print_quality(T.range_image_to_point_cloud(ri), T.range_image_to_point_cloud(rec))
+        if want_w:
+            print_intensity_error(T, frame, ri, w[0])
 
 
 def compress(args):
@@ -218,8 +256,12 @@ def compress(args):
     QM = make_quantizer(cfg, accuracy, uniform)
     residual_quantized, salience_level, key_point_map = QM.quantize_residual(residual, seg_idx, point_cloud, range_image)
     t_quantization = time.time()
+    want_w, rows, payload = getattr(args, "intensity", False), None, None
+    if want_w:     # the frame's rows against the range image they were projected to
+        rows = load_intensity_rows(dataset, args.input, filtered)
+        payload, _ = encode_intensity(dataset.PCTransformer, rows, range_image[..., 0], args.intensity_scale)
     original_data, compressed_data = compress_point_cloud(basic_compressor, model_param, seg_idx, salience_level,
-                                                          residual_quantized, full=False)
+                                                          residual_quantized, full=False, intensity=payload)
     t_basic_compressor = time.time()
     save_compressed_bitstream(args.output, compressed_data, uniform=uniform)
     t_save = time.time()
@@ -257,6 +299,13 @@ def compress(args):
         if float(np.max(dif)) > bound:
             raise AssertionError("Reconstruction error... Please check...")
         print_quality(point_cloud, dataset.PCTransformer.range_image_to_point_cloud(rec))
+        if want_w:
+            from rpcc_amd.tools.decompress import decode_frame
+            level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
+            w = decode_frame(read_compressed_bitstream(args.output, uniform=uniform, intensity=True), basic_compressor, dataset.PCTransformer,
+                             None if segment_cfg["segment_method"] == "DBSCAN" else segment_cfg["cluster_num"], accuracy, level_acc, uniform,
+                             want_points=False, intensity=True)[3]
+            print_intensity_error(dataset.PCTransformer, rows, range_image[..., 0], w)
 
 
 if __name__ == "__main__":

@@ -109,12 +109,17 @@ def compress(args, streaming_factory=None):
                          rans_delta=basic_compressor.rans_delta,
                          segment_method=segment_cfg["segment_method"], DBSCAN_eps=segment_cfg["DBSCAN_eps"],
                          max_labels=getattr(args, "max_labels", None),
-                         radius_outlier_removal=(3, 1.0) if getattr(args, "use_radius_outlier_removal", False) else None)
+                         radius_outlier_removal=(3, 1.0) if getattr(args, "use_radius_outlier_removal", False) else None,
+                         intensity_scale=args.intensity_scale if getattr(args, "intensity", False) else None)
     mine = shard_indices(len(dataset), rank, world)
     # the ingest mode follows from the WHOLE datalist -- the same decision on every rank, also on one whose shard is empty -- and is
     # settled before the process group forms, so that a datalist --ingest rows cannot take fails on all ranks together
     want = getattr(args, "ingest", "auto")
     all_bin = all(str(name).endswith(".bin") for name in dataset.data_list)
+    if getattr(args, "intensity", False):      # the fourth column must reach the device: the rows as stored
+        if not all_bin or want == "xyz":
+            raise SystemExit("--intensity needs a datalist of .bin files (float32 rows x, y, z, intensity)" + (" and not --ingest xyz" if want == "xyz" else ""))
+        want = "rows"
     if want == "rows" and not all_bin:
         raise SystemExit("--ingest rows needs a datalist of .bin files (float32 rows x, y, z, intensity)")
     ingest = "rows" if (len(dataset) > 0 and (want == "rows" or (want == "auto" and all_bin))) else "xyz"

@@ -15,9 +15,9 @@ import torch  # noqa: E402
 
 import rpcc_amd  # noqa: E402,F401
 from rpcc_amd import ops  # noqa: E402
-from rpcc_amd.compress_utils import decompress_point_cloud, read_compressed_bitstream  # noqa: E402
+from rpcc_amd.compress_utils import decompress_point_cloud, parse_intensity_payload, read_compressed_bitstream  # noqa: E402,F401
 from rpcc_amd.dataset import build_dataset  # noqa: E402
-from rpcc_amd.tools.compress import make_parser, print_quality, resolve_cfg  # noqa: E402
+from rpcc_amd.tools.compress import make_parser, print_intensity_error, print_quality, resolve_cfg  # noqa: E402
 
 
 def stream_cluster_num(segment_cfg):
@@ -26,10 +26,13 @@ def stream_cluster_num(segment_cfg):
     return None if segment_cfg["segment_method"] == "DBSCAN" else segment_cfg["cluster_num"]
 
 
-def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy, level_acc, uniform, want_points=True, decoded=None):
+def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy, level_acc, uniform, want_points=True, decoded=None,
+                 intensity=False):
     """decompress_point_cloud + dequantise + predict + back-project (tools/decompress.py:79-112).  cluster_num None
     (DBSCAN, stream_cluster_num): the labels 0 .. rows - 1 of the stream's model rows.  decoded: blob_dict's arrays with the entropy
-    stage already undone (basic_compressor.decompress_dicts over a chunk of frames)."""
+    stage already undone (basic_compressor.decompress_dicts over a chunk of frames).
+    intensity=True: blob_dict holds the container's 'intensity' trailer (unpack_bitstream(..., intensity=True)); a fourth value is
+    returned, f32 [H,W], by ops.intensity_decode on the label map just recovered; ValueError when the payload is refused."""
     H, W = transformer.H, transformer.W
     d = basic_compressor.decompress_dict(blob_dict) if decoded is None else decoded
     # The .rpcc file stores no configuration (as in the reference): a wrong --lidar / cluster_num / framework shows up as
@@ -85,7 +88,20 @@ def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy
         sl = np.frombuffer(d["salience_level"], dtype=np.uint8)
         sal[0, : sl.size] = torch.from_numpy(sl.copy()).to(dev)
         rec, pc = ops.decode(seg, q, model, transformer.tm_dev, list(level_acc), salience=sal, want_points=want_points)
-    return rec[0].cpu().numpy(), (pc[0].cpu().numpy() if pc is not None else None), seg[0].cpu().numpy()
+    out = rec[0].cpu().numpy(), (pc[0].cpu().numpy() if pc is not None else None), seg[0].cpu().numpy()
+    if not intensity:
+        return out
+    if "intensity" not in d:
+        raise ValueError("the bitstream holds no intensity payload (compressed without --intensity?)")
+    scale, _ = parse_intensity_payload(d["intensity"], n_nonempty)     # (the refusals in words; the device decoder checks the same)
+    pay = torch.from_numpy(np.frombuffer(d["intensity"], dtype=np.uint8).copy()[None]).to(dev)
+    nbytes = torch.tensor([pay.shape[1]], dtype=torch.int32, device=dev)
+    if pay.shape[1] < 8 + P:      # rpcc_intensity_decode takes rows of at least 8 + P bytes
+        pay = torch.cat([pay, torch.zeros((1, 8 + P - pay.shape[1]), dtype=torch.uint8, device=dev)], 1)
+    w, status = ops.intensity_decode(pay, nbytes, seg)
+    if int(status[0]) != 0:
+        raise ValueError("intensity payload refused by the device decoder (status %d)" % int(status[0]))
+    return out + (w[0].cpu().numpy(),)
 
 
 def decompress(args):
@@ -95,11 +111,12 @@ def decompress(args):
     dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     t0 = time.time()
-    cd = read_compressed_bitstream(args.input, uniform=uniform)
-    rec, pc, seg = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
-                                level_acc, uniform)
+    want_w = getattr(args, "intensity", False)
+    cd = read_compressed_bitstream(args.input, uniform=uniform, intensity=want_w)
+    rec, pc, seg, *w = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
+                                    level_acc, uniform, intensity=want_w)
     t1 = time.time()
-    dataset.save_point_cloud_to_file(args.output, pc.reshape(-1, 3))
+    dataset.save_point_cloud_to_file(args.output, pc.reshape(-1, 3), intensity=w[0].reshape(-1) if want_w else None)
     print("\nDecompression finished.")
     print("reconstructed point cloud save in ", args.output)
     print("    Decode time: ", t1 - t0)
@@ -116,6 +133,8 @@ def decompress(args):
         print("    Depth Error (mean): ", float(np.mean(dif)))
         print("    Depth Error (max): ", float(np.max(dif)))
         print_quality(point_cloud, pc)
+        if want_w:
+            print_intensity_error(dataset.PCTransformer, dataset.load_rows(args.original_point_cloud), range_image[..., 0], w[0])
 
 
 if __name__ == "__main__":

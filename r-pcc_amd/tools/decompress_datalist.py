@@ -33,17 +33,17 @@ def decompress_batched(args, dataset, mine, cluster_num, accuracy, level_acc, un
     # (DBSCAN streams: cluster_num None -- the label count is the frame's; the batch decodes them under a label cap)
     cap = (getattr(args, "max_labels", None) or 1023) if cluster_num is None else None
     bd = BatchDecompressor(dataset.PCTransformer, cluster_num, accuracy, uniform=uniform, level_acc=level_acc, basic_compressor=basic_compressor,
-                           max_labels=cap)
+                           max_labels=cap, intensity=getattr(args, "intensity", False))
     for c0 in range(0, len(mine), CHUNK):
         names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
         blobs = []
         for name in names:
             with open(name, "rb") as f:
                 blobs.append(f.read())
-        for name, (rec, pc, _) in zip(names, bd.decompress(blobs)):
+        for name, (rec, pc, _, *w) in zip(names, bd.decompress(blobs)):
             out = output_path(args, name)
             os.makedirs(os.path.dirname(out), exist_ok=True)
-            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3))
+            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3), intensity=w[0].reshape(-1) if w else None)
             if args.output:
                 print("%s -> %s (%d points)" % (name, out, int((rec != 0).sum())))
 
@@ -61,15 +61,16 @@ def decompress(args):
         return decompress_batched(args, dataset, mine, stream_cluster_num(segment_cfg), accuracy, level_acc, uniform, basic_compressor)
     for c0 in range(0, len(mine), CHUNK):
         names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
-        cds = [read_compressed_bitstream(name, uniform=uniform) for name in names]
+        want_w = getattr(args, "intensity", False)
+        cds = [read_compressed_bitstream(name, uniform=uniform, intensity=want_w) for name in names]
         for name, cd, d in zip(names, cds, basic_compressor.decompress_dicts(cds)):   # the chunk's entropy stage in one call where the back-end has one
-            rec, pc, _ = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
-                                      level_acc, uniform, decoded=d)
+            rec, pc, _, *w = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
+                                          level_acc, uniform, decoded=d, intensity=want_w)
             rel = name[1:] if name.startswith("/") else name
             out = os.path.join(args.output_dir, rel)
             out = out.replace(out.split(".")[-1], "bin")
             os.makedirs(os.path.dirname(out), exist_ok=True)
-            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3))
+            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3), intensity=w[0].reshape(-1) if w else None)
             if args.output:
                 print("%s -> %s (%d points)" % (name, out, int((rec != 0).sum())))
 

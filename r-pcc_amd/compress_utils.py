@@ -121,13 +121,88 @@ def compress_point_cloud(basic_compressor, plane_param, cluster_idx, salience_le
     return original_data, basic_compressor.compress_dict(original_data)
 
 
-_ORDER = ("contour_map", "idx_sequence", "plane_param", "residual_quantized")
+# The .rpcc container's payloads, one row each, in file order: the name, the dtype of the decoded array, the decoded bytes of one frame at
+# most as a function of (P pixels, K = cluster_num + 2 model rows), and the per-frame count that cuts the frame's part out of the batch's
+# buffer (frame_slices).  Everything else that is said about a column is derived from its row: the element width handed to rANS is
+# dtype.itemsize, the delta filter is rans_codec.delta_filter(dtype).
+Column = collections.namedtuple("Column", "name dtype bound cut")
+SCHEMA = (Column("salience_level", np.dtype(np.uint8), lambda P, K: K, "nrow"),
+          Column("contour_map", np.dtype(np.uint8), lambda P, K: (P + 7) // 8, "row"),
+          Column("idx_sequence", np.dtype(np.uint16), lambda P, K: 2 * P, "nseq"),
+          Column("plane_param", np.dtype(np.float32), lambda P, K: 16 * K, "nrow"),
+          Column("residual_quantized", np.dtype(np.int16), lambda P, K: 2 * P, "nnz"),
+          Column("intensity", np.dtype(np.uint8), lambda P, K: 8 + P, "nbytes"))
 INTENSITY_MAGIC = b"RPI1"
 
 
+def columns(uniform, intensity=False):
+    """The rows of SCHEMA a container holds, in file order: salience first with the non-uniform framework, intensity (the trailer no
+    reference reader looks at) last where it is carried."""
+    return SCHEMA[1 if uniform else 0: 6 if intensity else 5]
+
+
 def _keys(uniform, data=()):
-    """The arrays of a container in file order; 'intensity' (the trailer no reference reader looks at) where the frame holds it."""
-    return (() if uniform else ("salience_level",)) + _ORDER + (("intensity",) if "intensity" in data else ())
+    """The arrays of a container in file order; 'intensity' where the frame holds it."""
+    return tuple(c.name for c in columns(uniform, "intensity" in data))
+
+
+def payload_spans(blob, count):
+    """The one walk over a container: [int32 length | bytes] per payload.  Yields (start, length) of the first count payloads and ends
+    before the first one the blob does not hold: a prefix that is cut off or negative, or a payload longer than the bytes left."""
+    off = 0
+    for _ in range(count):
+        if off + 4 > len(blob):
+            return
+        (n,) = struct.unpack_from("i", blob, off)
+        if n < 0 or off + 4 + n > len(blob):
+            return
+        yield off + 4, n
+        off += 4 + n
+
+
+def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None):
+    """Which elements of which buffer are frame b's column c, stated once for the host assembly (BatchPayload: arrays read back or pinned)
+    and for the device containers (addresses).  buffers: {column name: the batch's buffer}; counts [B,K], nnz / nseq / nbytes [B] -- all
+    numpy arrays or all torch tensors of one device.  -> {name: (start, length)}, int64 [B] of the same kind, in elements of the column's
+    dtype into the flattened buffer.  By the column's cut: 'row', 'nrow' and 'nbytes' columns are rows of a padded [B, ...] array -- the
+    whole row, its first nrow sub-rows, its first nbytes elements; 'nseq' and 'nnz' columns lie packed back to back, frame b at the sum of
+    the counts before it.  nrow = max(seg) + 1 (tools/compress.py:102) = 1 + the index of the last non-zero count; 0 for a row of zeros,
+    which no frame has (its counts sum to P)."""
+    if torch.is_tensor(counts):
+        xp, i64, ar = torch, (lambda v: v.to(torch.int64)), (lambda lo, hi: torch.arange(lo, hi, dtype=torch.int64, device=counts.device))
+    else:
+        xp, i64, ar = np, (lambda v: np.asarray(v, np.int64)), (lambda lo, hi: np.arange(lo, hi, dtype=np.int64))
+    B, K = counts.shape
+    n = {"nrow": xp.amax(i64(counts != 0) * ar(1, K + 1), 1), "nseq": i64(nseq), "nnz": i64(nnz), "nbytes": None if nbytes is None else i64(nbytes)}
+    out = {}
+    for c in cols:
+        if c.cut in ("nseq", "nnz"):
+            out[c.name] = (xp.cumsum(n[c.cut], 0) - n[c.cut], n[c.cut])
+            continue
+        shape = tuple(buffers[c.name].shape)
+        row, sub = int(np.prod(shape[1:])), int(np.prod(shape[2:]))
+        out[c.name] = (ar(0, B) * row, ar(0, B) * 0 + row if c.cut == "row" else n[c.cut] * sub)
+    return out
+
+
+class BatchPayload:
+    """What the container of every frame of a batch is assembled from: views into the batch's host buffers -- a streaming slot's pinned
+    ones or the arrays BatchCompressor.collect read back -- cut by frame_slices.  cols: columns(...); buffers, counts, nnz, nseq, nbytes:
+    frame_slices' (numpy), the buffers read as the columns' dtypes; n: the frames that count (the first n; default all).
+    frame(b) -> the dict compress_point_cloud builds (utils/compress_utils.py:138-179), before the entropy coder: views, no copies."""
+
+    def __init__(self, cols, buffers, counts, nnz, nseq, nbytes=None, n=None):
+        self.n = len(nnz) if n is None else n
+        at = frame_slices(cols, buffers, counts, nnz, nseq, nbytes)
+        # per column: the flattened buffer, the frames' first and last + 1 elements, the shape of a sub-row (the model's rows keep their [., 4])
+        self.parts = [(c.name, buffers[c.name].reshape(-1).view(c.dtype), lo.tolist(), (lo + n_el).tolist(), (-1,) + tuple(buffers[c.name].shape[2:]))
+                      for c in cols for lo, n_el in (at[c.name],)]
+
+    def frame(self, b):
+        return {name: flat[lo[b]: hi[b]].reshape(shape) for name, flat, lo, hi, shape in self.parts}
+
+    def __len__(self):
+        return self.n
 
 
 def intensity_payload(q, scale):
@@ -152,18 +227,10 @@ def parse_intensity_payload(data, n):
 def intensity_trailer_span(blob, uniform=True):
     """(start, end) of the coded 'intensity' bytes of a container, or None: what follows the known payloads must be exactly one
     [int32 length | bytes] that ends the blob."""
-    off = 0
-    for _ in _keys(uniform):
-        if off + 4 > len(blob):
-            return None
-        (n,) = struct.unpack_from("i", blob, off)
-        if n < 0 or off + 4 + n > len(blob):
-            return None
-        off += 4 + n
-    if off + 4 > len(blob):
+    spans = list(payload_spans(blob, len(columns(uniform, True))))
+    if len(spans) < len(columns(uniform, True)) or sum(spans[-1]) != len(blob):
         return None
-    (n,) = struct.unpack_from("i", blob, off)
-    return (off + 4, off + 4 + n) if n >= 0 and off + 4 + n == len(blob) else None
+    return spans[-1][0], sum(spans[-1])
 
 
 BEAM_TABLE_INTENSITY = ("intensity with a per-beam elevation table (channel_distribute_csv): that projection's rule is 'the last point wins', "
@@ -232,17 +299,17 @@ def pack_frames(basic_compressor, frames, uniform=True):
 def unpack_bitstream(blob, uniform=True, intensity=False):
     """intensity=True (a caller that asks for it): the dictionary also holds 'intensity', the coded trailer -- ValueError unless what
     follows the known payloads is exactly one length-prefixed payload that ends the blob.  Without it: trailing bytes are ignored, as ever."""
-    out, off = {}, 0
-    for k in (() if uniform else ("salience_level",)) + _ORDER:
+    keys = _keys(uniform)
+    spans = list(payload_spans(blob, len(keys)))
+    off = sum(spans[-1]) if spans else 0      # where the walk ended
+    if len(spans) < len(keys):
         # (the reference reads whatever f.read(n) returns; a truncated or foreign file then fails somewhere inside the entropy decoder)
+        k = keys[len(spans)]
         if off + 4 > len(blob):
             raise ValueError("bitstream ends before the length of '%s' (%d bytes; written with the %s framework?)"
                              % (k, len(blob), "non-uniform" if uniform else "uniform"))
-        (n,) = struct.unpack_from("i", blob, off)
-        if n < 0 or off + 4 + n > len(blob):
-            raise ValueError("bitstream: payload '%s' claims %d bytes, %d are left" % (k, n, len(blob) - off - 4))
-        out[k] = blob[off + 4: off + 4 + n]
-        off += 4 + n
+        raise ValueError("bitstream: payload '%s' claims %d bytes, %d are left" % (k, struct.unpack_from("i", blob, off)[0], len(blob) - off - 4))
+    out = {k: blob[s: s + n] for k, (s, n) in zip(keys, spans)}
     if intensity:
         span = intensity_trailer_span(blob, uniform)
         if span is None:
@@ -277,15 +344,16 @@ def decompress_point_cloud(compressed_data, basic_compressor, model_num, H, W):
 # One row per basic_compressor method: the host library's functions (None: there is none, the device modules are used whatever the flags
 # say -- 'lz4' takes the lz4 package first where it is installed, see BasicCompressor._lz4), the device encoder --
 # module of this package, its list encoder, the BasicCompressor flag that turns it on -- and the device decoder alike; work_slots: its
-# decode_descriptors takes work slots.  The modules are imported where a row is used, not here.
-Backend = collections.namedtuple("Backend", "host_encode host_decode encoder encode_many encode_flag decoder decode_many decode_flag work_slots")
-_GZIP = Backend(gzip.compress, gzip.decompress, "deflate_codec", "compress_many", "device_entropy", "inflate_codec", "decompress_many", "device_entropy", False)
+# decode_descriptors takes work slots; typed: its encode_descriptors takes each stream's element width (widths=) and filter (filters=).
+# The modules are imported where a row is used, not here.
+Backend = collections.namedtuple("Backend", "host_encode host_decode encoder encode_many encode_flag decoder decode_many decode_flag work_slots typed")
+_GZIP = Backend(gzip.compress, gzip.decompress, "deflate_codec", "compress_many", "device_entropy", "inflate_codec", "decompress_many", "device_entropy", False, False)
 BACKENDS = {
-    "lz4": Backend(None, None, "lz4_codec", "dumps_many", None, "lz4_codec", "loads_many", None, False),
-    "bzip2": Backend(bz2.compress, bz2.decompress, "bzip2_codec", "compress_many", "device_bzip2", "bunzip2_codec", "decompress_many", "device_bunzip2", True),
+    "lz4": Backend(None, None, "lz4_codec", "dumps_many", None, "lz4_codec", "loads_many", None, False, False),
+    "bzip2": Backend(bz2.compress, bz2.decompress, "bzip2_codec", "compress_many", "device_bzip2", "bunzip2_codec", "decompress_many", "device_bunzip2", True, False),
     "gzip": _GZIP,
     "deflate": _GZIP,
-    "rans": Backend(None, None, "rans_codec", "compress_many", None, "rans_codec", "decompress_many", None, False),
+    "rans": Backend(None, None, "rans_codec", "compress_many", None, "rans_codec", "decompress_many", None, False, True),
 }
 
 

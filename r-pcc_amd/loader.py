@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .compress_utils import pack_bitstream, pack_frames  # noqa: F401
+from .compress_utils import BatchPayload, pack_bitstream, pack_frames  # noqa: F401
 from .utils import available_cpus
 
 
@@ -39,7 +39,7 @@ class _Slot:
         self.ground = torch.zeros((B, 4), dtype=torch.float64, device=device)
         self.buf = bc.new_buffers(B, max_points=self.cap)
         self.codec_ws = ops.codec_workspace(B, P, bc.M, device)
-        # packed device payload + its pinned mirror: residuals (<= points), index sequence (<= pixels), bits, rows, lengths
+        # packed device payload + the pinned mirror of every column's buffer (compress_utils.SCHEMA) and of the counts frame_slices cuts them by
         self.qp = torch.empty((self.cap,), dtype=torch.int16, device=device)
         self.sp = torch.empty((B * P,), dtype=torch.int16, device=device)
         self.tot = torch.zeros((2,), dtype=torch.int64, device=device)
@@ -69,38 +69,6 @@ class _Slot:
         self.xyz_dev = torch.empty((self.cap, self.cols), dtype=torch.float32, device=device)
         self.qp = torch.empty((self.cap,), dtype=torch.int16, device=device)
         self.qp_pin = torch.empty((self.cap,), dtype=torch.int16).pin_memory()
-
-
-class BatchPayload:
-    """What the container of every frame of a batch is assembled from: views into a slot's pinned output buffers.
-    frame(b) -> the dict compress_point_cloud builds (utils/compress_utils.py:138-179), before the entropy coder."""
-
-    def __init__(self, slot, uniform):
-        n = self.n = slot.n
-        nnz, nseq = slot.nnz_pin.numpy()[:n].astype(np.int64), slot.nseq_pin.numpy()[:n].astype(np.int64)
-        self.qo, self.so = np.concatenate([[0], np.cumsum(nnz)]), np.concatenate([[0], np.cumsum(nseq)])
-        self.q16, self.seq = slot.qp_pin.numpy(), slot.sp_pin.numpy().view(np.uint16)
-        self.bits, self.model = slot.bits_pin.numpy(), slot.model_pin.numpy()
-        counts = slot.counts_pin.numpy()[:n]
-        K = counts.shape[1]
-        self.nrow = np.where(counts.any(1), K - np.argmax(counts[:, ::-1] != 0, axis=1), 2)   # max(seg)+1 rows (tools/compress.py:102)
-        self.sal = slot.sal_pin.numpy() if (slot.sal_pin is not None and not uniform) else None
-        self.intensity = None if slot.int_pin is None else (slot.int_pin.numpy(), slot.int_n_pin.numpy()[0])
-
-    def frame(self, b):
-        nrow = int(self.nrow[b])
-        od = {"residual_quantized": self.q16[self.qo[b]: self.qo[b + 1]]}
-        if self.sal is not None:
-            od["salience_level"] = self.sal[b, :nrow]
-        od["contour_map"] = self.bits[b]
-        od["idx_sequence"] = self.seq[self.so[b]: self.so[b + 1]]
-        od["plane_param"] = self.model[b, :nrow]
-        if self.intensity is not None:
-            od["intensity"] = self.intensity[0][b, : self.intensity[1][b]]
-        return od
-
-    def __len__(self):
-        return self.n
 
 
 class StreamingCompressor:
@@ -249,7 +217,12 @@ class StreamingCompressor:
             with torch.cuda.stream(self.side_stream):
                 slot.sp_pin[self.seq_eager:stot].copy_(slot.sp[self.seq_eager:stot], non_blocking=True)
             self.side_stream.synchronize()
-        return BatchPayload(slot, uniform=self.bc.uniform)
+        # the columns' pinned buffers (compress_utils.SCHEMA), cut per frame by the rule BatchCompressor.collect uses (frame_slices)
+        num = lambda t: None if t is None else t.numpy()
+        bufs = dict(salience_level=num(slot.sal_pin), contour_map=num(slot.bits_pin), idx_sequence=num(slot.sp_pin), plane_param=num(slot.model_pin),
+                    residual_quantized=num(slot.qp_pin), intensity=num(slot.int_pin))
+        return BatchPayload(self.bc.columns, bufs, num(slot.counts_pin), num(slot.nnz_pin), num(slot.nseq_pin),
+                            None if slot.int_pin is None else num(slot.int_n_pin)[0], n=slot.n)
 
     def _encode_chunk(self, payload, lo, hi):
         bc = self.bc

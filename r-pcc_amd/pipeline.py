@@ -2,16 +2,15 @@
 payload assembly (casts, container, entropy coder) of the reference's compress_point_cloud /
 save_compressed_bitstream.  This is the counterpart of the closure body of
 tools/compress_datalist.py:91-142 for a whole batch at once.  BatchDecompressor is the way back: a list of .rpcc containers through one
-entropy launch and one fused decode call per chunk."""
-import inspect
-import struct
-
+entropy launch and one fused decode call per chunk.  What a container holds -- the columns, their order, dtypes and
+bounds, and which part of a batch's buffers is one frame's -- is compress_utils.SCHEMA / columns / frame_slices."""
 import numpy as np
 import torch
 
 from . import entropy, ops
 from . import _lib
-from .compress_utils import _ORDER, BEAM_TABLE_INTENSITY, BasicCompressor, intensity_trailer_span, device_decoder, pack_bitstream, pack_frames, unpack_bitstream  # noqa: F401
+from .compress_utils import (BACKENDS, BEAM_TABLE_INTENSITY, BasicCompressor, BatchPayload, columns, device_decoder, frame_slices, intensity_trailer_span,
+                             pack_bitstream, pack_frames, payload_spans, unpack_bitstream)  # noqa: F401
 
 
 class BatchCompressor:
@@ -225,45 +224,38 @@ class BatchCompressor:
         qp, qtot = ops.pack_payload(buf.q16, buf.nnz, capacity=npts)
         sp, stot = ops.pack_payload(seq.view(torch.int16), nseq)
         buf.in_flight = True    # until collect() has read it (_buffers)
-        ctx = dict(n=n, buf=buf, bits=bits, nseq=nseq, sal=sal, qp=qp, qtot=qtot, sp=sp, stot=stot,
+        # the batch's buffer of every column (compress_utils.SCHEMA; frame_slices cuts the frames out of them) and the per-frame counts
+        pay, nbytes, _ = buf.intensity if self.intensity_scale is not None else (None, None, None)
+        bufs = dict(salience_level=sal, contour_map=bits, idx_sequence=sp, plane_param=buf.model, residual_quantized=qp, intensity=pay)
+        ctx = dict(n=n, buf=buf, bufs=bufs, counts=(buf.counts, buf.nnz, nseq, nbytes), tot=dict(nnz=qtot, nseq=stot),
                    stream=torch.cuda.current_stream(self.device), keep=(xyz, g, seq))
         codec = self.bc.batch_codec()
         if codec:
-            ctx["containers"] = self._device_containers(codec[0], n, buf, bits, nseq, sal, qp, sp)
+            ctx["containers"] = self._device_containers(codec[0], bufs, *ctx["counts"])
         return ctx
 
-    def _device_containers(self, codec, B, buf, bits, nseq, sal, qp, sp):
+    @property
+    def columns(self):
+        return columns(self.uniform, self.intensity_scale is not None)
+
+    def _device_containers(self, codec, bufs, counts, nnz, nseq, nbytes):
         """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), 'deflate' / 'gzip' with device_entropy (deflate_codec),
-        'bzip2' with device_bzip2 (bzip2_codec) or 'rans' (rans_codec, which is also told each column's element width, as the per-frame
-        path takes it from the arrays' itemsize, and -- with rans_delta -- each column's filter, by the same rule from its dtype):
-        the batch's .rpcc containers are built in HBM (the codec's encode_descriptors over the arrays where they lie, then
-        rpcc_lz4_pack_containers, which asks nothing of the streams' format) on the current stream.
-        -> (containers, frame offsets / lengths)."""
+        'bzip2' with device_bzip2 (bzip2_codec) or 'rans' (rans_codec, a typed back-end: it is also told each column's element width, as
+        the per-frame path takes it from the arrays' itemsize, and -- with rans_delta -- each column's filter, by the same rule from its
+        dtype): the batch's .rpcc containers are built in HBM (the codec's encode_descriptors over the arrays where they lie -- the
+        columns' bounds and dtypes from compress_utils.SCHEMA, their places from frame_slices -- then rpcc_lz4_pack_containers, which
+        asks nothing of the streams' format) on the current stream.  -> (containers, frame offsets / lengths)."""
         from . import lz4_codec
-        dev, K, P = self.device, buf.counts.shape[1], self.T.H * self.T.W
-        i64 = dict(dtype=torch.int64, device=dev)
-        nrow = ((buf.counts != 0).to(torch.int64) * torch.arange(1, K + 1, **i64)).amax(1)   # max(seg) + 1 (tools/compress.py:102)
-        nnz, ns = buf.nnz.to(torch.int64), nseq.to(torch.int64)
-        excl = lambda v: torch.cumsum(v, 0) - v
-        rows = torch.arange(B, **i64)
-        nb = bits.shape[1]
-        # per frame, in container order: (device address, bytes, host bound of the bytes, element width, dtype as the per-frame path codes it)
-        cols = [(bits.data_ptr() + rows * nb, torch.full((B,), nb, **i64), nb, 1, np.uint8),
-                (sp.data_ptr() + 2 * excl(ns), 2 * ns, 2 * P, 2, np.uint16),
-                (buf.model.data_ptr() + rows * (K * 16), 16 * nrow, 16 * K, 4, np.float32),
-                (qp.data_ptr() + 2 * excl(nnz), 2 * nnz, 2 * P, 2, np.int16)]
-        if sal is not None:
-            cols.insert(0, (sal.data_ptr() + rows * K, nrow, K, 1, np.uint8))
-        if self.intensity_scale is not None:     # the trailer: a payload row each, its 8 + n bytes
-            pay, nbytes, _ = buf.intensity
-            cols.append((pay.data_ptr() + rows * pay.stride(0), nbytes.to(torch.int64), 8 + P, 1, np.uint8))
-        addr = torch.stack([c[0] for c in cols], 1).reshape(-1)
-        lens = torch.stack([c[1] for c in cols], 1).reshape(-1)
-        takes = inspect.signature(codec.encode_descriptors).parameters
-        kw = dict(widths=[c[3] for c in cols] * B) if "widths" in takes else {}
-        if "filters" in takes and self.bc.rans_delta:      # delta for the residual column only (rans_codec.delta_filter)
-            kw["filters"] = [codec.delta_filter(c[4]) for c in cols] * B
-        slots, dst_off, dst_len, _ = codec.encode_descriptors(addr, lens, [c[2] for c in cols] * B, **kw)
+        (B, K), P, cols = counts.shape, self.T.H * self.T.W, self.columns
+        at = frame_slices(cols, bufs, counts, nnz, nseq, nbytes)
+        # per frame, in container order: device address and bytes of every column
+        addr = torch.stack([bufs[c.name].data_ptr() + c.dtype.itemsize * at[c.name][0] for c in cols], 1).reshape(-1)
+        lens = torch.stack([c.dtype.itemsize * at[c.name][1] for c in cols], 1).reshape(-1)
+        typed = BACKENDS[self.bc.method_name].typed
+        kw = dict(widths=[c.dtype.itemsize for c in cols] * B) if typed else {}
+        if typed and self.bc.rans_delta:      # delta for the residual column only (rans_codec.delta_filter)
+            kw["filters"] = [codec.delta_filter(c.dtype) for c in cols] * B
+        slots, dst_off, dst_len, _ = codec.encode_descriptors(addr, lens, [c.bound(P, K) for c in cols] * B, **kw)
         cap = int(slots.numel()) + 4 * len(cols) * B
         out, frame = lz4_codec.pack_containers(slots, dst_off, dst_len, B, len(cols), cap)
         return out, frame, (addr, lens, slots, dst_off, dst_len)
@@ -277,63 +269,34 @@ class BatchCompressor:
         """Waits for submit()'s stream and assembles the .rpcc byte strings (host part: casts, container, entropy coder).
         pool: a concurrent.futures executor -- the frames' entropy coding then runs on its threads (bz2 / zlib / lz4
         release the GIL), like the reference's --workers ThreadPoolExecutor (tools/compress_datalist.py:202-206)."""
-        buf = ctx["buf"]
-        if "containers" in ctx:
-            return self._collect_containers(ctx)
+        buf, built = ctx["buf"], ctx.get("containers")
         try:
             ctx["stream"].synchronize()
-            bits, nseq, sal = ctx["bits"], ctx["nseq"], ctx["sal"]
-            nnz, nseq_h = buf.nnz.cpu().numpy(), nseq.cpu().numpy()
-            seg_max = buf.counts.cpu().numpy()
-            q16 = ctx["qp"][: int(ctx["qtot"].item())].cpu().numpy()
-            seq_h = ctx["sp"][: int(ctx["stot"].item())].cpu().numpy().view(np.uint16)
-            qo, so = np.concatenate([[0], np.cumsum(nnz)]), np.concatenate([[0], np.cumsum(nseq_h)])
-            bits_h, model = bits.cpu().numpy(), buf.model.cpu().numpy()
-            sal_h = None if sal is None else sal.cpu().numpy()
+            if built:       # by _device_containers: the frames' places now, the containers in one copy below
+                fr = built[1].cpu().numpy()
+            else:           # the columns' buffers, the packed ones as far as the batch filled them
+                bufs, tot, cols = ctx["bufs"], ctx["tot"], self.columns
+                counts, nnz, nseq, nbytes = (None if t is None else t.cpu().numpy() for t in ctx["counts"])
+                host = {c.name: (bufs[c.name][: int(tot[c.cut].item())] if c.cut in tot else bufs[c.name]).cpu().numpy() for c in cols}
             status = buf.status.cpu().numpy() if self.dbscan else None
-            if self.intensity_scale is not None:
-                pay_h, pay_n, orphans = (t.cpu().numpy() for t in buf.intensity)
+            orphans = buf.intensity[2].cpu().numpy() if self.intensity_scale is not None else None
         finally:
             buf.in_flight = False   # everything collect() needs is on the host -- or the call failed: either way the slot is free again
-        self.check_status(status)
-        if self.intensity_scale is not None:
-            self.check_orphans(orphans[: ctx["n"]])
-        def assemble(b):
-            nrow = int(np.flatnonzero(seg_max[b])[-1]) + 1          # max(seg)+1 rows (tools/compress.py:102)
-            od = {"residual_quantized": q16[qo[b]: qo[b + 1]]}
-            if sal_h is not None:
-                od["salience_level"] = sal_h[b, :nrow]
-            od["contour_map"] = bits_h[b]
-            od["idx_sequence"] = seq_h[so[b]: so[b + 1]]
-            od["plane_param"] = model[b, :nrow]
-            if self.intensity_scale is not None:
-                od["intensity"] = pay_h[b, : pay_n[b]]
-            return od
-        # a few frames per task: one call into the host library per chunk (compress_utils.pack_frames)
         n = ctx["n"]
+        self.check_status(status)
+        if orphans is not None:
+            self.check_orphans(orphans[:n])
+        if built:
+            if (fr[1, :n] < 0).any():
+                raise RuntimeError("rpcc_lz4: the containers of frames %s were not built" % np.flatnonzero(fr[1, :n] < 0).tolist())
+            h = built[0][: int((fr[0, :n] + fr[1, :n]).max()) if n else 0].cpu().numpy()
+            return [h[o: o + l].tobytes() for o, l in zip(fr[0, :n], fr[1, :n])]
+        assemble = BatchPayload(cols, host, counts, nnz, nseq, nbytes).frame      # the object the streaming loader assembles from
+        # a few frames per task: one call into the host library per chunk (compress_utils.pack_frames)
         step = max(1, n // 64) if pool is not None else max(n, 1)
         chunk = lambda lo: pack_frames(self.bc, [assemble(b) for b in range(lo, min(lo + step, n))], uniform=self.uniform)
         parts = list(pool.map(chunk, range(0, n, step))) if pool is not None else [chunk(lo) for lo in range(0, n, step)]
         return [blob for part in parts for blob in part]
-
-    def _collect_containers(self, ctx):
-        """The containers _device_containers built: the frames' places, then the containers in one copy."""
-        out, frame, _ = ctx["containers"]
-        try:
-            ctx["stream"].synchronize()
-            fr = frame.cpu().numpy()
-            status = ctx["buf"].status.cpu().numpy() if self.dbscan else None
-            orphans = ctx["buf"].intensity[2].cpu().numpy() if self.intensity_scale is not None else None
-        finally:
-            ctx["buf"].in_flight = False
-        self.check_status(status)
-        if orphans is not None:
-            self.check_orphans(orphans[: ctx["n"]])
-        n = ctx["n"]
-        if (fr[1, :n] < 0).any():
-            raise RuntimeError("rpcc_lz4: the containers of frames %s were not built" % np.flatnonzero(fr[1, :n] < 0).tolist())
-        h = out[: int((fr[0, :n] + fr[1, :n]).max()) if n else 0].cpu().numpy()
-        return [h[o: o + l].tobytes() for o, l in zip(fr[0, :n], fr[1, :n])]
 
     def discard(self, ctx):
         """Gives up a submit() whose results are not wanted (a caller that aborts a batch): waits for its stream -- the kernels may still
@@ -422,16 +385,8 @@ STREAM_TEXT = {_lib.STREAM_E_ENTROPY: "an entropy stream was refused by the devi
 def container_spans(blob, uniform=True):
     """The (offset, length) of every payload of one .rpcc container by unpack_bitstream's rules (compress_utils), in container order; None for
     a container they refuse: a prefix that is cut off or negative, or a payload longer than the bytes left."""
-    spans, off = [], 0
-    for _ in range(4 if uniform else 5):
-        if off + 4 > len(blob):
-            return None
-        (n,) = struct.unpack_from("i", blob, off)
-        if n < 0 or off + 4 + n > len(blob):
-            return None
-        spans.append((off + 4, n))
-        off += 4 + n
-    return spans
+    spans = list(payload_spans(blob, len(columns(uniform))))
+    return spans if len(spans) == len(columns(uniform)) else None
 
 
 class BatchDecompressor:
@@ -477,34 +432,40 @@ class BatchDecompressor:
         self.host_bc = BasicCompressor(method_name=self.method)   # the E_ENTROPY fallback: the host library's decoder
         self.work_bytes, self.decode_slots = device_decoder(self.method)   # the device decoder, whatever the flags say
         P, K = transformer.H * transformer.W, self.M + 2
-        self.ns = 4 if self.uniform else 5
-        # decoded bytes a stream can have, in container order (salience first when present): fixed by the geometry
-        self.caps = ([] if self.uniform else [K]) + [(P + 7) // 8, 2 * P, 16 * K, 2 * P]
+        # the geometry's columns (compress_utils.SCHEMA) and the decoded bytes a stream of each can have: fixed by the geometry; the trailer's alike
+        self.cols = columns(self.uniform)
+        self.ns = len(self.cols)
+        self.caps = [c.bound(P, K) for c in self.cols]
+        self.trailer_cap = columns(self.uniform, True)[-1].bound(P, K)
         self.chunk = max(1, min(self.CHUNK_FRAMES, self.CHUNK_BUDGET_BYTES // self._frame_bytes()))
-
-    def _work_caps(self, heads):
-        """Work slot bytes of the streams of one frame (8-byte multiples, 0 where the decoder takes none), from each stream's first bytes."""
-        return [self.work_bytes(h, c) for h, c in zip(heads, self.caps)]
 
     def _frame_bytes(self):
         """Device bytes a frame of a chunk takes at most (bzip2: every stream at level 9)."""
-        P = self.T.H * self.T.W
-        work = sum(self._work_caps([b"BZh9"] * self.ns))
+        P, t = self.T.H * self.T.W, self.trailer_cap
+        work = sum(self.work_bytes(b"BZh9", c) for c in self.caps)
         outs = P * (2 if ops.is_wide(self.M) else 1) + 4 * P + 12 * P
         ws = -(-_lib.lib().rpcc_decompress_workspace_bytes(self.CHUNK_FRAMES, P, self.M) // self.CHUNK_FRAMES)
-        inten = (2 * (8 + P) + 4 * P + self.work_bytes(b"BZh9", 8 + P)) if self.intensity else 0   # coded + decoded trailer, the f32 image, its work slot
+        inten = (2 * t + 4 * P + self.work_bytes(b"BZh9", t)) if self.intensity else 0   # coded + decoded trailer, the f32 image, its work slot
         return sum(self.caps) + 5 * 256 + work + outs + ws + inten
+
+    def _descriptors(self, m, addr, lens, dst_off, dst_cap, heads):
+        """The six descriptor rows decode_slots takes, [addr | lens | dst_off | dst_cap | work_off | work_cap], into m (host i64 [6, n]): the
+        work slots -- 8-byte multiples, 0 where the decoder takes none -- sized from each stream's first bytes and packed back to back.
+        -> the work buffer's bytes."""
+        m[0], m[1], m[2], m[3] = addr, lens, dst_off, dst_cap
+        m[5] = [self.work_bytes(h, c) for h, c in zip(heads, m[3].tolist())]
+        m[4], wtotal = entropy.packed_slots(m[5])
+        return wtotal
 
     def _chunk_device(self, blobs, out, data=None):
         """One chunk: parse, upload, entropy launch, decode call on the current stream.  out: the chunk's rows of (status, seg, rec, pc).
         data: (device u8 tensor, offsets) when the containers are on the device already (the tensor must stay alive until the stream has run)."""
         B, ns, dev = len(blobs), self.ns, self.device
         H, W, K = self.T.H, self.T.W, self.M + 2
-        P = H * W
         spans = [container_spans(b, self.uniform) for b in blobs]
         sound = [i for i, sp in enumerate(spans) if sp is not None]
         n = ns * len(sound)
-        # the padded arrays, one allocation: [salience | contour bits | idx | model | residuals], every part 256-aligned
+        # the padded arrays, one allocation: a part per column of self.cols, B rows of the column's bound, every part 256-aligned
         row = self.caps
         part = np.zeros(ns + 1, np.int64)
         part[1:] = np.cumsum([(B * r + 255) // 256 * 256 for r in row])
@@ -523,13 +484,9 @@ class BatchDecompressor:
                 body[o: o + a.size] = a
         sp = np.array([spans[i] for i in sound], np.int64).reshape(len(sound), ns, 2)
         fr = np.array(sound, np.int64)
-        meta_h[0 * n: 1 * n] = (base + offs[fr][:, None] + sp[:, :, 0]).reshape(-1)
-        meta_h[1 * n: 2 * n] = sp[:, :, 1].reshape(-1)
-        meta_h[2 * n: 3 * n] = (part[None, :ns] + fr[:, None] * np.array(row, np.int64)[None, :]).reshape(-1)
-        meta_h[3 * n: 4 * n] = np.tile(np.array(row, np.int64), len(sound))
-        wcap = np.array([self._work_caps([arrays[i][o: o + min(l, 4)] for o, l in spans[i]]) for i in sound], np.int64).reshape(-1)
-        meta_h[4 * n: 5 * n], wtotal = entropy.packed_slots(wcap)
-        meta_h[5 * n: 6 * n] = wcap
+        wtotal = self._descriptors(meta_h[: 6 * n].reshape(6, n), (base + offs[fr][:, None] + sp[:, :, 0]).reshape(-1), sp[:, :, 1].reshape(-1),
+                                   (part[None, :ns] + fr[:, None] * np.array(row, np.int64)[None, :]).reshape(-1), np.tile(np.array(row, np.int64), len(sound)),
+                                   [arrays[i][o: o + min(l, 4)] for i in sound for o, l in spans[i]])
         work = torch.empty(wtotal, dtype=torch.uint8, device=dev) if wtotal else None
         bad = np.array([i for i in range(B) if spans[i] is None], np.int64)
         meta_h[6 * n: 6 * n + len(sound)], meta_h[6 * n + len(sound): 6 * n + B] = fr, bad
@@ -546,12 +503,11 @@ class BatchDecompressor:
         elif sound:
             idx = meta[6 * n: 6 * n + len(sound)]
             plen[idx, 5 - ns:], pest[idx, 5 - ns:] = dst_len.view(-1, ns), est.view(-1, ns)
-        view = lambda c, dt, shape: dst[int(part[c]): int(part[c]) + B * row[c]].view(dt).view(shape)
-        c0 = ns - 4
-        sal = None if self.uniform else view(0, torch.uint8, (B, K))
-        ops.decompress_batch(view(c0, torch.uint8, (B, (P + 7) // 8)), view(c0 + 1, torch.uint16, (B, P)), view(c0 + 2, torch.float32, (B, K, 4)),
-                             view(c0 + 3, torch.int16, (B, P)), plen, pest, self.T.tm_dev, self.accuracy if self.uniform else self.level_acc,
-                             H, W, salience=sal, out=out[:4])
+        # the parts as [B, ...] arrays of their columns' dtypes; the last four in file order are decompress_batch's first four arguments
+        typed = [dst[int(part[i]): int(part[i]) + B * row[i]].view(getattr(torch, c.dtype.name)).view(B, -1) for i, c in enumerate(self.cols)]
+        bits, seq, model, q16 = typed[-4:]
+        ops.decompress_batch(bits, seq, model.view(B, K, 4), q16, plen, pest, self.T.tm_dev, self.accuracy if self.uniform else self.level_acc,
+                             H, W, salience=None if self.uniform else typed[0], out=out[:4])
         if len(bad):
             out[0][meta[6 * n + len(sound): 6 * n + B]] = _lib.STREAM_E_CONTAINER
         if self.per_frame_rows and not self.uniform:
@@ -570,8 +526,7 @@ class BatchDecompressor:
         """intensity=True: the chunk's trailers through one more decode_slots call into a [B, 8+P] array, then ops.intensity_decode on the
         label maps just decoded.  A frame without a (valid) trailer, or whose geometry was refused, keeps its earlier status or gets
         STREAM_E_INTENSITY, and a zero row."""
-        B, dev, P = len(blobs), self.device, self.T.H * self.T.W
-        row = 8 + P
+        B, dev, row = len(blobs), self.device, self.trailer_cap
         spans = [intensity_trailer_span(b, self.uniform) for b in blobs]
         have = [i for i, sp in enumerate(spans) if sp is not None]
         n = len(have)
@@ -582,10 +537,8 @@ class BatchDecompressor:
             sp = np.array([spans[i] for i in have], np.int64)
             meta_h = torch.empty((7, n), dtype=torch.int64, pin_memory=True)
             m = meta_h.numpy()
-            m[0], m[1], m[2], m[3] = base + offs[fr] + sp[:, 0], sp[:, 1] - sp[:, 0], fr * row, row
-            wcap = np.array([self.work_bytes(arrays[i][s: s + min(e - s, 4)], row) for i, (s, e) in zip(have, sp)], np.int64)
-            m[4], wtotal = entropy.packed_slots(wcap)
-            m[5], m[6] = wcap, fr
+            wtotal = self._descriptors(m, base + offs[fr] + sp[:, 0], sp[:, 1] - sp[:, 0], fr * row, row, [arrays[i][s: s + min(e - s, 4)] for i, (s, e) in zip(have, sp)])
+            m[6] = fr
             meta = meta_h.to(dev, non_blocking=True)
             work = torch.empty(wtotal, dtype=torch.uint8, device=dev) if wtotal else None
             dst_len, est = self.decode_slots([meta[k] for k in range(6)], pay.view(-1), work)

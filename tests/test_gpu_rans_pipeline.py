@@ -19,7 +19,6 @@ ACC = 0.02
 LACC = np.array([2 * ACC] * 4) + np.array((0, 0.02, 0.04, 0.06))
 GEOM = "VelodyneVLP16"
 M = 40
-WIDTHS = {"salience_level": 1, "contour_map": 1, "idx_sequence": 2, "plane_param": 4, "residual_quantized": 2}
 
 
 @pytest.fixture(scope="module")
@@ -50,6 +49,7 @@ def test_batch_containers_equal_the_per_frame_path(env, uniform):
     """The per-frame path is fed from the same batch's bzip2 containers (host-coded; tests/test_gpu_parity.py ties those to the per-frame
     compressor): their arrays through compress_point_cloud with BasicCompressor('rans') and pack_bitstream."""
     cu, T = env["cu"], env["T"]
+    WIDTHS = {c.name: c.dtype.itemsize for c in cu.SCHEMA}       # the element widths are the container schema's
     got = _containers(env, uniform, "rans")
     rans, bz = cu.BasicCompressor(method_name="rans"), cu.BasicCompressor(method_name="bzip2")
     for b, (g, w) in enumerate(zip(got, _containers(env, uniform, "bzip2"))):

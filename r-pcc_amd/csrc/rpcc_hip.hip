@@ -2816,6 +2816,8 @@ extern "C" int rpcc_assign_wide(const float *ri, const float *tm, const double *
 
 static inline int kpad(int M) { return ((M + 2) + 63) & ~63; }
 static inline int ntiles(int P) { return (P + TILE - 1) / TILE; }
+// count_scan_kernel's table in LDS: per tile a row of K 16-bit counts (a count is at most TILE), two to a word
+__host__ __device__ static inline int count_row_words(int K) { return (K + 1) >> 1; }
 struct WsLayout {
     int64_t *sums;
     int32_t *flags;
@@ -2896,6 +2898,9 @@ struct ScanArgs {
     float *model;
     int32_t *counts, *nnz;
 };
+// LDS_COUNTS: the tile x label counts are the 16-bit table that count_tiles_lds has left in the dynamic LDS (count_scan_kernel below), not
+// hist: the same three phases on the same numbers, no count held in registers, and hist is only written.  NT: the workgroup's threads.
+template <bool LDS_COUNTS = false, int NT = SCAN_THREADS>
 __device__ __forceinline__ void model_scan_body(const ScanArgs &A, const int b) {
     const float *__restrict__ ri = A.ri;
     const uint8_t *__restrict__ seg = A.seg;
@@ -2906,28 +2911,34 @@ __device__ __forceinline__ void model_scan_body(const ScanArgs &A, const int b) 
     uint32_t *__restrict__ hist = A.hist;
     float *__restrict__ model = A.model;
     int32_t *__restrict__ counts = A.counts, *__restrict__ nnz = A.nnz;
-    __shared__ uint32_t gtot[SCAN_THREADS];   // [group][KP2] counts of a label in a tile group
+    __shared__ uint32_t gtot[NT];   // [group][KP2] counts of a label in a tile group
     __shared__ uint32_t base[256];
     __shared__ uint32_t wsum[4];
     const int K = M + 2;
-    const int NG = SCAN_THREADS / KP2, k = threadIdx.x & (KP2 - 1), grp = threadIdx.x / KP2;
+    const int NG = NT / KP2, k = threadIdx.x & (KP2 - 1), grp = threadIdx.x / KP2;
     const int TG = (T + NG - 1) / NG, tbeg = grp * TG, tend = min(T, tbeg + TG);
     uint32_t *gh = hist + (int64_t)b * T * KP;
     const uint32_t kp4 = (uint32_t)KP * 4u, k4 = (uint32_t)k * 4u;
-    const bool held = TG <= SCAN_U;   // (workgroup-uniform)
+    const bool held = !LDS_COUNTS && TG <= SCAN_U;   // (workgroup-uniform)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const uint32_t row2 = (uint32_t)count_row_words(K) * 4u, k2 = (uint32_t)k * 2u;
+    auto count_at = [&](int t) -> uint32_t {   // the pixels of label k in tile t (t < T, k < K)
+        if constexpr (LDS_COUNTS) return (uint32_t)ld_at(reinterpret_cast<const uint16_t *>(smem_raw), (uint32_t)t * row2 + k2);
+        else return ld_at(gh, (uint32_t)t * kp4 + k4);
+    };
     uint32_t c[SCAN_U];
     uint32_t part = 0;
     if (k < K) {
         if (held) {
 #pragma unroll
-            for (int j = 0; j < SCAN_U; j++) c[j] = ld_at(gh, (uint32_t)min(tbeg + j, T - 1) * kp4 + k4);   // unconditional (clamped) loads
+            for (int j = 0; j < SCAN_U; j++) c[j] = count_at(min(tbeg + j, T - 1));   // unconditional (clamped) loads
 #pragma unroll
             for (int j = 0; j < SCAN_U; j++) { if (tbeg + j >= tend) c[j] = 0u; part += c[j]; }
         } else {
             for (int t0 = tbeg; t0 < tend; t0 += SCAN_U) {
                 uint32_t d[SCAN_U];
 #pragma unroll
-                for (int j = 0; j < SCAN_U; j++) d[j] = ld_at(gh, (uint32_t)min(t0 + j, T - 1) * kp4 + k4);
+                for (int j = 0; j < SCAN_U; j++) d[j] = count_at(min(t0 + j, T - 1));
 #pragma unroll
                 for (int j = 0; j < SCAN_U; j++) part += t0 + j < tend ? d[j] : 0u;
             }
@@ -2965,7 +2976,7 @@ __device__ __forceinline__ void model_scan_body(const ScanArgs &A, const int b) 
             for (int t0 = tbeg; t0 < tend; t0 += SCAN_U) {
                 uint32_t d[SCAN_U];
 #pragma unroll
-                for (int j = 0; j < SCAN_U; j++) d[j] = ld_at(gh, (uint32_t)min(t0 + j, T - 1) * kp4 + k4);
+                for (int j = 0; j < SCAN_U; j++) d[j] = count_at(min(t0 + j, T - 1));
 #pragma unroll
                 for (int j = 0; j < SCAN_U; j++) {
                     if (t0 + j < tend) { st_at(gh, (uint32_t)(t0 + j) * kp4 + k4, run); run += d[j]; }
@@ -2984,6 +2995,82 @@ __global__ __launch_bounds__(SCAN_THREADS) void model_scan_multi_kernel(const Mu
     const ScanArgs &A = multi_locate(m, b, t);
     model_scan_body(A, b);
 }
+#include "label_bytes.h"
+// The histogram as the scan's head (byte labels, counts only): the frame's one workgroup counts its own tiles into LDS and scans them there, so
+// the tile x label table never goes through memory as counts, nothing is published between workgroups, and the T x B short workgroups of
+// model_hist_kernel are not launched.  Table: uint16 [T][2 * count_row_words(K)] in the dynamic LDS, cleared here; a tile belongs to ONE
+// wavefront (tile t: wavefront t % NW), whose lane owns 16 consecutive pixels: one 16-byte load per tile where the frame's labels are
+// 16-byte aligned and the tile is whole, COUNT_U tiles' loads issued before the first is used; byte loads (clamped) otherwise.
+// A lane counts its own 16 pixels, label by label: the label of its first pending pixel, the pixels that carry it found in the four packed
+// words at once (rpcc_label_count_word, label_bytes.h), one LDS add per distinct label of the lane -- lidar labels come in runs, so a lane
+// usually holds one or two -- until nothing is pending: no cap, 16 different labels take 16 steps.  (Aggregating over the WAVEFRONT first, as
+// the quantiser and the old histogram do with round_label, costs a round of 16 compare masks per distinct label of the 1024-pixel tile, and a
+// tile of the headline holds tens of them: 194 us alone against 35 + 12 for the two launches, profiles/HISTORY.md.)  A label >= K (no
+// caller's map holds one) is dropped, not counted into a neighbour's row.
+// 512 threads (eight wavefronts, 16 tiles each for 64 x 2048): 26.6 us alone against 35.0 with 256, and -- unlike the bare scan, whose 256
+// threads won in flight -- also the faster step with three batches in flight, in both sessions that took turns with the parent and the
+// 256-thread build (profiles/HISTORY.md "Counting in the scan kernel").  76 VGPRs, no scratch; the multi form takes 88.
+#define COUNT_U 8
+#define COUNT_SCAN_THREADS 512
+template <bool WHOLE>
+__device__ __forceinline__ void count_tile_row(const uint32_t w0, const uint32_t w1, const uint32_t w2, const uint32_t w3, const int nval, const int K,
+                                               uint32_t *row) {
+    // (scalars, not arrays: the choice of the first pending word below must stay a chain of selects, not an indexed read of a spilled array)
+    uint32_t p0 = rpcc_label_marks(WHOLE ? 4 : nval), p1 = rpcc_label_marks(WHOLE ? 4 : nval - 4), p2 = rpcc_label_marks(WHOLE ? 4 : nval - 8),
+             p3 = rpcc_label_marks(WHOLE ? 4 : nval - 12);   // 0x80 per pending byte
+    while ((p0 | p1 | p2 | p3) != 0u) {   // (lanes leave as they finish)
+        const uint32_t px = p0 ? p0 : p1 ? p1 : p2 ? p2 : p3, wx = p0 ? w0 : p1 ? w1 : p2 ? w2 : w3;
+        const uint32_t cur = (wx >> (__ffs((int)px) - 8)) & 255u;   // (mark of byte i: bit 8 i + 7)
+        const uint32_t n = rpcc_label_count_word(w0, cur, &p0) + rpcc_label_count_word(w1, cur, &p1) + rpcc_label_count_word(w2, cur, &p2) +
+                           rpcc_label_count_word(w3, cur, &p3);
+        // (two counts to a word, each at most TILE: the add never carries into the other half)
+        if ((int)cur < K) atomicAdd(&row[cur >> 1], n << (16u * (cur & 1u)));
+    }
+}
+template <int NT>
+__device__ __forceinline__ void count_tiles_lds(const uint8_t *__restrict__ seg_b, const int P, const int T, const int K) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem_raw);
+    const int RW = count_row_words(K), lane = threadIdx.x & 63, wave = threadIdx.x >> 6, NW = NT / 64;
+    for (int i = threadIdx.x; i < (T * RW + 3) >> 2; i += NT) reinterpret_cast<uint4 *>(tab)[i] = make_uint4(0u, 0u, 0u, 0u);   // (count_scan_lds_bytes)
+    __syncthreads();
+    const int Tw = ((uintptr_t)seg_b & 15u) == 0 ? P / TILE : 0;   // the tiles that take the 16-byte loads (workgroup-uniform)
+    for (int t0 = wave; t0 < Tw; t0 += NW * COUNT_U) {
+        uint4 x[COUNT_U];
+#pragma unroll
+        for (int j = 0; j < COUNT_U; j++)   // unconditional (clamped) loads
+            x[j] = ld_at(reinterpret_cast<const uint4 *>(seg_b), (uint32_t)min(t0 + NW * j, Tw - 1) * (uint32_t)TILE + 16u * (uint32_t)lane);
+#pragma unroll
+        for (int j = 0; j < COUNT_U; j++) {
+            const int t = t0 + NW * j;
+            if (t < Tw) count_tile_row<true>(x[j].x, x[j].y, x[j].z, x[j].w, 16, K, tab + t * RW);
+        }
+    }
+    for (int t = Tw + wave; t < T; t += NW) {
+        const int p0 = t * TILE + 16 * lane, nval = min(max(P - p0, 0), 16);
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int e = 0; e < 16; e++) w[e >> 2] |= (uint32_t)ld_at(seg_b, (uint32_t)min(p0 + e, P - 1)) << (8 * (e & 3));
+        count_tile_row<false>(w[0], w[1], w[2], w[3], nval, K, tab + t * RW);
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(COUNT_SCAN_THREADS) void count_scan_kernel(const ScanArgs A) {
+    count_tiles_lds<COUNT_SCAN_THREADS>(A.seg + (int64_t)blockIdx.x * A.P, A.P, A.T, A.M + 2);
+    model_scan_body<true, COUNT_SCAN_THREADS>(A, blockIdx.x);
+}
+// (rpcc_compress_batch_mixed, as model_scan_multi_kernel: the launch's LDS is that of the group with the largest table)
+__global__ __launch_bounds__(COUNT_SCAN_THREADS) void count_scan_multi_kernel(const MultiArgs<ScanArgs> m) {
+    int b, t;
+    const ScanArgs &A = multi_locate(m, b, t);
+    count_tiles_lds<COUNT_SCAN_THREADS>(A.seg + (int64_t)b * A.P, A.P, A.T, A.M + 2);
+    model_scan_body<true, COUNT_SCAN_THREADS>(A, b);
+}
+// The fused kernel's LDS and the budget under which launch_hist_scan / mixed_labels take it: 96 KB of the CU's 160 KB hold 64 x 2048 (128
+// tiles) and 80 x 2000 (157 tiles) at up to 254 clusters (512 bytes a tile), and leave the kernel's static 3 KB and a neighbour some room.
+static inline size_t count_scan_lds_budget() { return (size_t)96 * 1024; }
+static inline size_t count_scan_lds_bytes(int P, int M) { return round_up((size_t)ntiles(P) * count_row_words(M + 2) * 4, 16); }
+static inline bool count_scan_fits(int P, int M) { return count_scan_lds_bytes(P, M) <= count_scan_lds_budget(); }
 // The scan on uint16 labels (up to RPCC_MAX_CLUSTERS_MID clusters): a thread per label (K <= 1024) -- label totals, their exclusive prefix
 // without label 1, the tiles' offsets, counts, nnz and the point model's rows (cpp_modules.cpp:471-518).
 #define SCANW_THREADS 1024
@@ -3167,13 +3254,27 @@ static inline int scan_kp2(int M) { int v = 1; while (v < M + 2) v <<= 1; return
 // -- with `model` -- the point model's rows.  The sums / flags block must be zero (memset or BatchInit) before the sums are added: by the
 // histogram here, or -- summed = true -- by the assignment that wrote seg (launch_assign with lay.sums / lay.flags); the histogram is then
 // the count-only form, and ri serves the scan's sequential fallback alone (point_model_row).  counted = true: no histogram launch at all.
+// The sums are the point model's: without `model` the histogram only counts, whatever ri is.  Byte labels that are to be counted and not
+// summed take ONE launch, count_scan_kernel, when the frame's table fits count_scan_lds_budget(); everything else -- uint16 labels, the
+// summing form (rpcc_point_model), counted = true, larger images -- keeps the two launches.
 template <class L>
 static int launch_hist_scan(const float *ri, const L *seg, const double *ground, int B, int P, int M, const WsLayout &lay, float *model,
                             int32_t *counts, int32_t *nnz, hipStream_t st, bool summed = false, bool counted = false) {
     const int KP = kpad(M), T = ntiles(P);
-    const bool hist_sums = ri != nullptr && !summed;
+    const bool hist_sums = ri != nullptr && model != nullptr && !summed;   // (the sums serve the model's rows alone)
     const size_t sh = hist_lds_bytes(KP, hist_sums);
     const bool vec = hist_vec(P, seg, hist_sums ? ri : nullptr);
+    // Byte labels to be counted and nothing to be summed: one launch, the counts never leave LDS (count_scan_kernel) -- if the table fits.
+    if constexpr (sizeof(L) == 1) {
+        if (!counted && !hist_sums && count_scan_fits(P, M)) {
+            const size_t ch = count_scan_lds_bytes(P, M);
+            const ScanArgs sa = {ri, seg, ground, P, M, KP, T, scan_kp2(M), lay.sums, lay.flags, lay.hist, model, counts, nnz};
+            HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&count_scan_kernel), (int)ch));
+            count_scan_kernel<<<B, COUNT_SCAN_THREADS, ch, st>>>(sa);
+            LAUNCH_CHECK();
+            return RPCC_OK;
+        }
+    }
     // (The scan as the tail of the histogram kernel -- the frame's last workgroup to finish runs it -- was measured in round 4: a workgroup must
     // release its rows device-wide before it draws its ticket, and an agent-scope fence writes the XCD's L2 back: 62 us -> 2.9 ms.)
     if (counted) {   // lay.hist holds the tile counts already, and lay.sums what `summed` says (labels_in_kernel wrote both with seg)
@@ -4006,10 +4107,19 @@ static int mixed_labels(const BatchPlan *pl, int G, hipStream_t st) {
         const PlaneLayout pa = plane_layout(p.extra, p.Bs, p.P);
         if (!point) multi_add(mo, OrderGroup{io->seg, p.L.hist, p.P, T, pa.order, io->ri, io->tm, pa.pts4}, p.Bs, T);
     }
-    model_hist_multi_kernel<<<mh.first[mh.n], 256, hist_lds_bytes(KP, false), st>>>(mh, KP);
-    LAUNCH_CHECK();
-    model_scan_multi_kernel<<<ms.first[ms.n], SCAN_THREADS, 0, st>>>(ms);
-    LAUNCH_CHECK();
+    size_t ch = 0;   // the fused count + scan launch when every group's table fits (launch_hist_scan's rule)
+    bool fits = true;
+    for (int i = 0; i < G; i++) { fits = fits && count_scan_fits(pl[i].P, M); ch = std::max(ch, count_scan_lds_bytes(pl[i].P, M)); }
+    if (fits) {
+        HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&count_scan_multi_kernel), (int)ch));
+        count_scan_multi_kernel<<<ms.first[ms.n], COUNT_SCAN_THREADS, ch, st>>>(ms);
+        LAUNCH_CHECK();
+    } else {
+        model_hist_multi_kernel<<<mh.first[mh.n], 256, hist_lds_bytes(KP, false), st>>>(mh, KP);
+        LAUNCH_CHECK();
+        model_scan_multi_kernel<<<ms.first[ms.n], SCAN_THREADS, 0, st>>>(ms);
+        LAUNCH_CHECK();
+    }
     if (mo.n > 0) {
         label_order_multi_kernel<<<mo.first[mo.n], 256, label_order_lds_bytes(KP), st>>>(mo, M, KP);
         LAUNCH_CHECK();

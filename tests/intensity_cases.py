@@ -124,9 +124,114 @@ def example():
     return [_batch(g, [rows], 100)]
 
 
+# ---- past the grid caps ------------------------------------------------------------------------------------------------------------------
+PAST_GEOM = dict(H=16, W=512, hfov_deg=360, vmax_deg=2.0, vmin_deg=-24.9)
+PAST_N = 6001                                     # rows of a frame: odd, so frame ends fall inside wavefronts and chunk boundaries move from cycle to cycle
+PAST_HEAD = 700                                   # leading rows of a seam frame that are all aimed at the seam
+PAST_DEPTHS = (2.5, 4.0, 6.0, 9.0, 13.0, 19.0, 27.0, 40.0)
+PAST_DEPTH_P = (0.01, 0.04, 0.10, 0.17, 0.17, 0.17, 0.17, 0.17)     # the nearest depth is rare: a pixel's owner lies anywhere in its frame
+PAST_ZERO_AT, PAST_RUN = 320, 300                 # the constructed zero of the `zero` frame and the run of its own pixel's rows behind it
+
+
+def _past_w(n):
+    """n intensities that all differ, q = (97 i) mod 256 at scale 255: rows 1 .. 255 places apart never share a byte."""
+    i = np.arange(n)
+    return (((i * 97) % 256 + 0.3 * i / max(n, 1)) / 255).astype(np.float32)
+
+
+def _past_pool(g, rng):
+    """Seam directions: f32 [H, depths, 4 aims, 3], every one within 0.4 cell of column 0 or of column W (which wraps) and a quarter cell of its
+    row.  Rows drawn from the pool repeat exactly, so equal depths in one pixel are bit-equal and only the input position tells them apart."""
+    H, D = g.H, len(PAST_DEPTHS)
+    row = np.repeat(np.arange(H), D * 4) + rng.uniform(-0.25, 0.25, H * D * 4)
+    col = rng.choice([0.0, float(g.W)], H * D * 4) + rng.uniform(-0.4, 0.4, H * D * 4)
+    dep = np.tile(np.repeat(np.asarray(PAST_DEPTHS), 4), H)
+    return rays(g, row, col, dep, 0.0)[:, :3].reshape(H, D, 4, 3)
+
+
+def _past_seam(pool, rng, n, rows=None):
+    rows = rng.integers(0, pool.shape[0], n) if rows is None else np.asarray(rows)
+    return pool[rows, rng.choice(len(PAST_DEPTHS), n, p=PAST_DEPTH_P), rng.integers(0, 4, n)]
+
+
+def _past_plain(g, rng, n):
+    """Rows aimed within a quarter cell of a pixel centre in columns 2 .. W - 2 at 1 .. 60 m: the screened fast path is certain of every one."""
+    row = rng.integers(0, g.H, n) + rng.uniform(-0.25, 0.25, n)
+    col = rng.integers(2, g.W - 1, n) + rng.uniform(-0.25, 0.25, n)
+    return rays(g, row, col, rng.uniform(1.0, 60.0, n), 0.0)[:, :3]
+
+
+def _past_seam_frame(g, pool, rng):
+    """-> (rows f32 [PAST_N,4], aimed_fast bool [PAST_N]).  The first PAST_HEAD rows all at the seam, every image row among them; behind them
+    three rows in four at the seam, at random, and the fourth an ordinary one."""
+    n = PAST_N
+    seam = np.ones(n, bool)
+    seam[PAST_HEAD:] = rng.random(n - PAST_HEAD) < 0.75
+    rows = np.empty((n, 4), np.float32)
+    head_rows = rng.permutation(np.arange(PAST_HEAD) % g.H)
+    rows[:PAST_HEAD, :3] = _past_seam(pool, rng, PAST_HEAD, head_rows)
+    rest = np.flatnonzero(seam[PAST_HEAD:]) + PAST_HEAD
+    rows[rest, :3] = _past_seam(pool, rng, rest.shape[0])
+    rows[~seam, :3] = _past_plain(g, rng, int((~seam).sum()))
+    rows[:, 3] = _past_w(n)
+    return rows, ~seam
+
+
+def past_zero_pixel(g):
+    """The pixel (0, 0, 0) lands in: column 0 of the row elevation 0 maps to."""
+    import intensity_ref as R
+    return int(R.pixels(np.zeros((1, 3), np.float32), g)[1][0])
+
+
+def _past_zero_frame(g, pool, rng):
+    """A seam frame with (0, 0, 0, w) rows sprinkled in.  The constructed one stands at PAST_ZERO_AT with PAST_RUN seam rows of its own pixel
+    behind it; rows of the nearest depth of that pixel stand before it (10 rows from 100 on) and inside the run, so the pixel's owner is
+    another row with and without the rule about zeros.  The other zeros all come later, and none behind row 5000."""
+    rows, fast = _past_seam_frame(g, pool, rng)
+    r0 = past_zero_pixel(g) // g.W
+    own = lambda n: _past_seam(pool, rng, n, np.full(n, r0))
+    nearest = pool[r0, 0, 1]
+    rows[PAST_ZERO_AT + 1: PAST_ZERO_AT + 1 + PAST_RUN, :3] = own(PAST_RUN)
+    rows[100:110, :3] = nearest
+    rows[PAST_ZERO_AT + 40: PAST_ZERO_AT + 44, :3] = nearest
+    rows[5500:5510, :3] = nearest
+    fast[5500:5510] = False
+    zeros_at = np.concatenate([[PAST_ZERO_AT], rng.choice(np.arange(PAST_HEAD, 5000), 12, replace=False)])
+    rows[zeros_at, :3] = 0
+    fast[zeros_at] = False
+    return rows, fast
+
+
+def past_the_grid_frames(min_rows, min_pixels):
+    """-> the batch: the four distinct frames (seam, plain, zero, empty) in a cycle until the batch holds at least min_rows rows and more than
+    min_pixels pixels.  Besides g / frames / scale: distinct (the four frames; batch position b holds distinct[which[b]], the same array),
+    which, aimed_fast (per distinct frame: the rows the fast path is certain of by construction)."""
+    g, rng = orc.LidarGeom(**PAST_GEOM), np.random.default_rng(9)
+    pool = _past_pool(g, rng)
+    seam, seam_fast = _past_seam_frame(g, pool, rng)
+    plain = np.concatenate([_past_plain(g, rng, PAST_N), _past_w(PAST_N)[:, None]], 1).astype(np.float32)
+    zero, zero_fast = _past_zero_frame(g, pool, rng)
+    distinct = [np.ascontiguousarray(f, dtype=np.float32) for f in (seam, plain, zero, np.zeros((0, 4), np.float32))]
+    fast = [seam_fast, np.ones(PAST_N, bool), zero_fast, np.zeros(0, bool)]
+    B, rows = 0, 0
+    while rows < min_rows or B * g.H * g.W <= min_pixels:
+        rows += distinct[B % 4].shape[0]
+        B += 1
+    which = np.arange(B) % 4
+    return dict(g=g, frames=[distinct[k] for k in which], scale=255.0, distinct=distinct, which=which, aimed_fast=fast)
+
+
+def past_the_grid():
+    """B = 247 frames of 6001 / 6001 / 6001 / 0 rows at 16 x 512: 1 116 186 rows and 2 023 424 pixels, the smallest batch of this cycle that takes
+    intensity_fill_kernel and intensity_owner_kernel<false> through a second trip and the fix-up pass through a third, 65 536 rows past
+    the cap of the owner pass (sized from tests/grid_caps.py; tests/test_intensity_ref.py asserts what the batch reaches)."""
+    import grid_caps as GC
+    return [past_the_grid_frames(GC.INT_OWNER_CAP * GC.INT_THREADS + 65536, GC.INT_FILL_CAP * GC.INT_FILL_THREADS)]
+
+
 CASES = dict(tiny=tiny, ties=ties, zeros=zeros, nonfinite=nonfinite, rounding=rounding, wrap_clamp=wrap_clamp, frames=frames, odd_P=odd_P,
-             example=example)
-SMALL = tuple(n for n in CASES if n not in ("odd_P", "example"))     # the cases whose reference takes milliseconds
+             example=example, past_the_grid=past_the_grid)
+SMALL = tuple(n for n in CASES if n not in ("odd_P", "example", "past_the_grid"))     # the cases whose reference takes milliseconds
 
 
 def offsets(frames_):

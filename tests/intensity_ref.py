@@ -100,6 +100,19 @@ def encode_frame(rows, g, scale):
     return dict(ri=ri, own=own, d=d, pix=pix, payload=payload, image=image, q=q)
 
 
+def encode_frames(frames, g, scale):
+    """encode_frame of every frame of a batch -> a list of its dicts, computed once per distinct array (a batch that repeats a frame holds
+    the same array again: the specification is per frame, so the same dict stands at every one of its places)."""
+    memo = {}
+    out = []
+    for f in frames:
+        key = (f.__array_interface__["data"][0], f.shape, f.strides)
+        if key not in memo:
+            memo[key] = encode_frame(f, g, scale)
+        out.append(memo[key])
+    return out
+
+
 def parse_payload(data, n):
     """-> (scale f32, q uint8 [n]); ValueError for each of the refusals."""
     data = bytes(data)

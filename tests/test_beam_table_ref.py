@@ -136,6 +136,78 @@ def test_transform_map_from_the_table():
     assert hashlib.sha256(R.transform_map(va, HFOV, 64, 2000).tobytes()).digest() == g["transform_map_sha256"].tobytes()
 
 
+def test_past_the_grid_reaches_every_second_trip_and_the_carried_queue():
+    """The batch of BT.past_the_grid(), by the reference and the launch rules alone (tests/grid_caps.py): every loop of the three kernels
+    makes a second trip, and the LDS queue of beams_pix_kernel goes through a drain of two turns, a drain that only the carried queue
+    causes, and a non-empty tail behind the loop.  A point counts as queued only where the fast path refuses it by rule (column 0, depth 0
+    or not finite, an exact elevation tie) and as certainly fast only where it was aimed so (a quarter cell, a fifth of the way to the
+    midpoint, 1 .. 60 m)."""
+    import grid_caps as GC
+    c = BT.past_the_grid()
+    va, H, W = c["va"], c["H"], c["W"]
+    B, P = len(c["frames"]), H * W
+    total = sum(f.shape[0] for f in c["frames"])
+    assert [f.shape[0] for f in c["distinct"]] == [8191, 8191, 8191, 0] and all(c["frames"][b] is c["distinct"][b % 4] for b in range(B))
+    assert total >= GC.BEAMS_PIX_CAP * GC.BEAMS_CHUNK + 131072 and total > GC.BEAMS_WRITE_CAP * GC.BEAMS_WRITE_THREADS
+    assert GC.trips(total, GC.BEAMS_CHUNK, GC.BEAMS_PIX_CAP) >= 2 and GC.trips(total, GC.BEAMS_WRITE_THREADS, GC.BEAMS_WRITE_CAP) >= 2
+    assert GC.fill_trips(B * P, GC.BEAMS_FILL_THREADS, GC.BEAMS_FILL_CAP) >= 2
+    assert total < 2 ** 31 and total * 12 < 40e6                                # (the kernels' own limit; the data stays below 40 MB)
+    mid32 = (np.sort(va)[:-1] * 0.5 + np.sort(va)[1:] * 0.5).astype(np.float32)
+    queued, ties = [], 0
+    for f, fast in zip(c["distinct"], c["aimed_fast"]):
+        keep, row, col, depth = R.pixels(f, va, HFOV, W)
+        el = R.atan2f(f[:, 2], np.sqrt(f[:, 0] ** 2 + f[:, 1] ** 2))
+        tie = np.isin(el, mid32)
+        q = ~keep | (col == 0) | (depth == 0) | tie
+        assert not (q & fast).any() and fast.shape == q.shape
+        ties += int(tie.sum())
+        queued.append(q)
+    assert ties >= 550 and queued[1][: BT.PAST_HEAD].all() and not queued[2].any()
+    # ties in ordinary columns: most are the last point of their pixel, so a queue that loses one changes the image (the points at the seam
+    # share 16 pixels per frame: losing one of those shows only if it is the frame's last in its pixel)
+    seam = c["distinct"][1]
+    keep, row, col, depth = R.pixels(seam, va, HFOV, W)
+    pix = row * W + col
+    last = np.zeros(seam.shape[0], bool)
+    last[np.unique(pix[::-1], return_index=True)[1]] = True
+    last = last[::-1]
+    el = R.atan2f(seam[:, 2], np.sqrt(seam[:, 0] ** 2 + seam[:, 1] ** 2))
+    shown = np.isin(el, mid32) & (col != 0) & last
+    assert shown.sum() >= 300 and shown[: BT.PAST_HEAD].sum() >= 1, (int(shown[: BT.PAST_HEAD].sum()), int(shown.sum()))   # (of at most W - 3: one row)
+    # the tie goes to the lower row, and the zero that ends the zero-last frame leaves its pixel empty behind real points
+    k, r, _, _ = R.pixels(c["tie"][None], va, HFOV, W)
+    d = np.abs(va - float(R.atan2f(c["tie"][2:3], np.sqrt(c["tie"][0:1] ** 2 + c["tie"][1:2] ** 2))[0]))
+    assert (d == d.min()).sum() == 2 and d.min() == BT.PAST_TIE_HALF and r[0] == np.flatnonzero(d == d.min())[0]
+    zl = c["distinct"][0]
+    keep, row, col, depth = R.pixels(zl, va, HFOV, W)
+    same = (row == row[-1]) & (col == col[-1])
+    assert depth[-1] == 0 and col[-1] == 0 and same.sum() == BT.PAST_RUN + 1 and R.project(zl, va, HFOV, H, W)[row[-1], col[-1]] == 0
+    assert R.project(zl[:-1], va, HFOV, H, W)[row[-1], col[-1]] == depth[-2] > 0
+    which = c["which"]
+    q_all = np.concatenate([queued[k] for k in which])
+    maybe_all = np.concatenate([~c["aimed_fast"][k] for k in which])
+    facts = GC.queue_facts(q_all, maybe_all, total, GC.BEAMS_CHUNK, GC.BEAMS_PIX_CAP, GC.BEAMS_THREADS)
+    print("beams past the grid: B %d, total %d, grid %d, trips %d; chunks of a drain or more %d (up to %d turns), carried %d, tails %d"
+          % (B, total, facts["grid"], facts["trips"], facts["full"].size, facts["full_n"], facts["carried"].size, facts["tail"].size))
+    assert facts["grid"] == GC.BEAMS_PIX_CAP and facts["trips"] >= 2
+    assert facts["full_n"] >= 2                               # a chunk of 512 or more: two turns of the `while`
+    assert facts["carried"].size >= 1                         # chunks k and k + cap, each below a drain, together one
+    assert facts["tail"].size >= 1                            # a queue that is not empty behind the last trip
+    first, end = GC.pix_rows(total, int(facts["carried"][0]), 1)
+    assert GC.BEAMS_PIX_CAP * GC.BEAMS_CHUNK <= first < end <= total
+    # a drain of one turn per chunk (the `while` as an `if`) would lose points whose loss the image shows: in both trips
+    lost = GC.single_turn_losses(q_all, total, GC.BEAMS_CHUNK, GC.BEAMS_PIX_CAP, GC.BEAMS_THREADS)
+    offs = np.concatenate([[0], np.cumsum([f.shape[0] for f in c["frames"]])])
+    want = [R.project(f, va, HFOV, H, W) for f in c["distinct"]]
+    changed = {}
+    for b in (1, 5, int(np.flatnonzero(which == 1)[-1])):           # seam frames: the first two, and the last one (its points lie past the cap)
+        assert which[b] == 1
+        gone = lost[offs[b]: offs[b + 1]]
+        changed[b] = int((R.project(c["frames"][b][~gone], va, HFOV, H, W).view(np.uint32) != want[1].view(np.uint32)).sum())
+    print("a single turn per chunk would lose %d points; pixels that change in frames %s" % (int(lost.sum()), changed))
+    assert lost.sum() > 1000 and all(v >= 8 for v in changed.values()) and offs[max(changed)] >= GC.BEAMS_PIX_CAP * GC.BEAMS_CHUNK
+
+
 @pytest.mark.parametrize("W", (8, 64))
 @pytest.mark.parametrize("H", (2, 5))
 def test_constructed_sets_reach_what_they_aim_at(H, W):

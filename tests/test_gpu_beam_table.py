@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 import beam_table_ref as R
-from beam_table_cases import HFOV, constructed as _constructed, tables as _tables
+import grid_caps as GC
+from beam_table_cases import HFOV, constructed as _constructed, past_the_grid as _past_the_grid, tables as _tables
 from buffer_arena import Arena, filled
 
 pytestmark = pytest.mark.gpu
@@ -176,6 +177,63 @@ def test_scratch_of_exact_size_with_any_contents(env):
         run(0)
         run(1)        # ... on what the call before left there, under another B and point count
         run(0)
+
+
+# ------------------------------------------------------------------------------------------------
+# past the grid caps: two trips of every loop, the LDS queue carried from one to the next (tests/grid_caps.py, BT.past_the_grid;
+# tests/test_beam_table_ref.py asserts on the CPU what the batch reaches)
+# ------------------------------------------------------------------------------------------------
+def _past(env):
+    """The batch on the device (packed points and stored rows), and the reference image of every frame: one R.project per distinct frame."""
+    if "past" not in env["cache"]:
+        ops = env["ops"]
+        c = _past_the_grid()
+        per = np.stack([R.project(f, c["va"], HFOV, c["H"], c["W"]) for f in c["distinct"]])
+        pts = np.concatenate(c["frames"])
+        rows = np.concatenate([pts, np.full((pts.shape[0], 1), 0.5, np.float32)], 1)
+        env["cache"]["past"] = dict(c, want=per[c["which"]], pts=_to(env, pts), rows=_to(env, rows), offs=_to(env, _offsets(c["frames"])),
+                                    geom=ops.make_geom(c["H"], c["W"], HFOV, 0.0, 0.0), beams=ops.beam_index(c["va"], env["dev"]), total=pts.shape[0])
+    return env["cache"]["past"]
+
+
+def _assert_frames(got, p, tag):
+    bad = np.flatnonzero((got.view(np.uint32) != p["want"].view(np.uint32)).reshape(got.shape[0], -1).any(1))
+    assert got.shape == p["want"].shape and bad.size == 0, (tag, "frames", bad[:8].tolist(), "of kinds", p["which"][bad[:8]].tolist())
+
+
+@pytest.mark.parametrize("rows16", (False, True))
+def test_past_the_grid_equals_the_reference(env, rows16):
+    ops = env["ops"]
+    p = _past(env)
+    assert p["total"] > GC.BEAMS_PIX_CAP * GC.BEAMS_CHUNK and p["total"] > GC.BEAMS_WRITE_CAP * GC.BEAMS_WRITE_THREADS
+    assert p["want"].size > GC.BEAMS_FILL_CAP * GC.BEAMS_FILL_THREADS
+    for tag in ("first", "again"):
+        _assert_frames(ops.project(p["rows" if rows16 else "pts"], p["offs"], p["geom"], beams=p["beams"]).cpu().numpy(), p, (rows16, tag))
+    zl, r0 = np.flatnonzero(p["which"] == 0), int(np.argmin(np.abs(p["va"])))
+    assert not p["want"][zl, r0, 0].any() and p["want"][zl].any(axis=(1, 2)).all()     # (the zero that ends those frames leaves its pixel empty)
+    if not rows16:
+        sure, bad, slow = ops.project_beams_check(p["pts"], p["geom"], p["beams"])
+        by_rule = int(sum((~p["aimed_fast"][k]).sum() for k in p["which"]))
+        print("past the grid: %d points, %d certain, %d disagree, %d exact (%d aimed at the exact sequence)" % (p["total"], sure, bad, slow, by_rule))
+        assert bad == 0 and sure + slow == p["total"] and slow >= by_rule
+
+
+@pytest.mark.parametrize("pattern", ("ones", "alt(0,1)"))
+def test_past_the_grid_scratch_of_exact_size(env, pattern):
+    """... into a scratch of exactly the size asked for, filled with 0xFF (every remembered pixel reads as `skipped`, every maximum as -1) or
+    with small positive words (every remembered pixel a pixel of the image): neither the fill kernel's second trip nor a point the queue
+    lost may leave such a word in place."""
+    ops, torch = env["ops"], env["torch"]
+    p = _past(env)
+    B, H, W = p["want"].shape
+    need = int(env["lib"].lib().rpcc_project_beams_scratch_bytes(p["total"], B, H * W))
+    arena = Arena(need, env["dev"])
+    for rows16 in (False, True):
+        arena.fill(pattern)
+        out = filled((B, H, W), torch.float32, env["dev"], POISON)
+        ri = ops.project(p["rows" if rows16 else "pts"], p["offs"], p["geom"], ri=out, scratch=arena.view, beams=p["beams"])
+        _assert_frames(ri.cpu().numpy(), p, (pattern, rows16))
+        assert arena.check_guards() is None
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """-m gpu: the intensity kernels against tests/intensity_ref.py on every case of tests/intensity_cases.py (payload bytes, nbytes, image,
-orphans == 0, the way back with uint8 and uint16 label maps), the four refusals, the caller-buffer contract, and the channel end to end
+orphans == 0, the way back with uint8 and uint16 label maps; `past_the_grid` takes every grid-stride loop past its cap, tests/grid_caps.py),
+the four refusals, the caller-buffer contract, and the channel end to end
 at 16 x 1800 through the per-frame path, BatchCompressor / BatchDecompressor with every back-end, the radius filter, DBSCAN, uint16 labels,
 the streaming loader and the tools."""
 import os
@@ -15,6 +16,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import buffer_arena as BA  # noqa: E402
+import gzip_compare as GZ  # noqa: E402
 import intensity_cases as IC  # noqa: E402
 import intensity_ref as R  # noqa: E402
 
@@ -24,7 +26,7 @@ _REF = {}
 def ref(name):
     """The case's batches with the reference's results per frame, computed once and shared."""
     if name not in _REF:
-        _REF[name] = [dict(b, ref=[R.encode_frame(f, b["g"], b["scale"]) for f in b["frames"]]) for b in IC.CASES[name]()]
+        _REF[name] = [dict(b, ref=R.encode_frames(b["frames"], b["g"], b["scale"])) for b in IC.CASES[name]()]     # (once per distinct frame)
     return _REF[name]
 
 
@@ -70,6 +72,7 @@ def test_encode_and_decode_equal_the_reference(env, name):
         assert payload.shape == (B, 8 + P) and image.shape == (B, g.H, g.W)
         assert orphans.cpu().tolist() == [0] * B and o2.cpu().tolist() == [0] * B
         ph, nh, ih, oh, rh = payload.cpu().numpy(), nbytes.cpu().numpy(), image.cpu().numpy(), own.cpu().numpy(), ri.cpu().numpy()
+        p2h = p2.cpu().numpy()
         assert np.array_equal(nh, n2.cpu().numpy()) and np.array_equal(ih, im2.cpu().numpy())
         decs = {}
         for dt in ("uint8", "uint16"):
@@ -81,7 +84,7 @@ def test_encode_and_decode_equal_the_reference(env, name):
             assert np.array_equal(rh[b].reshape(-1).view(np.uint32), e["ri"].view(np.uint32)), (name, b)
             assert nh[b] == e["payload"].shape[0], (name, b, nh[b], e["payload"].shape[0])
             assert ph[b, : nh[b]].tobytes() == e["payload"].tobytes(), (name, b)
-            assert p2.cpu().numpy()[b, : nh[b]].tobytes() == e["payload"].tobytes(), (name, b)
+            assert p2h[b, : nh[b]].tobytes() == e["payload"].tobytes(), (name, b)
             assert np.array_equal(ih[b].reshape(-1), e["image"]), (name, b)
             set_ = e["ri"] != 0
             w_own = f[e["own"][set_], 3]
@@ -94,13 +97,82 @@ def test_encode_and_decode_equal_the_reference(env, name):
                 inside = np.isfinite(t) & (t >= 0) & (t <= 255)
             err = np.abs(back[set_][inside].astype(np.float64) - w_own[inside].astype(np.float64))
             tol = 0.5 / scale + 2.0 ** -23 * np.maximum(1.0, np.abs(w_own[inside].astype(np.float64)))
-            print(name, b, "n", int(set_.sum()), "max err", float(err.max()) if err.size else 0.0, "bound", 0.5 / scale)
+            if b < 4 or "distinct" not in batch:     # (a batch that repeats four frames: one line per distinct frame)
+                print(name, b, "n", int(set_.sum()), "max err", float(err.max()) if err.size else 0.0, "bound", 0.5 / scale)
             assert np.all(err <= tol), (name, b, float(err.max()))
             if name == "example" or (name == "rounding" and scale == 100):
                 assert np.array_equal(back[set_].view(np.uint32), w_own.view(np.uint32)), (name, b)     # bit-equal to the input column
         if name == "example":
             z = np.load(os.path.join(HERE, "golden", "intensity_example_64E.npz"))
             assert ph[0, : nh[0]].tobytes() == z["payload"].tobytes()
+
+
+def _expected_rows(batch):
+    """(payload rows u8 [B, 8+P] with zeros behind nbytes, nbytes i32 [B], image u8 [B,P]) of a batch, from its references."""
+    P = batch["g"].H * batch["g"].W
+    rows = np.zeros((len(batch["ref"]), 8 + P), np.uint8)
+    for b, e in enumerate(batch["ref"]):
+        rows[b, : e["payload"].shape[0]] = e["payload"]
+    return rows, np.array([e["payload"].shape[0] for e in batch["ref"]], np.int32), np.stack([e["image"] for e in batch["ref"]])
+
+
+def test_past_the_grid_twice_and_from_a_dirty_scratch(env):
+    """The batch past the grid caps (two trips of the fill kernel and the owner pass, three of the fix-up pass) into the caller's buffers: a
+    second call gives the same bytes, and so does a call whose scratch holds 0xFF everywhere -- the upper half of the owner and lastz
+    planes is what the fill kernel's second trip initialises."""
+    import grid_caps as GC
+    torch, ops, dev = env["torch"], env["ops"], env["dev"]
+    batch = ref("past_the_grid")[0]
+    g, B = batch["g"], len(batch["frames"])
+    P = g.H * g.W
+    geom, rows, offs = _upload(env, batch)
+    total = rows.shape[0]
+    assert B * P > GC.INT_FILL_CAP * GC.INT_FILL_THREADS and total > GC.INT_OWNER_CAP * GC.INT_THREADS and total > 2 * GC.INT_FIXUP_CAP * GC.INT_THREADS
+    ri = ops.project(rows, offs, geom)
+    want_rows, want_n, want_image = _expected_rows(batch)
+    scratch = torch.empty(env["lib"].lib().rpcc_intensity_scratch_bytes(B, P), dtype=torch.uint8, device=dev)
+    outs = dict(payload=torch.empty((B, 8 + P), dtype=torch.uint8, device=dev), nbytes=torch.empty((B,), dtype=torch.int32, device=dev),
+                image=torch.empty((B, g.H, g.W), dtype=torch.uint8, device=dev), orphans=torch.empty((B,), dtype=torch.int32, device=dev))
+    for tag, fill in (("first", None), ("again", None), ("scratch 0xFF", 0xFF), ("scratch 0x00", 0x00)):
+        if fill is not None:
+            scratch.fill_(fill)
+        for t in outs.values():
+            t.zero_()
+        ops.intensity_encode(rows, offs, geom, ri, batch["scale"], want_image=True, scratch=scratch, **outs)
+        assert outs["orphans"].cpu().tolist() == [0] * B, tag
+        assert np.array_equal(outs["nbytes"].cpu().numpy(), want_n), tag
+        got = outs["payload"].cpu().numpy()
+        bad = np.flatnonzero((got != want_rows).any(1))
+        assert bad.size == 0, (tag, "frames", bad[:8].tolist(), "of kinds", batch["which"][bad[:8]].tolist())
+        assert np.array_equal(outs["image"].cpu().numpy().reshape(B, P), want_image), tag
+    # for the record: what the screened path really sends to the queue in the two chunks of the first workgroup whose drain leaves a remainder
+    queued = np.concatenate([(e["pix"] < 0) | (e["pix"] % g.W == 0) | (e["d"] == 0) for e in batch["ref"]])
+    maybe = np.concatenate([~batch["aimed_fast"][k] for k in batch["which"]])
+    w = int(GC.queue_facts(queued, maybe, total, GC.INT_THREADS, GC.INT_OWNER_CAP, GC.INT_THREADS)["remainder"][0])
+    for r in (0, 1):
+        a, b = GC.owner_rows(total, w, r)
+        sure, bad, slow = ops.project_fastpath_check(rows[a:b, :3].contiguous(), geom)[:3]
+        print("workgroup %d trip %d: rows %d .. %d, %d queued by rule, %d sent to the exact sequence" % (w, r, a, b, int(queued[a:b].sum()), slow))
+        assert bad == 0 and slow >= int(queued[a:b].sum())
+
+
+def test_past_the_grid_through_the_batch_compressor(env):
+    """The same 247 frames of rows through BatchCompressor(intensity_scale=255): every container's intensity trailer decodes to the
+    reference's payload of its frame (the geometry columns are other tests' matter)."""
+    from rpcc_amd.pipeline import BatchCompressor
+    from rpcc_amd.transformer import PCTransformer
+    cu = env["cu"]
+    batch = ref("past_the_grid")[0]
+    T = PCTransformer(dict(HORIZONTAL_FOV=IC.PAST_GEOM["hfov_deg"], VERTICAL_ANGLE_MAX=IC.PAST_GEOM["vmax_deg"], VERTICAL_ANGLE_MIN=IC.PAST_GEOM["vmin_deg"],
+                           RANGE_IMAGE_HEIGHT=IC.PAST_GEOM["H"], RANGE_IMAGE_WIDTH=IC.PAST_GEOM["W"]), device=env["dev"])
+    bc = BatchCompressor(T, cluster_num=10, accuracy=0.02, basic_compressor="bzip2", seed=4, intensity_scale=batch["scale"])
+    blobs = bc.compress(batch["frames"])
+    host = cu.BasicCompressor(method_name="bzip2")
+    assert len(blobs) == len(batch["frames"])
+    for b, (blob, e) in enumerate(zip(blobs, batch["ref"])):
+        span = cu.intensity_trailer_span(blob)
+        assert span is not None, b
+        assert bytes(host.decompress(blob[span[0]: span[1]])) == e["payload"].tobytes(), (b, int(batch["which"][b]))
 
 
 def test_refusals_zero_the_middle_frame_only(env):
@@ -258,8 +330,17 @@ def test_end_to_end(e2e, method, kw):
     bd = e2e["pl"].BatchDecompressor(T, M, 2 * ACC, basic_compressor=method, intensity=True)
     batch = bd.decompress(with_w)
     geometry = e2e["pl"].BatchDecompressor(T, M, 2 * ACC, basic_compressor=method).decompress(with_w)
+
+    def same(x, y, tag):
+        """Two containers byte for byte; where separate gzip.compress calls on the host wrote them, but for the members' MTIME bytes."""
+        if method in ("gzip", "deflate") and not kw:
+            GZ.assert_equal_but_mtime(x, y, tag)
+        else:
+            assert x == y, tag
+
     for b, (blob, bare) in enumerate(zip(with_w, plain)):
-        assert blob[: len(bare)] == bare and len(blob) > len(bare) + 4, (method, b)             # the bytes before the trailer: the container without it
+        same(blob[: len(bare)], bare, (method, b, "prefix"))                                    # the bytes before the trailer: the container without it
+        assert len(blob) > len(bare) + 4, (method, b)
         span = cu.intensity_trailer_span(blob)
         assert span is not None and span[0] == len(bare) + 4
         assert bytes(host.decompress(blob[span[0]: span[1]])) == e2e["refs"][b]["payload"].tobytes(), (method, b)
@@ -270,7 +351,7 @@ def test_end_to_end(e2e, method, kw):
         pay, _ = cu.encode_intensity(T, e2e["frames"][b], T.point_cloud_to_range_image(e2e["frames"][b]), SCALE)
         assert pay.tobytes() == e2e["refs"][b]["payload"].tobytes()
         _, compressed = cu.compress_point_cloud(bc, plane, idx_map, sal, rq, intensity=pay)
-        assert blob == cu.pack_bitstream(compressed), (method, b)
+        same(blob, cu.pack_bitstream(compressed), (method, b, "per frame"))
         # the way back, per frame and batched
         rec, pc, seg, w = e2e["dec"](cu.unpack_bitstream(blob, intensity=True), host, T, M, 2 * ACC, None, True, intensity=True)
         assert w.dtype == np.float32 and w.tobytes() == e2e["want"][b].tobytes(), (method, b)

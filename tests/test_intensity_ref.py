@@ -31,7 +31,7 @@ def built():
 def test_owner_rule_forms_agree(name):
     for batch in IC.CASES[name]():
         g = batch["g"]
-        for f in batch["frames"]:
+        for f in batch.get("distinct", batch["frames"]):         # (a batch that repeats frames names the distinct ones)
             e = R.encode_frame(f, g, batch["scale"])
             assert np.array_equal(R.owners_closed(e["d"], e["pix"], e["ri"]), e["own"]), name
             n = int((e["ri"] != 0).sum())
@@ -82,6 +82,70 @@ def test_cases_hold_what_they_promise():
     fr = IC.frames()[0]
     assert [f.shape[0] for f in fr["frames"]] == [0, 1, 63, 64, 4099]
     assert R.encode_frame(fr["frames"][0], fr["g"], 255)["payload"].shape[0] == 8
+
+
+def test_past_the_grid_reaches_every_second_trip_and_the_carried_queue():
+    """The batch of IC.past_the_grid(), by the reference and the launch rules alone (tests/grid_caps.py): the fill kernel and the owner pass
+    make a second trip and the fix-up pass a third, and in both passes the LDS queue goes through a drain to exactly 0, a drain that
+    leaves a remainder (then the tail behind the loop) and a refill after a drain.  A row counts as queued only where project_point_fast
+    refuses it by rule (the reference's column is 0, the depth 0 or not finite), and as certainly fast only where it was aimed so (a
+    quarter cell from a pixel centre in columns 2 .. W - 2 at 1 .. 60 m)."""
+    import grid_caps as GC
+    batch = IC.past_the_grid()[0]
+    g, frames, which = batch["g"], batch["frames"], batch["which"]
+    B, P = len(frames), g.H * g.W
+    offs = IC.offsets(frames)
+    total = int(offs[-1])
+    assert (g.H, g.W) == (16, 512) and [f.shape[0] for f in batch["distinct"]] == [6001, 6001, 6001, 0]
+    assert all(frames[b] is batch["distinct"][b % 4] for b in range(B))
+    assert total >= GC.INT_OWNER_CAP * GC.INT_THREADS + 65536 and B * P > GC.INT_FILL_CAP * GC.INT_FILL_THREADS
+    assert (B, total, B * P) == (247, 1116186, 2023424) or (GC.INT_OWNER_CAP, GC.INT_FILL_CAP, GC.INT_FIXUP_CAP) != (4096, 4096, 2048)
+    assert GC.fill_trips(B * P, GC.INT_FILL_THREADS, GC.INT_FILL_CAP) >= 2
+    assert GC.trips(total, GC.INT_THREADS, GC.INT_OWNER_CAP) >= 2 and GC.trips(total, GC.INT_THREADS, GC.INT_FIXUP_CAP) >= 3
+    refs = R.encode_frames(batch["distinct"], g, batch["scale"])
+    assert R.encode_frames(frames, g, batch["scale"])[4] is not refs[0]            # (another call: another memo) ...
+    again = R.encode_frames(frames, g, batch["scale"])
+    assert all(again[b] is again[b % 4] for b in range(B))                         # ... and one dict per distinct frame inside a call
+    queued = []
+    for f, e, fast in zip(batch["distinct"], refs, batch["aimed_fast"]):
+        assert np.array_equal(R.owners_closed(e["d"], e["pix"], e["ri"]), e["own"])               # owners_loop == owners_closed
+        assert np.unique(f[:, 3]).shape[0] == f.shape[0]                                          # intensities that all differ
+        q = (e["pix"] < 0) | (e["pix"] % g.W == 0) | (e["d"] == 0)
+        assert not (q & fast).any() and np.all((e["d"][fast] >= 0.99) & (e["d"][fast] <= 60.01))
+        queued.append(q)
+    seam, plain, zero = batch["distinct"][:3]
+    assert queued[0][: IC.PAST_HEAD].all() and set((refs[0]["pix"][: IC.PAST_HEAD] // g.W).tolist()) == set(range(g.H)) and not queued[1].any()
+    assert 0.70 < queued[0][IC.PAST_HEAD:].mean() < 0.80
+    # equal depths inside one pixel: the owner of most seam pixels has later rows of its own depth bits
+    e = refs[0]
+    tied = [p for p in np.flatnonzero(e["own"] >= 0) if p % g.W == 0 and ((e["pix"] == p) & (e["d"].view(np.uint32) == e["ri"][p].view(np.uint32))).sum() > 1]
+    assert len(tied) >= g.H // 2
+    # the zero frame: a zero beyond row 300 with 300 seam rows of its own pixel behind it, and an owner that the rule about zeros changes
+    e, p0 = refs[2], IC.past_zero_pixel(g)
+    z = IC.PAST_ZERO_AT
+    assert z > 300 and e["d"][z] == 0 and e["pix"][z] == p0 and np.all(e["pix"][z + 1: z + 1 + 300] == p0) and np.all(e["d"][z + 1: z + 1 + 300] > 0)
+    assert int((e["d"] == 0).sum()) == 13 and np.all(e["pix"][e["d"] == 0] == p0)
+    no_zero = np.where(e["d"] == 0, -1, e["pix"])
+    _, own_without = R.owners_loop(e["d"], no_zero, P)
+    assert e["own"][p0] >= 0 and own_without[p0] >= 0 and e["own"][p0] != own_without[p0]
+    assert zero[e["own"][p0], :3].tobytes() == zero[own_without[p0], :3].tobytes()                # equal depths before and after the zeros
+    assert R.quantise(zero[e["own"][p0], 3:], 255)[0] != R.quantise(zero[own_without[p0], 3:], 255)[0]
+    # the two passes' queues
+    q_all = np.concatenate([queued[k] for k in which])
+    maybe_all = np.concatenate([~batch["aimed_fast"][k] for k in which])
+    flagged = np.repeat(np.array([bool((r["d"] == 0).any()) for r in refs])[which], np.diff(offs))
+    starts = offs[:-1][which == 2]
+    assert (starts > GC.INT_FIXUP_CAP * GC.INT_THREADS).any() and (starts > 2 * GC.INT_FIXUP_CAP * GC.INT_THREADS).any()
+    for name, cap, part in (("owner", GC.INT_OWNER_CAP, np.ones(total, bool)), ("fix-up", GC.INT_FIXUP_CAP, flagged)):
+        facts = GC.queue_facts(q_all & part, maybe_all & part, total, GC.INT_THREADS, cap, GC.INT_THREADS)
+        print("intensity past the grid, %s pass: grid %d, trips %d; chunks that are one drain %d, drains with a remainder %d, refills %d, tails %d"
+              % (name, facts["grid"], facts["trips"], facts["full"].size, facts["remainder"].size, facts["refilled"].size, facts["tail"].size))
+        assert facts["grid"] == cap
+        assert facts["full"].size >= 1 and facts["remainder"].size >= 1 and facts["refilled"].size >= 1, name
+        w = int(facts["remainder"][0])
+        (a0, a1), (b0, b1) = GC.owner_rows(total, w, 0, cap), GC.owner_rows(total, w, 1, cap)
+        assert a1 - a0 == GC.INT_THREADS and b0 == a0 + cap * GC.INT_THREADS and b1 > b0
+        assert 1 <= int((q_all & part)[a0:a1].sum()) < GC.INT_THREADS and int((q_all & part)[a0:a1].sum() + (q_all & part)[b0:b1].sum()) > GC.INT_THREADS
 
 
 def test_quantiser_table():

@@ -2823,6 +2823,7 @@ struct WsLayout {
     int32_t *flags;
     uint32_t *hist;
     size_t bytes;
+    size_t clear_bytes() const { return (size_t)((char *)hist - (char *)sums); }   // sums and flags: what a clear of the model part covers, from `sums`
 };
 static WsLayout ws_layout(void *ws, int B, int P, int M) {
     const size_t KP = (size_t)kpad(M), T = (size_t)ntiles(P);
@@ -3066,7 +3067,7 @@ __global__ __launch_bounds__(COUNT_SCAN_THREADS) void count_scan_multi_kernel(co
     count_tiles_lds<COUNT_SCAN_THREADS>(A.seg + (int64_t)b * A.P, A.P, A.T, A.M + 2);
     model_scan_body<true, COUNT_SCAN_THREADS>(A, b);
 }
-// The fused kernel's LDS and the budget under which launch_hist_scan / mixed_labels take it: 96 KB of the CU's 160 KB hold 64 x 2048 (128
+// The fused kernel's LDS and the budget under which launch_point_model / mixed_labels take it: 96 KB of the CU's 160 KB hold 64 x 2048 (128
 // tiles) and 80 x 2000 (157 tiles) at up to 254 clusters (512 bytes a tile), and leave the kernel's static 3 KB and a neighbour some room.
 static inline size_t count_scan_lds_budget() { return (size_t)96 * 1024; }
 static inline size_t count_scan_lds_bytes(int P, int M) { return round_up((size_t)ntiles(P) * count_row_words(M + 2) * 4, 16); }
@@ -3250,18 +3251,28 @@ static inline size_t hist_lds_bytes(int KP, bool sums) { return (sums ? (size_t)
 template <class L>
 static inline bool hist_vec(int P, const L *seg, const float *ri) { return (P & 3) == 0 && seg4_aligned(seg) && (ri == nullptr || aligned16(ri)); }
 static inline int scan_kp2(int M) { int v = 1; while (v < M + 2) v <<= 1; return v; }   // labels rounded up to a power of two (<= 256)
-// histogram + scan: tile x label counts (and the labels' range sums when ri is given), then the offsets of the ordered scatter, counts, nnz and
-// -- with `model` -- the point model's rows.  The sums / flags block must be zero (memset or BatchInit) before the sums are added: by the
-// histogram here, or -- summed = true -- by the assignment that wrote seg (launch_assign with lay.sums / lay.flags); the histogram is then
-// the count-only form, and ri serves the scan's sequential fallback alone (point_model_row).  counted = true: no histogram launch at all.
-// The sums are the point model's: without `model` the histogram only counts, whatever ri is.  Byte labels that are to be counted and not
-// summed take ONE launch, count_scan_kernel, when the frame's table fits count_scan_lds_budget(); everything else -- uint16 labels, the
-// summing form (rpcc_point_model), counted = true, larger images -- keeps the two launches.
+// What the caller of the histogram + scan has prepared in the model part of its workspace: ordered, each value includes the one before it.
+// (The sums and flags are the point model's: without `model` nothing reads them, and only TABLE_COUNTED makes a difference.)
+enum TableState {
+    TABLE_FRESH,     // nothing: launch_point_model clears sums and flags (WsLayout::clear_bytes), then as TABLE_CLEARED
+    TABLE_CLEARED,   // sums and flags are zero (memset or BatchInit), nothing is cleared.  With ri and `model` the histogram adds the labels' range
+                     // sums, then the scan; otherwise it only counts, and byte labels whose table fits count_scan_lds_budget() take ONE launch
+    TABLE_SUMMED,    // the assignment that wrote seg has added the range sums (launch_assign with lay.sums / lay.flags): the histogram only counts
+                     // whatever ri is -- ri serves the scan's sequential fallback alone (point_model_row) --, in one launch if the table fits
+    TABLE_COUNTED,   // lay.hist holds the tile counts too (labels_in_kernel wrote them with seg): no histogram launch, the scan kernel alone
+};
+// histogram + scan: tile x label counts (and the labels' range sums), then the offsets of the ordered scatter, counts, nnz and -- with `model`
+// -- the point model's rows.  uint16 labels always keep the two launches.  Without ri, ground and model: the tile offsets, counts and nnz of a
+// segmentation alone (the plane model, the quantiser's entry, the decoders) -- neither kernel then adds to or reads sums / flags, and the clear
+// of TABLE_FRESH only keeps the block in the state the enum states (tests/test_gpu_buffers.py::test_plane_model_workspace: hostile contents).
 template <class L>
-static int launch_hist_scan(const float *ri, const L *seg, const double *ground, int B, int P, int M, const WsLayout &lay, float *model,
-                            int32_t *counts, int32_t *nnz, hipStream_t st, bool summed = false, bool counted = false) {
+static int launch_point_model(const float *ri, const L *seg, const double *ground, int B, int P, int M,
+                              float *model, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, TableState state = TABLE_FRESH) {
     const int KP = kpad(M), T = ntiles(P);
-    const bool hist_sums = ri != nullptr && model != nullptr && !summed;   // (the sums serve the model's rows alone)
+    const WsLayout lay = ws_layout(ws, B, P, M);
+    if (state == TABLE_FRESH) HIP_TRY(hipMemsetAsync(lay.sums, 0, lay.clear_bytes(), st));
+    const bool counted = state >= TABLE_COUNTED;
+    const bool hist_sums = ri != nullptr && model != nullptr && state < TABLE_SUMMED;   // (the sums serve the model's rows alone)
     const size_t sh = hist_lds_bytes(KP, hist_sums);
     const bool vec = hist_vec(P, seg, hist_sums ? ri : nullptr);
     // Byte labels to be counted and nothing to be summed: one launch, the counts never leave LDS (count_scan_kernel) -- if the table fits.
@@ -3277,7 +3288,7 @@ static int launch_hist_scan(const float *ri, const L *seg, const double *ground,
     }
     // (The scan as the tail of the histogram kernel -- the frame's last workgroup to finish runs it -- was measured in round 4: a workgroup must
     // release its rows device-wide before it draws its ticket, and an agent-scope fence writes the XCD's L2 back: 62 us -> 2.9 ms.)
-    if (counted) {   // lay.hist holds the tile counts already, and lay.sums what `summed` says (labels_in_kernel wrote both with seg)
+    if (counted) {   // lay.hist holds the tile counts already, and lay.sums the range sums (labels_in_kernel wrote both with seg)
     } else if (hist_sums) {
         if (vec) model_hist_kernel<true, L, true><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
         else     model_hist_kernel<false, L, true><<<dim3(T, B), 256, sh, st>>>(ri, seg, P, KP, T, lay.sums, lay.flags, lay.hist);
@@ -3294,16 +3305,6 @@ static int launch_hist_scan(const float *ri, const L *seg, const double *ground,
     }
     LAUNCH_CHECK();
     return RPCC_OK;
-}
-
-// One workgroup per frame: label totals, tile offsets, label bases, means, model rows.
-template <class L>
-static int launch_point_model(const float *ri, const L *seg, const double *ground, int B, int P, int M,
-                              float *model, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared = false, bool summed = false,
-                              bool counted = false) {
-    const WsLayout lay = ws_layout(ws, B, P, M);
-    if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
-    return launch_hist_scan(ri, seg, ground, B, P, M, lay, model, counts, nnz, st, summed, counted);
 }
 
 template <class L>
@@ -3619,30 +3620,52 @@ static CodecLayout codec_layout(void *ws, int B, int P, int M) {
 }
 extern "C" size_t rpcc_codec_workspace_bytes(int B, int P, int M) { return B > 0 && P > 0 && M > 0 ? codec_layout(nullptr, B, P, M).bytes : 0; }
 
-extern "C" int rpcc_contour_encode(const uint8_t *seg, int B, int H, int W, uint8_t *contour_bits, uint16_t *idx_sequence,
-                                   int32_t *nseq, void *ws, void *stream) {
+template <class L>
+static int contour_encode_entry(const L *seg, int B, int H, int W, uint8_t *contour_bits, uint16_t *idx_sequence, int32_t *nseq, void *ws, void *stream) {
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && seg && contour_bits && idx_sequence && nseq && ws);
     hipStream_t st = (hipStream_t)stream;
     const int P = H * W, T = ntiles(P);
     uint32_t *tile_cnt = codec_layout(ws, B, P, 1).tile_cnt;   // (M places no tile count)
-    contour_count_kernel<uint8_t><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt);
+    contour_count_kernel<L><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt);
     tile_scan_kernel<<<B, 256, 0, st>>>(tile_cnt, T, nseq);
-    contour_write_kernel<uint8_t><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt, contour_bits, idx_sequence);
+    contour_write_kernel<L><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt, contour_bits, idx_sequence);
     LAUNCH_CHECK();
     return RPCC_OK;
 }
+extern "C" int rpcc_contour_encode(const uint8_t *seg, int B, int H, int W, uint8_t *contour_bits, uint16_t *idx_sequence,
+                                   int32_t *nseq, void *ws, void *stream) {
+    return contour_encode_entry(seg, B, H, W, contour_bits, idx_sequence, nseq, ws, stream);
+}
+extern "C" int rpcc_contour_encode_wide(const uint16_t *seg, int B, int H, int W, uint8_t *contour_bits, uint16_t *idx_sequence, int32_t *nseq, void *ws, void *stream) {
+    return contour_encode_entry(seg, B, H, W, contour_bits, idx_sequence, nseq, ws, stream);
+}
 
-extern "C" int rpcc_contour_decode(const uint8_t *contour_bits, const uint16_t *idx_sequence, int B, int H, int W,
-                                   uint8_t *seg, void *ws, void *stream) {
+template <class L>
+static int contour_decode_entry(const uint8_t *contour_bits, const uint16_t *idx_sequence, int B, int H, int W, L *seg, void *ws, void *stream) {
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && seg && contour_bits && idx_sequence && ws);
     hipStream_t st = (hipStream_t)stream;
     const int P = H * W, T = ntiles(P);
     uint32_t *tile_cnt = codec_layout(ws, B, P, 1).tile_cnt;   // (M places no tile count)
     contour_bits_count_kernel<<<dim3(T, B), 256, 0, st>>>(contour_bits, P, T, tile_cnt);
     tile_scan_kernel<<<B, 256, 0, st>>>(tile_cnt, T, nullptr);
-    recover_map_kernel<uint8_t><<<dim3(T, B), 256, 0, st>>>(contour_bits, idx_sequence, P, T, tile_cnt, seg);
+    recover_map_kernel<L><<<dim3(T, B), 256, 0, st>>>(contour_bits, idx_sequence, P, T, tile_cnt, seg);
     LAUNCH_CHECK();
     return RPCC_OK;
+}
+extern "C" int rpcc_contour_decode(const uint8_t *contour_bits, const uint16_t *idx_sequence, int B, int H, int W,
+                                   uint8_t *seg, void *ws, void *stream) {
+    return contour_decode_entry(contour_bits, idx_sequence, B, H, W, seg, ws, stream);
+}
+extern "C" int rpcc_contour_decode_wide(const uint8_t *contour_bits, const uint16_t *idx_sequence, int B, int H, int W, uint16_t *seg, void *ws, void *stream) {
+    return contour_decode_entry(contour_bits, idx_sequence, B, H, W, seg, ws, stream);
+}
+
+// the decoder's quantisation steps: level_acc[0 .. levels) (uniform framework, levels == 0: the one step level_acc[0])
+static DecodeSteps decode_steps(const double *level_acc, int levels) {
+    DecodeSteps steps;
+    steps.levels = levels;
+    for (int i = 0; i < 8; i++) steps.acc[i] = i < (levels ? levels : 1) ? level_acc[i] : 0.0;
+    return steps;
 }
 
 extern "C" int rpcc_decode(const uint8_t *seg, const int16_t *q16, const float *model, const float *tm,
@@ -3652,14 +3675,10 @@ extern "C" int rpcc_decode(const uint8_t *seg, const int16_t *q16, const float *
     ARG_TRY(levels >= 0 && levels <= 8 && (levels == 0 || salience != nullptr));
     hipStream_t st = (hipStream_t)stream;
     const int KP = kpad(M), T = ntiles(P);
-    const WsLayout L = codec_layout(ws, B, P, M).L;
-    HIP_TRY(hipMemsetAsync(L.sums, 0, (size_t)((char *)L.hist - (char *)L.sums), st));
+    const WsLayout L = codec_layout(ws, B, P, M).L;   // (the model part opens the codec workspace)
     int rc;
-    if ((rc = launch_hist_scan(nullptr, seg, nullptr, B, P, M, L, nullptr, nullptr, nullptr, st))) return rc;
-    DecodeSteps steps;
-    steps.levels = levels;
-    for (int i = 0; i < 8; i++) steps.acc[i] = i < (levels ? levels : 1) ? level_acc[i] : 0.0;
-    decode_kernel<<<dim3(T, B), 256, decode_lds_bytes(KP), st>>>(seg, q16, model, tm, L.hist, salience, steps, P, M, KP, T, ri_rec, pc_rec);
+    if ((rc = launch_point_model<uint8_t>(nullptr, seg, nullptr, B, P, M, nullptr, nullptr, nullptr, ws, st))) return rc;
+    decode_kernel<<<dim3(T, B), 256, decode_lds_bytes(KP), st>>>(seg, q16, model, tm, L.hist, salience, decode_steps(level_acc, levels), P, M, KP, T, ri_rec, pc_rec);
     LAUNCH_CHECK();
     return RPCC_OK;
 }
@@ -3751,7 +3770,26 @@ static int launch_salience_levels(const int32_t *counts, const int32_t *kpn, int
     LAUNCH_CHECK();
     return RPCC_OK;
 }
-// the same from a segmentation and a key-point map
+// The non-uniform framework of the batch entries: key points (the map, and their number per label into kpn -- zero before), then salience level
+// and quantisation step per label from the per-label totals (pixels: the scan's counts; key points: kpn).  `io`'s fields, checked by nonuniform_ok.
+static bool nonuniform_ok(const rpcc_nonuniform_cfg *nu, const uint8_t *salience, const uint8_t *key_point_map) {
+    return !nu || (salience && key_point_map && nu->levels >= 1 && nu->levels <= 8 && nu->ground_level >= 0 && nu->ground_level < nu->levels);
+}
+static SalienceParams salience_params(const rpcc_nonuniform_cfg *nu) { return salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level); }
+template <class L>
+static int launch_key_points(const float *ri, const L *seg, int B, int H, int W, int M, const rpcc_nonuniform_cfg *nu, uint8_t *key_point_map, int32_t *kpn,
+                             hipStream_t st) {
+    return launch_features(ri, seg, B, H, W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num, nu->flat_num, nullptr, key_point_map, st,
+                           kpn, M + 2);
+}
+template <class L>
+static int launch_nonuniform(const float *ri, const L *seg, int B, int H, int W, int M, const rpcc_nonuniform_cfg *nu, const int32_t *counts,
+                             uint8_t *key_point_map, uint8_t *salience, int32_t *kpn, float *label_acc, hipStream_t st) {
+    int rc;
+    if ((rc = launch_key_points(ri, seg, B, H, W, M, nu, key_point_map, kpn, st))) return rc;
+    return launch_salience_levels<L>(counts, kpn, B, M, salience_params(nu), salience, label_acc, st);
+}
+// salience level and quantisation step per label from a segmentation and a key-point map
 template <class L>
 static int salience_entry(const L *seg, const uint8_t *key_point_map, const int32_t *level_kp_num, const float *level_acc, int levels,
                           int ground_level, int B, int P, int M, uint8_t *salience, float *label_acc, void *stream) {
@@ -3797,18 +3835,8 @@ extern "C" int rpcc_intra_predict_wide(const uint16_t *seg, const float *model, 
 static inline size_t plane_extra_offset(int B, int P, int M) { return ws_layout(nullptr, B, P, M).bytes + 256; }
 extern "C" size_t rpcc_plane_workspace_bytes(int B, int P, int M) { return B > 0 && P > 0 && M > 0 ? plane_extra_offset(B, P, M) + plane_layout(nullptr, B, P).bytes : 0; }
 
-// hist / scan for a segmentation without the point sums: tile offsets (ordered scatter), counts, nnz
-template <class L>
-static int launch_label_scan(const L *seg, int B, int P, int M, int32_t *counts, int32_t *nnz, void *ws, hipStream_t st, bool cleared, bool counted = false) {
-    const WsLayout lay = ws_layout(ws, B, P, M);
-    // (Not a requirement of this scan: without ri and model neither kernel below adds to or reads sums / flags -- the results are the same
-    // with the clear left out, tests/test_gpu_buffers.py::test_plane_model_workspace runs it on hostile contents.  It only keeps the block in
-    // the state launch_hist_scan's comment asks for; launch_point_model's clear is the one that matters.)
-    if (!cleared) HIP_TRY(hipMemsetAsync(lay.sums, 0, (size_t)((char *)lay.hist - (char *)lay.sums), st));
-    return launch_hist_scan(nullptr, seg, nullptr, B, P, M, lay, nullptr, counts, nnz, st, false, counted);
-}
-// plane rows from a segmentation whose tile offsets (launch_label_scan) are in ws; extra = the plane area (plane_layout).  Two launches:
-// the label-ordered lists, then the fits.
+// plane rows from a segmentation whose tile offsets (launch_point_model without ri, ground and model) are in ws; extra = the plane area
+// (plane_layout).  Two launches: the label-ordered lists, then the fits.
 template <class L>
 static int launch_label_order(const float *ri, const float *tm, const L *seg, int B, int P, int M, void *ws, void *extra, hipStream_t st) {
     const int KP = kpad(M), T = ntiles(P);
@@ -3822,6 +3850,18 @@ static int launch_label_order(const float *ri, const float *tm, const L *seg, in
     LAUNCH_CHECK();
     return RPCC_OK;
 }
+// the fits' constants (RANSAC inlier distance, fewest points of a plane, iterations: plane_model_kernel<10>) beside a call's own parameters
+static PlaneParams plane_params(double cos_cut, uint32_t seed, const int64_t *frame_ids, const double *inject) {
+    PlaneParams pp;
+    pp.cos_cut = cos_cut; pp.thr = 0.1f; pp.min_points = 30; pp.iters = 10; pp.seed = seed; pp.frame_ids = frame_ids; pp.inject = inject;
+    return pp;
+}
+// The fits' grid for B frames: B x (K-2) workgroups that exist for the labels above PL_BIG points (they start first: the long ones are the
+// tail of the launch), then one wavefront per label for the rest
+static inline int plane_grid(int B, int M) {
+    const int K = M + 2, wpg = PL_THREADS / 64, groups = (K + wpg - 1) / wpg;
+    return B * (K - 2) + B * groups;
+}
 static PlaneGroupArgs plane_group_args(const float *tm, const double *ground, int B, int P, int M, double cos_cut, uint32_t seed,
                                        const int64_t *frame_ids, float *model, const int32_t *counts, void *ws, void *extra, const double *inject) {
     WsLayout L = ws_layout(ws, B, P, M);
@@ -3829,18 +3869,12 @@ static PlaneGroupArgs plane_group_args(const float *tm, const double *ground, in
     PlaneGroupArgs a;
     a.tm = tm; a.order_all = pa.order; a.pts_all = pa.pts4; a.hist = L.hist; a.counts = counts;
     a.ground = ground; a.B = B; a.P = P; a.T = ntiles(P); a.model = model;
-    a.pp.cos_cut = cos_cut; a.pp.thr = 0.1f; a.pp.min_points = 30; a.pp.iters = 10; a.pp.seed = seed; a.pp.frame_ids = frame_ids; a.pp.inject = inject;
+    a.pp = plane_params(cos_cut, seed, frame_ids, inject);
     return a;
 }
-static int launch_plane_fits(const float *tm, const double *ground, int B, int P, int M, double cos_cut, uint32_t seed, const int64_t *frame_ids,
-                             float *model, const int32_t *counts, void *ws, void *extra, hipStream_t st, const double *inject = nullptr) {
-    const int K = M + 2;
-    const PlaneGroupArgs a = plane_group_args(tm, ground, B, P, M, cos_cut, seed, frame_ids, model, counts, ws, extra, inject);
-    // B x (K-2) workgroups that exist for the labels above PL_BIG points (they start first: the long ones are the tail of
-    // the launch), then one wavefront per label for the rest
-    const int wpg = PL_THREADS / 64, groups = (K + wpg - 1) / wpg;
-    plane_model_kernel<10><<<B * (K - 2) + B * groups, PL_THREADS, 0, st>>>(a.tm, a.order_all, a.pts_all, a.hist, a.counts, a.ground, B, P, M, kpad(M), a.T,
-                                                                            a.pp, PL_BIG, a.model);
+static int launch_plane_fits(const PlaneGroupArgs &a, int M, hipStream_t st) {
+    plane_model_kernel<10><<<plane_grid(a.B, M), PL_THREADS, 0, st>>>(a.tm, a.order_all, a.pts_all, a.hist, a.counts, a.ground, a.B, a.P, M, kpad(M), a.T,
+                                                                      a.pp, PL_BIG, a.model);
     LAUNCH_CHECK();
     return RPCC_OK;
 }
@@ -3853,10 +3887,10 @@ static int plane_model_entry(const float *ri, const float *tm, const L *seg, con
     ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && P > 0 && M > 0 && M <= LabelTraits<L>::max_clusters && ri && tm && seg && model && counts && ws);
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if ((rc = launch_label_scan(seg, B, P, M, counts, nullptr, ws, st, false))) return rc;
+    if ((rc = launch_point_model<L>(nullptr, seg, nullptr, B, P, M, nullptr, counts, nullptr, ws, st))) return rc;
     void *extra = reinterpret_cast<char *>(ws) + plane_extra_offset(B, P, M);
     if ((rc = launch_label_order(ri, tm, seg, B, P, M, ws, extra, st))) return rc;
-    return launch_plane_fits(tm, ground, B, P, M, cos_cut, seed, frame_ids, model, counts, ws, extra, st, inject_planes);
+    return launch_plane_fits(plane_group_args(tm, ground, B, P, M, cos_cut, seed, frame_ids, model, counts, ws, extra, inject_planes), M, st);
 }
 extern "C" int rpcc_plane_model(const float *ri, const float *tm, const uint8_t *seg, const double *ground, int B, int P, int M, double cos_cut, uint32_t seed,
                                 const int64_t *frame_ids, const double *inject_planes, float *model, int32_t *counts, void *ws, void *stream) {
@@ -3871,6 +3905,34 @@ extern "C" int rpcc_plane_model_wide(const float *ri, const float *tm, const uin
 // ================================================================================================
 // fused batch entry (uniform framework, FPS segmentation, point model): a2 .. a11
 // ================================================================================================
+// What every batch entry runs once its segmentation exists -- label table and scan, point or plane model, (non-uniform framework) key points and
+// salience levels, prediction and quantiser -- and all it reads for that: an io's buffers and choices (rpcc_batch_io or rpcc_labels_io) and the
+// entry's workspace.  tail_labels / tail_planes / tail_quantise are the launches, split at the stage seams; rpcc_compress_batch_mixed builds
+// its groups' rows from the same fields (mixed_labels, mixed_planes, mixed_quantise).
+struct BatchTail {
+    const float *ri, *tm; const double *ground; void *seg;
+    float *model; int32_t *counts, *nnz; int16_t *q16; const int64_t *frame_ids;
+    bool point; double plane_cos_cut; uint32_t plane_seed;   // model method 0, or the plane model's parameters
+    const rpcc_nonuniform_cfg *nu; uint8_t *salience, *key_point_map;   // nu == nullptr: uniform framework
+    int B, H, W, M; float acc;
+    void *ws, *extra;   // model part first; the plane area
+    int32_t *kpn; float *label_acc;   // (both nullptr in the uniform framework)
+    int32_t *epoch;   // the last kernel of a fused batch gives the next call's projection flags a new mark (or nullptr)
+    TableState state;
+    int P() const { return H * W; }
+    // the scan's arguments: rows of the point model, or tile offsets, counts and nnz alone (ri: the scan's sequential fallback)
+    const float *scan_ri() const { return point ? ri : nullptr; }
+    const double *scan_ground() const { return point ? ground : nullptr; }
+    float *scan_model() const { return point ? model : nullptr; }
+    PlaneGroupArgs plane_args() const { return plane_group_args(tm, ground, B, P(), M, plane_cos_cut, plane_seed, frame_ids, model, counts, ws, extra, nullptr); }
+};
+template <class IO>
+static BatchTail batch_tail(const IO *io, int B, rpcc_geom g, int M, float acc, void *ws, void *extra, int32_t *kpn, float *label_acc, int32_t *epoch,
+                            TableState state) {
+    return BatchTail{io->ri, io->tm, io->ground, io->seg, io->model, io->counts, io->nnz, io->q16, io->frame_ids, io->model_method == 0,
+                     io->plane_cos_cut, (uint32_t)io->plane_seed, io->nonuniform, io->salience, io->key_point_map, B, g.H, g.W, M, acc, ws, extra,
+                     io->nonuniform ? kpn : nullptr, io->nonuniform ? label_acc : nullptr, epoch, state};
+}
 // Everything a call derives from its arguments for ONE geometry group (one io, one rpcc_geom): the carve-up of the workspace and the
 // choices that follow from the flags.  rpcc_compress_batch has one plan, rpcc_compress_batch_mixed one per group.
 struct BatchPlan : BatchLayout {
@@ -3879,6 +3941,7 @@ struct BatchPlan : BatchLayout {
     bool fit_ground, tiled;   // tiled: the FPS is tile-pruned, so the mask kernel fills the tile table
     int32_t *zcnt;
     BatchInit bi;
+    BatchTail tail;   // as it is once the assignment has run (launch_batch_assign): TABLE_SUMMED with the point model
     const void *beams = nullptr;   // rpcc_compress_batch_beams: the projection goes through this per-beam index
 };
 static int plan_batch(BatchPlan &p, const rpcc_batch_io *io, int Bs, int64_t npts, rpcc_geom g, int M, double ground_threshold, float acc, char *ws) {
@@ -3893,12 +3956,39 @@ static int plan_batch(BatchPlan &p, const rpcc_batch_io *io, int Bs, int64_t npt
     // flags are marked with an epoch kept in the workspace (BatchInit), so the batch has no initialisation launch.
     p.bi.tm = io->tm; p.bi.soa = p.rays_soa; p.bi.P = P; p.bi.info = io->info; p.bi.B = Bs; p.bi.on = 1;
     p.bi.z0 = {reinterpret_cast<uint32_t *>(p.zcnt), p.zcnt ? (int)rs_count_words(Bs) : 0};
-    p.bi.z1 = {reinterpret_cast<uint32_t *>(p.L.sums), (int)(((char *)p.L.hist - (char *)p.L.sums) / 4)};
+    p.bi.z1 = {reinterpret_cast<uint32_t *>(p.L.sums), (int)(p.L.clear_bytes() / 4)};
     if (!io->nonuniform) { p.label_acc = nullptr; p.kpn = nullptr; }
     p.bi.z2 = {reinterpret_cast<uint32_t *>(p.kpn), p.kpn ? Bs * (M + 2) : 0};  // key points per label
     p.tiled = fps_pruned(fps_pick_range(g.H, g.W, Bs, io->flags, range_quads16(g.W, io->ri, p.temp, io->tm), true));
+    p.tail = batch_tail(io, Bs, g, M, acc, ws, p.extra, p.kpn, p.label_acc, p.epoch, io->model_method == 0 ? TABLE_SUMMED : TABLE_CLEARED);
     return RPCC_OK;
 }
+// The assignment of a batch.  temp: the FPS state is the un-fused minimum the assignment's bound needs, a CUDA-binary mode contracts it.  The point
+// model's range sums are added here -- into the block BatchInit cleared --, so its histogram only counts (TABLE_SUMMED).
+template <class L>
+static int launch_batch_assign(const BatchPlan &p, hipStream_t st) {
+    const rpcc_batch_io *io = p.io;
+    const bool point = io->model_method == 0;
+    return launch_assign(io->ri, io->tm, io->ground, io->centers, p.Bs, p.g.H, p.g.W, p.M, reinterpret_cast<L *>(io->seg), st,
+                         (io->flags & RPCC_FPS_MODE_BITS) ? nullptr : p.temp, point ? p.L.sums : nullptr, point ? p.L.flags : nullptr);
+}
+// label table + scan with the point model's rows, or + the plane model's label-ordered lists
+template <class L>
+static int tail_labels(const BatchTail &t, hipStream_t st) {
+    const L *seg = reinterpret_cast<const L *>(t.seg);
+    int rc;
+    if ((rc = launch_point_model(t.scan_ri(), seg, t.scan_ground(), t.B, t.P(), t.M, t.scan_model(), t.counts, t.nnz, t.ws, st, t.state))) return rc;
+    return t.point ? RPCC_OK : launch_label_order(t.ri, t.tm, seg, t.B, t.P(), t.M, t.ws, t.extra, st);
+}
+static int tail_planes(const BatchTail &t, hipStream_t st) { return t.point ? RPCC_OK : launch_plane_fits(t.plane_args(), t.M, st); }
+template <class L>
+static int tail_quantise(const BatchTail &t, hipStream_t st) {
+    const L *seg = reinterpret_cast<const L *>(t.seg);
+    int rc;
+    if (t.nu && (rc = launch_nonuniform(t.ri, seg, t.B, t.H, t.W, t.M, t.nu, t.counts, t.key_point_map, t.salience, t.kpn, t.label_acc, st))) return rc;
+    return launch_predict_quantize(t.ri, t.tm, seg, t.model, t.acc, t.label_acc, nullptr, t.B, t.P(), t.M, t.q16, nullptr, nullptr, t.ws, st, t.epoch);
+}
+
 // The launches of a batch in order, as stages: the three marked (*) are the kernels with one workgroup per frame or per label, which
 // rpcc_compress_batch_mixed runs as one launch over all groups (the others it runs group after group).
 enum { ST_PROJECT, ST_GROUND /* (*) */, ST_MASK, ST_FPS /* (*) */, ST_ASSIGN_LABELS, ST_PLANES /* (*) */, ST_QUANTISE, ST_COUNT };
@@ -3906,7 +3996,6 @@ template <class L>
 static int run_stage(const BatchPlan &p, int stage, hipStream_t st) {
     const rpcc_batch_io *io = p.io;
     const int Bs = p.Bs, M = p.M, P = p.P;
-    L *seg = reinterpret_cast<L *>(io->seg);
     int rc;
     switch (stage) {
     case ST_PROJECT:
@@ -3928,32 +4017,12 @@ static int run_stage(const BatchPlan &p, int stage, hipStream_t st) {
         return launch_fps_range(io->ri, io->tm, p.temp, io->info, Bs, p.g.H, p.g.W, M, io->cen_pix, io->centers, io->flags, false,
                                 p.tiled ? p.tiletab : nullptr, io->timer, st, p.rays_soa);
     case ST_ASSIGN_LABELS:
-        // (the FPS state is the un-fused minimum the assignment's bound needs; a CUDA-binary mode contracts it)
-        // (the point model's range sums are added by the assignment -- into the block BatchInit cleared --, its histogram only counts)
-        if ((rc = launch_assign(io->ri, io->tm, io->ground, io->centers, Bs, p.g.H, p.g.W, M, seg, st,
-                                (io->flags & RPCC_FPS_MODE_BITS) ? nullptr : p.temp, io->model_method == 0 ? p.L.sums : nullptr,
-                                io->model_method == 0 ? p.L.flags : nullptr))) return rc;
-        if (io->model_method == 0) return launch_point_model(io->ri, seg, io->ground, Bs, P, M, io->model, io->counts, io->nnz, p.ws, st, true, true);
-        if ((rc = launch_label_scan(seg, Bs, P, M, io->counts, io->nnz, p.ws, st, true))) return rc;
-        return launch_label_order(io->ri, io->tm, seg, Bs, P, M, p.ws, p.extra, st);
+        if ((rc = launch_batch_assign<L>(p, st))) return rc;
+        return tail_labels<L>(p.tail, st);
     case ST_PLANES:
-        if (io->model_method == 0) return RPCC_OK;
-        return launch_plane_fits(io->tm, io->ground, Bs, P, M, io->plane_cos_cut, (uint32_t)io->plane_seed, io->frame_ids, io->model,
-                                 io->counts, p.ws, p.extra, st);
+        return tail_planes(p.tail, st);
     case ST_QUANTISE:
-        if (io->nonuniform) {   // key points -> salience level and quantisation step per label
-            const rpcc_nonuniform_cfg *nu = io->nonuniform;
-            if ((rc = launch_features(io->ri, seg, Bs, p.g.H, p.g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num,
-                                      nu->flat_num, nullptr, io->key_point_map, st, p.kpn, M + 2)))
-                return rc;
-            // levels from the per-label totals (pixels: the scan's counts; key points: counted by the key-point kernel)
-            if ((rc = launch_salience_levels<L>(io->counts, p.kpn, Bs, M, salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level),
-                                                io->salience, p.label_acc, st)))
-                return rc;
-        }
-        // (the last kernel of the batch gives the next call's projection flags a new mark: p.epoch)
-        return launch_predict_quantize(io->ri, io->tm, seg, io->model, p.acc, p.label_acc, nullptr, Bs, P, M, io->q16,
-                                       nullptr, nullptr, p.ws, st, p.epoch);
+        return tail_quantise<L>(p.tail, st);
     }
     return RPCC_ERR_ARG;
 }
@@ -3972,10 +4041,7 @@ static int check_batch_io(const rpcc_batch_io *io, int B, rpcc_geom g, int M, co
         ARG_TRY(P % 4 == 0 || fps_pick_range(g.H, g.W, B, io->flags, true, true).family != FPS_ONE_PASS);
     ARG_TRY(io->model_method == 0 || io->model_method == 1);
     ARG_TRY(point_floats(io->point_stride_bytes) > 0 && (io->point_stride_bytes != 16 || (reinterpret_cast<uintptr_t>(io->xyz) & 15u) == 0));
-    if (io->nonuniform) {
-        const rpcc_nonuniform_cfg *nu = io->nonuniform;
-        ARG_TRY(io->salience && io->key_point_map && nu->levels >= 1 && nu->levels <= 8 && nu->ground_level >= 0 && nu->ground_level < nu->levels);
-    }
+    ARG_TRY(nonuniform_ok(io->nonuniform, io->salience, io->key_point_map));
     return RPCC_OK;
 }
 
@@ -4057,13 +4123,12 @@ static int mixed_fps(const BatchPlan *pl, int G, hipStream_t st) {
 static int mixed_planes(const BatchPlan *pl, int G, hipStream_t st) {
     PlaneMulti m;
     m.n = 0; m.first[0] = 0;
-    const int M = pl[0].M, K = M + 2, wpg = PL_THREADS / 64, groups = (K + wpg - 1) / wpg;
+    const int M = pl[0].M;
     for (int i = 0; i < G; i++) {
-        const BatchPlan &p = pl[i];
-        if (p.io->model_method == 0) continue;
-        m.a[m.n] = plane_group_args(p.io->tm, p.io->ground, p.Bs, p.P, M, p.io->plane_cos_cut, (uint32_t)p.io->plane_seed, p.io->frame_ids,
-                                    p.io->model, p.io->counts, p.ws, p.extra, nullptr);
-        m.first[m.n + 1] = m.first[m.n] + p.Bs * (K - 2) + p.Bs * groups;
+        const BatchTail &t = pl[i].tail;
+        if (t.point) continue;
+        m.a[m.n] = t.plane_args();
+        m.first[m.n + 1] = m.first[m.n] + plane_grid(t.B, M);
         m.n++;
     }
     if (m.n == 0) return RPCC_OK;
@@ -4079,17 +4144,6 @@ template <class A>
 static void multi_add(MultiArgs<A> &m, const A &a, int frames, int per_frame) {
     m.a[m.n] = a; m.per[m.n] = per_frame; m.first[m.n + 1] = m.first[m.n] + frames * per_frame; m.n++;
 }
-static int mixed_assign(const BatchPlan *pl, int G, hipStream_t st) {
-    int rc;
-    for (int i = 0; i < G; i++) {
-        const rpcc_batch_io *io = pl[i].io;
-        const bool point = io->model_method == 0;   // (the point model's range sums: as in run_stage)
-        if ((rc = launch_assign(io->ri, io->tm, io->ground, io->centers, pl[i].Bs, pl[i].g.H, pl[i].g.W, pl[i].M, io->seg, st,
-                                (io->flags & RPCC_FPS_MODE_BITS) ? nullptr : pl[i].temp, point ? pl[i].L.sums : nullptr,
-                                point ? pl[i].L.flags : nullptr))) return rc;
-    }
-    return RPCC_OK;
-}
 // label histograms + scan (+ the point model's rows, or the plane model's label-ordered lists)
 static int mixed_labels(const BatchPlan *pl, int G, hipStream_t st) {
     const int M = pl[0].M, KP = kpad(M);
@@ -4097,20 +4151,18 @@ static int mixed_labels(const BatchPlan *pl, int G, hipStream_t st) {
     mh.n = ms.n = mo.n = 0; mh.first[0] = ms.first[0] = mo.first[0] = 0;
     for (int i = 0; i < G; i++) {
         const BatchPlan &p = pl[i];
-        const rpcc_batch_io *io = p.io;
+        const BatchTail &t = p.tail;   // (TABLE_SUMMED or, without the model's rows, TABLE_CLEARED: every group's histogram only counts)
+        const uint8_t *seg = reinterpret_cast<const uint8_t *>(t.seg);
         const int T = ntiles(p.P);
-        const bool point = io->model_method == 0;
-        const float *ri = point ? io->ri : nullptr;   // (the scan's sequential fallback; the sums themselves came with the assignment)
-        multi_add(mh, HistGroup{io->seg, p.P, T, hist_vec(p.P, io->seg, (const float *)nullptr) ? 1 : 0, p.L.hist}, p.Bs, T);
-        multi_add(ms, ScanArgs{ri, io->seg, point ? io->ground : nullptr, p.P, M, KP, T, scan_kp2(M), p.L.sums, p.L.flags, p.L.hist,
-                               point ? io->model : nullptr, io->counts, io->nnz}, p.Bs, 1);
-        const PlaneLayout pa = plane_layout(p.extra, p.Bs, p.P);
-        if (!point) multi_add(mo, OrderGroup{io->seg, p.L.hist, p.P, T, pa.order, io->ri, io->tm, pa.pts4}, p.Bs, T);
+        multi_add(mh, HistGroup{seg, p.P, T, hist_vec(p.P, seg, (const float *)nullptr) ? 1 : 0, p.L.hist}, t.B, T);
+        multi_add(ms, ScanArgs{t.scan_ri(), seg, t.scan_ground(), p.P, M, KP, T, scan_kp2(M), p.L.sums, p.L.flags, p.L.hist, t.scan_model(), t.counts, t.nnz},
+                  t.B, 1);
+        const PlaneLayout pa = plane_layout(t.extra, t.B, p.P);
+        if (!t.point) multi_add(mo, OrderGroup{seg, p.L.hist, p.P, T, pa.order, t.ri, t.tm, pa.pts4}, t.B, T);
     }
-    size_t ch = 0;   // the fused count + scan launch when every group's table fits (launch_hist_scan's rule)
-    bool fits = true;
-    for (int i = 0; i < G; i++) { fits = fits && count_scan_fits(pl[i].P, M); ch = std::max(ch, count_scan_lds_bytes(pl[i].P, M)); }
-    if (fits) {
+    size_t ch = 0;   // the fused count + scan launch when every group's table fits (launch_point_model's rule for TABLE_CLEARED / TABLE_SUMMED)
+    for (int i = 0; i < G; i++) ch = std::max(ch, count_scan_lds_bytes(pl[i].P, M));
+    if (ch <= count_scan_lds_budget()) {
         HIP_TRY(ensure_dyn_lds(reinterpret_cast<const void *>(&count_scan_multi_kernel), (int)ch));
         count_scan_multi_kernel<<<ms.first[ms.n], COUNT_SCAN_THREADS, ch, st>>>(ms);
         LAUNCH_CHECK();
@@ -4134,19 +4186,16 @@ static int mixed_quantise(const BatchPlan *pl, int G, hipStream_t st) {
     msal.n = mq.n = 0; msal.first[0] = mq.first[0] = 0;
     for (int i = 0; i < G; i++) {
         const BatchPlan &p = pl[i];
-        const rpcc_batch_io *io = p.io;
-        if (io->nonuniform) {
-            const rpcc_nonuniform_cfg *nu = io->nonuniform;
-            if ((rc = launch_features(io->ri, io->seg, p.Bs, p.g.H, p.g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num,
-                                      nu->flat_num, nullptr, io->key_point_map, st, p.kpn, M + 2)))
-                return rc;
-            multi_add(msal, SalienceGroup{io->counts, p.kpn, salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level), io->salience,
-                                          p.label_acc}, p.Bs, 1);
+        const BatchTail &t = p.tail;
+        const uint8_t *seg = reinterpret_cast<const uint8_t *>(t.seg);
+        if (t.nu) {   // launch_nonuniform's pair: the key points here, the levels as a row of the shared launch
+            if ((rc = launch_key_points(t.ri, seg, t.B, t.H, t.W, M, t.nu, t.key_point_map, t.kpn, st))) return rc;
+            multi_add(msal, SalienceGroup{t.counts, t.kpn, salience_params(t.nu), t.salience, t.label_acc}, t.B, 1);
         }
         const int T = ntiles(p.P);
-        const bool vec = quantise_vec(p.P, io->seg, io->ri, io->tm, nullptr, false);
+        const bool vec = quantise_vec(p.P, seg, t.ri, t.tm, nullptr, false);
         // (every group's kernel advances its own workspace's epoch: its frame 0 / tile 0 workgroup)
-        multi_add(mq, QuantGroup{io->ri, io->tm, io->model, p.label_acc, io->seg, p.L.hist, p.P, T, vec ? 1 : 0, io->q16, p.epoch}, p.Bs, T);
+        multi_add(mq, QuantGroup{t.ri, t.tm, t.model, t.label_acc, seg, p.L.hist, p.P, T, vec ? 1 : 0, t.q16, t.epoch}, t.B, T);
     }
     if (msal.n > 0) {
         salience_levels_multi_kernel<<<msal.first[msal.n], 256, 0, st>>>(msal, M);
@@ -4171,7 +4220,10 @@ extern "C" int rpcc_compress_batch_mixed(const rpcc_batch_io *ios, const int *Bs
         if (stage == ST_GROUND) rc = mixed_ground(pl, G, st);
         else if (stage == ST_FPS) rc = mixed_fps(pl, G, st);
         else if (stage == ST_PLANES) rc = mixed_planes(pl, G, st);
-        else if (stage == ST_ASSIGN_LABELS) { if (!(rc = mixed_assign(pl, G, st))) rc = mixed_labels(pl, G, st); }
+        else if (stage == ST_ASSIGN_LABELS) {   // the assignment group after group, then the labels' launches over the groups
+            for (int i = 0; i < G && !(rc = launch_batch_assign<uint8_t>(pl[i], st)); i++) {}
+            if (!rc) rc = mixed_labels(pl, G, st);
+        }
         else if (stage == ST_QUANTISE) rc = mixed_quantise(pl, G, st);
         else
             for (int i = 0; i < G && !(rc = run_stage<uint8_t>(pl[i], stage, st)); i++) {}
@@ -4190,10 +4242,7 @@ extern "C" int rpcc_compress_batch_mixed(const rpcc_batch_io *ios, const int *Bs
 // instantiated for uint16_t labels (assign_kernel<uint16_t, 16>: sixteen screening rounds of 64 centres) instead of going through the radix sort of
 // wide_kernels.h (89 k frames/s at 300 clusters against 367 k at 100: a 4 x cliff at 254 -> 255).  Such a batch is the fused batch's own plan and
 // stages (run_batch<uint16_t>); ws is laid out as for rpcc_compress_batch (rpcc_wide_workspace_bytes covers rpcc_workspace_bytes_general for these counts).
-static bool mid_clusters_ok(const rpcc_batch_io *io, rpcc_geom g, int M) {
-    (void)io;
-    return M <= RPCC_MAX_CLUSTERS_MID && fps_prunable(fps_tiling_range(g.H, g.W));
-}
+static bool mid_clusters_ok(rpcc_geom g, int M) { return M <= RPCC_MAX_CLUSTERS_MID && fps_prunable(fps_tiling_range(g.H, g.W)); }
 
 // carve-up of a wide workspace: [ keys, vals (in / out) u32 4 x [B,P] | pos i32 [B,P] | order u32 [B,P] | pts4 float4 [B,P] | sums u64 [B,K] |
 //   base u32 [B,K] | kpn i32 [B,K] | label_acc f32 [B,K] | flags i32 [B,4] | cen4 float4 [B,M] | FPS temp f32 [B,P] | FPS tile table |
@@ -4254,7 +4303,7 @@ extern "C" int rpcc_compress_batch_wide(const rpcc_batch_io *io, int B, rpcc_geo
     hipStream_t st = (hipStream_t)stream;
     const int P = g.H * g.W, K = M + 2;
     ARG_TRY(fps_prunable(fps_tiling_range(g.H, g.W)));
-    if (mid_clusters_ok(io, g, M)) return run_batch<uint16_t>(io, B, g, M, ground_threshold, acc, ws, (1 << ST_COUNT) - 1, st);
+    if (mid_clusters_ok(g, M)) return run_batch<uint16_t>(io, B, g, M, ground_threshold, acc, ws, (1 << ST_COUNT) - 1, st);
     const WideWs w = wide_layout(ws, B, P, M, io->total);
     uint16_t *seg = reinterpret_cast<uint16_t *>(io->seg);
     if ((rc = launch_project(io->xyz, io->offsets, io->total, 0, B, g, io->ri, w.proj, w.proj_bytes, st, nullptr, nullptr, nullptr, nullptr,
@@ -4272,21 +4321,14 @@ extern "C" int rpcc_compress_batch_wide(const rpcc_batch_io *io, int B, rpcc_geo
         wide_point_model_kernel<uint16_t><<<dim3((K + 255) / 256, B), 256, 0, st>>>(io->ri, seg, io->ground, io->counts, w.sums, w.flags, P, K, io->model);
         LAUNCH_CHECK();
     } else {   // the plane fits read a label's slice of the ordered lists through "tile 0" of a one-tile offset table: base[b][k]
-        PlaneParams pp;   // (as plane_group_args sets them)
-        pp.cos_cut = io->plane_cos_cut; pp.thr = 0.1f; pp.min_points = 30; pp.iters = 10; pp.seed = (uint32_t)io->plane_seed; pp.frame_ids = io->frame_ids; pp.inject = nullptr;
-        const int wpg = PL_THREADS / 64, groups = (K + wpg - 1) / wpg;
-        plane_model_kernel<10><<<B * (K - 2) + B * groups, PL_THREADS, 0, st>>>(io->tm, w.order, w.pts4, w.base, io->counts, io->ground, B, P, M, K, 1, pp, PL_BIG, io->model);
+        const PlaneParams pp = plane_params(io->plane_cos_cut, (uint32_t)io->plane_seed, io->frame_ids, nullptr);
+        plane_model_kernel<10><<<plane_grid(B, M), PL_THREADS, 0, st>>>(io->tm, w.order, w.pts4, w.base, io->counts, io->ground, B, P, M, K, 1, pp, PL_BIG, io->model);
         LAUNCH_CHECK();
     }
     const float *label_acc = nullptr;
     if (io->nonuniform) {
-        const rpcc_nonuniform_cfg *nu = io->nonuniform;
         HIP_TRY(hipMemsetAsync(w.kpn, 0, (size_t)B * K * 4, st));
-        if ((rc = launch_features<uint16_t>(io->ri, seg, B, g.H, g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num, nu->flat_num,
-                                            nullptr, io->key_point_map, st, w.kpn, K))) return rc;
-        if ((rc = launch_salience_levels<uint16_t>(io->counts, w.kpn, B, M, salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level),
-                                                   io->salience, w.label_acc, st)))
-            return rc;
+        if ((rc = launch_nonuniform(io->ri, seg, B, g.H, g.W, M, io->nonuniform, io->counts, io->key_point_map, io->salience, w.kpn, w.label_acc, st))) return rc;
         label_acc = w.label_acc;
     }
     wide_quantise_kernel<uint16_t><<<dim3((P + 255) / 256, B), 256, 0, st>>>(io->ri, io->tm, seg, io->model, w.pos, acc, label_acc, P, K, io->q16);
@@ -4315,28 +4357,6 @@ extern "C" int rpcc_compress_batch_beams(const rpcc_batch_io *io, int B, rpcc_ge
     return run_batch<uint8_t>(io, B, g, M, ground_threshold, acc, ws, (1 << ST_COUNT) - 1, (hipStream_t)stream, beams_dev);
 }
 
-extern "C" int rpcc_contour_encode_wide(const uint16_t *seg, int B, int H, int W, uint8_t *contour_bits, uint16_t *idx_sequence, int32_t *nseq, void *ws, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && seg && contour_bits && idx_sequence && nseq && ws);
-    hipStream_t st = (hipStream_t)stream;
-    const int P = H * W, T = ntiles(P);
-    uint32_t *tile_cnt = codec_layout(ws, B, P, 1).tile_cnt;   // (M places no tile count)
-    contour_count_kernel<uint16_t><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt);
-    tile_scan_kernel<<<B, 256, 0, st>>>(tile_cnt, T, nseq);
-    contour_write_kernel<uint16_t><<<dim3(T, B), 256, 0, st>>>(seg, P, W, T, tile_cnt, contour_bits, idx_sequence);
-    LAUNCH_CHECK();
-    return RPCC_OK;
-}
-extern "C" int rpcc_contour_decode_wide(const uint8_t *contour_bits, const uint16_t *idx_sequence, int B, int H, int W, uint16_t *seg, void *ws, void *stream) {
-    ARG_TRY(B > 0 && B <= RPCC_MAX_BATCH && H > 0 && W > 0 && seg && contour_bits && idx_sequence && ws);
-    hipStream_t st = (hipStream_t)stream;
-    const int P = H * W, T = ntiles(P);
-    uint32_t *tile_cnt = codec_layout(ws, B, P, 1).tile_cnt;   // (M places no tile count)
-    contour_bits_count_kernel<<<dim3(T, B), 256, 0, st>>>(contour_bits, P, T, tile_cnt);
-    tile_scan_kernel<<<B, 256, 0, st>>>(tile_cnt, T, nullptr);
-    recover_map_kernel<uint16_t><<<dim3(T, B), 256, 0, st>>>(contour_bits, idx_sequence, P, T, tile_cnt, seg);
-    LAUNCH_CHECK();
-    return RPCC_OK;
-}
 // ws: rpcc_wide_workspace_bytes(B, P, M, 0) bytes
 extern "C" int rpcc_decode_wide(const uint16_t *seg, const int16_t *q16, const float *model, const float *tm, const double *level_acc, int levels,
                                 const uint8_t *salience, int B, int P, int M, float *ri_rec, float *pc_rec, void *ws, void *stream) {
@@ -4347,10 +4367,7 @@ extern "C" int rpcc_decode_wide(const uint16_t *seg, const int16_t *q16, const f
     int rc;
     // (the per-label counts land in the workspace's key-point counters: the decoder has no use for either)
     if ((rc = wide_order<uint16_t>(seg, nullptr, nullptr, nullptr, B, P, M, w, w.kpn, nullptr, false, st))) return rc;
-    DecodeSteps steps;
-    steps.levels = levels;
-    for (int i = 0; i < 8; i++) steps.acc[i] = i < (levels ? levels : 1) ? level_acc[i] : 0.0;
-    wide_decode_kernel<uint16_t><<<dim3((P + 255) / 256, B), 256, 0, st>>>(seg, q16, model, tm, w.pos, salience, steps, P, M + 2, ri_rec, pc_rec);
+    wide_decode_kernel<uint16_t><<<dim3((P + 255) / 256, B), 256, 0, st>>>(seg, q16, model, tm, w.pos, salience, decode_steps(level_acc, levels), P, M + 2, ri_rec, pc_rec);
     LAUNCH_CHECK();
     return RPCC_OK;
 }
@@ -4389,7 +4406,7 @@ static int run_labels(const rpcc_labels_io *io, int B, rpcc_geom g, int M, float
     int rc;
     // The intake accumulates the point model's sums and flags over a frame's tiles: they are cleared ahead of it (the one thing a kernel cannot
     // do for itself); the key-point counters are cleared by the intake, the tile counts and notes are plain stores.
-    if (point) HIP_TRY(hipMemsetAsync(l.L.sums, 0, (size_t)((char *)l.L.hist - (char *)l.L.sums), st));
+    if (point) HIP_TRY(hipMemsetAsync(l.L.sums, 0, l.L.clear_bytes(), st));
     const ZeroRange zero = {reinterpret_cast<uint32_t *>(l.kpn), nu ? B * K : 0};
     const bool vec = hist_vec(P, seg, point ? io->ri : nullptr) && aligned16(io->labels);
     const size_t sh = hist_lds_bytes(KP, point);
@@ -4398,21 +4415,9 @@ static int run_labels(const rpcc_labels_io *io, int B, rpcc_geom g, int M, float
     else       { if (vec) LABELS_IN(true, false); else LABELS_IN(false, false); }
 #undef LABELS_IN
     LAUNCH_CHECK();
-    if (point) {   // the sums came with the labels, and so did the tile counts: the scan alone
-        if ((rc = launch_point_model(io->ri, seg, io->ground, B, P, M, io->model, io->counts, io->nnz, ws, st, true, true, true))) return rc;
-    } else {
-        if ((rc = launch_label_scan(seg, B, P, M, io->counts, io->nnz, ws, st, true, true))) return rc;
-        if ((rc = launch_label_order(io->ri, io->tm, seg, B, P, M, ws, l.extra, st))) return rc;
-        if ((rc = launch_plane_fits(io->tm, io->ground, B, P, M, io->plane_cos_cut, (uint32_t)io->plane_seed, io->frame_ids, io->model, io->counts, ws,
-                                    l.extra, st))) return rc;
-    }
-    if (nu) {
-        if ((rc = launch_features(io->ri, seg, B, g.H, g.W, nu->feature_region, nu->segments, nu->sharp_num, nu->less_sharp_num, nu->flat_num, nullptr,
-                                  io->key_point_map, st, l.kpn, K))) return rc;
-        if ((rc = launch_salience_levels<L>(io->counts, l.kpn, B, M, salience_params(nu->levels, nu->level_kp_num, nu->level_acc, nu->ground_level),
-                                            io->salience, l.label_acc, st))) return rc;
-    }
-    if ((rc = launch_predict_quantize(io->ri, io->tm, seg, io->model, acc, nu ? l.label_acc : nullptr, nullptr, B, P, M, io->q16, nullptr, nullptr, ws, st))) return rc;
+    // the tile counts came with the labels, and so did the point model's sums: the scan alone (no epoch: this entry has no projection)
+    const BatchTail t = batch_tail(io, B, g, M, acc, ws, l.extra, l.kpn, l.label_acc, nullptr, TABLE_COUNTED);
+    if ((rc = tail_labels<L>(t, st)) || (rc = tail_planes(t, st)) || (rc = tail_quantise<L>(t, st))) return rc;
     labels_refuse_kernel<L><<<dim3(T, B), 256, 0, st>>>(io->max_label, l.tile_bad, P, M, T, io->status, seg, io->model, io->counts, io->q16, io->nnz,
                                                         nu ? io->salience : nullptr, nu ? io->key_point_map : nullptr);
     LAUNCH_CHECK();
@@ -4423,10 +4428,7 @@ extern "C" int rpcc_compress_batch_labels(const rpcc_labels_io *io, int B, rpcc_
     ARG_TRY(io != nullptr && ws != nullptr && B > 0 && B <= RPCC_MAX_BATCH && M > 0 && M <= RPCC_MAX_CLUSTERS_MID && g.H > 1 && g.W > 0);
     ARG_TRY(io->ri && io->tm && io->ground && io->labels && io->max_label && io->seg && io->model && io->counts && io->q16 && io->nnz && io->status);
     ARG_TRY(io->model_method == 0 || io->model_method == 1);
-    if (io->nonuniform) {
-        const rpcc_nonuniform_cfg *nu = io->nonuniform;
-        ARG_TRY(io->salience && io->key_point_map && nu->levels >= 1 && nu->levels <= 8 && nu->ground_level >= 0 && nu->ground_level < nu->levels);
-    }
+    ARG_TRY(nonuniform_ok(io->nonuniform, io->salience, io->key_point_map));
     if (M <= RPCC_MAX_CLUSTERS) return run_labels<uint8_t>(io, B, g, M, acc, ws, (hipStream_t)stream);
     return run_labels<uint16_t>(io, B, g, M, acc, ws, (hipStream_t)stream);
 }
@@ -4469,9 +4471,7 @@ static int decompress_entry(const uint8_t *contour_bits, const uint16_t *idx_seq
     stream_status_kernel<<<B, 256, 0, st>>>(l.tile_cnt, l.tile_max, l.sal_max, payload_len, entropy_status, levels, P, K, T, l.pre);
     recover_map_gated_kernel<L><<<dim3(T, B), 256, 0, st>>>(contour_bits, idx_sequence, P, T, l.tile_cnt, l.pre, seg);
     LAUNCH_CHECK();
-    DecodeSteps steps;
-    steps.levels = levels;
-    for (int i = 0; i < 8; i++) steps.acc[i] = i < (levels ? levels : 1) ? level_acc[i] : 0.0;
+    const DecodeSteps steps = decode_steps(level_acc, levels);
     const StreamGate gate = {l.pre, l.nnz, payload_len, status, seg};
     int rc;
     if constexpr (wide) {
@@ -4482,9 +4482,8 @@ static int decompress_entry(const uint8_t *contour_bits, const uint16_t *idx_seq
     } else {
         const int KP = kpad(M);
         const WsLayout wl = ws_layout(l.dec, B, P, M);
-        HIP_TRY(hipMemsetAsync(wl.sums, 0, (size_t)((char *)wl.hist - (char *)wl.sums), st));
         // the label histogram the decoder consumes also counts the pixels whose label is not 1 (check 8)
-        if ((rc = launch_hist_scan(nullptr, seg, nullptr, B, P, M, wl, nullptr, nullptr, l.nnz, st))) return rc;
+        if ((rc = launch_point_model<uint8_t>(nullptr, seg, nullptr, B, P, M, nullptr, nullptr, l.nnz, l.dec, st))) return rc;
         decode_gated_kernel<<<dim3(T, B), 256, decode_lds_bytes(KP), st>>>(seg, q16, model, tm, wl.hist, salience, steps, P, M, KP, T, ri_rec, pc_rec, gate);
     }
     LAUNCH_CHECK();

@@ -119,15 +119,15 @@ def fps_pick_list(N, lists, aligned=True, brute=False):
 
 
 def fused_refuses(H, W, frames, flags=0):
-    """check_batch_io (rpcc_hip.hip:3712-3713): the one-pass kernel reads 16 bytes at frame bases, so a frame that takes it needs P % 4 == 0."""
+    """check_batch_io (rpcc_hip.hip): the one-pass kernel reads 16 bytes at frame bases, so a frame that takes it needs P % 4 == 0."""
     return (H * W) % 4 != 0 and fps_pick_range(H, W, frames, flags, True, True)[0] == ONE_PASS
 
 
 def mixed_fps_picks(groups):
-    """mixed_fps (rpcc_hip.hip:3769-3795).  groups: [(H, W, frames, quads16)] of tile-pruned, untimed groups -> per group
+    """mixed_fps (rpcc_hip.hip).  groups: [(H, W, frames, quads16)] of tile-pruned, untimed groups -> per group
     (shares the common launch, pick).  The groups whose pick for a launch of ALL the frames is the planar kernel share one
     fps_regtab_planar_multi_kernel of that thread count, each with its own EDGE flag; every other group runs alone, with the pick of its
-    own frame count (run_stage, rpcc_hip.hip:3670-3672)."""
+    own frame count (run_stage's ST_FPS case, rpcc_hip.hip)."""
     total = sum(g[2] for g in groups)
     out = []
     for (H, W, frames, quads16) in groups:

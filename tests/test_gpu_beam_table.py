@@ -60,15 +60,15 @@ def _project(env, frames, va, H, W, rows16=False, **kw):
     return ops.project(_to(env, pts), _to(env, _offsets(frames)), geom, beams=ops.beam_index(va, env["dev"]), **kw).cpu().numpy()
 
 
-def _frames4(env):
-    """Four sweeps from the example: as stored, every second point, rotated about z, its tail."""
-    if "frames4" not in env["cache"]:
+def _frames4(env, W=2000):
+    """Four sweeps from the example: as stored, every second point, rotated about z, its tail; and their reference image at width W."""
+    if ("frames4", W) not in env["cache"]:
         x = env["xyz"]
         c, s = np.float32(math.cos(0.1)), np.float32(math.sin(0.1))
         rot = np.stack([c * x[:, 0] - s * x[:, 1], s * x[:, 0] + c * x[:, 1], x[:, 2]], 1).astype(np.float32)
         fr = [x, np.ascontiguousarray(x[::2]), rot, np.ascontiguousarray(x[30000:])]
-        env["cache"]["frames4"] = (fr, R.project_batch(np.concatenate(fr), _offsets(fr), env["va"], HFOV, 64, 2000))
-    return env["cache"]["frames4"]
+        env["cache"]["frames4", W] = (fr, R.project_batch(np.concatenate(fr), _offsets(fr), env["va"], HFOV, 64, W))
+    return env["cache"]["frames4", W]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -242,19 +242,22 @@ def test_past_the_grid_scratch_of_exact_size(env, pattern):
 ACC, THR, SEED = 0.04, 0.1, 3
 
 
-@pytest.mark.parametrize("variant", ("uniform_point", "nonuniform_plane"))
-@pytest.mark.parametrize("M", (100, 300))
+@pytest.mark.parametrize("variant", ("uniform_point", "nonuniform_plane", "nonuniform_point", "uniform_plane"))
+@pytest.mark.parametrize("M", (100, 300, 254))
 def test_fused_batch(env, M, variant):
+    """100 and 300 clusters (byte and uint16 labels) on the shipped 64 x 2000 image; 254 clusters on 64 x 3080 -- the table indexes rows, the
+    width is free --: 193 scatter tiles, the last of 512 pixels, x 128 words, one tile past count_scan_kernel's LDS budget."""
     ops, torch, dev = env["ops"], env["torch"], env["dev"]
-    frames, want_ri = _frames4(env)
-    B, H, W = 4, 64, 2000
+    B, H, W = 4, 64, 3080 if M == 254 else 2000
+    frames, want_ri = _frames4(env, W)
+    geom = ops.make_geom(H, W, HFOV, 0.0, 0.0)
     tm = _to(env, ops.transform_map(H, W, HFOV, 0.0, 0.0, vertical_angle=env["va"]))
     xyz, offs = _to(env, np.concatenate(frames)), _to(env, _offsets(frames))
-    uniform = variant == "uniform_point"
+    framework, method = variant.split("_")
+    uniform = framework == "uniform"
     nu = None if uniform else ops.nonuniform_cfg(ACC)
-    method = "point" if uniform else "plane"
     fid = [7, 8, 11, 2]
-    buf = ops.BatchBuffers(B, env["geom"], M, dev, max_points=xyz.shape[0], general=not uniform)
+    buf = ops.BatchBuffers(B, geom, M, dev, max_points=xyz.shape[0], general=variant != "uniform_point")
     ground = filled((B, 4), torch.float64, dev, POISON)
     ops.compress_batch(xyz, offs, tm, ground, buf, THR, ACC, ground_seed=SEED, frame_ids=fid, model_method=method, plane_seed=SEED, nonuniform=nu,
                        beams=env["beams"])
@@ -269,7 +272,7 @@ def test_fused_batch(env, M, variant):
     assert np.array_equal(buf.cen_pix.cpu().numpy(), cen_pix.cpu().numpy()) and _beq(buf.centers.cpu().numpy(), centers.cpu().numpy())
     seg = ops.assign(ri, tm, g2, centers)
     assert seg.dtype == buf.seg.dtype and np.array_equal(buf.seg.cpu().numpy(), seg.cpu().numpy())
-    if uniform:
+    if method == "point":
         model, counts = ops.point_model(ri, seg, g2, M)
     else:
         model, counts = ops.plane_model(ri, tm, seg, M, seed=SEED, ground=g2, want_counts=True, frame_ids=fid)

@@ -1,5 +1,5 @@
 """-m gpu: the label counts of the ordered scatter, whichever launch makes them -- count_scan_kernel (the frame's one workgroup counts its
-tiles into LDS and scans them there) or the histogram + scan pair that larger tables keep (launch_hist_scan, r-pcc_amd/csrc/rpcc_hip.hip).
+tiles into LDS and scans them there) or the histogram + scan pair that larger tables keep (launch_point_model, r-pcc_amd/csrc/rpcc_hip.hip).
 
 Seen through the public entries on byte labels: ops.predict_quantize on a caller's integer residual with a step of 1 must leave the residual
 stable-sorted by label without label 1, and nnz = P - (pixels of label 1); ops.decode of that list must put every value back on its pixel.

@@ -24,8 +24,9 @@ def env():
 
 
 def _geom(env, name):
+    """name: a lidar of orc.GEOMS, or a geometry given as such a dict."""
     orc, ops = env["orc"], env["ops"]
-    g = orc.LidarGeom(**orc.GEOMS[name])
+    g = orc.LidarGeom(**(name if isinstance(name, dict) else orc.GEOMS[name]))
     tm = ops.transform_map(g.H, g.W, g.horizontal_FOV, g.vertical_max, g.vertical_min)
     assert np.array_equal(tm, orc.transform_map(g))
     return g, ops.make_geom(g.H, g.W, g.horizontal_FOV, g.vertical_max, g.vertical_min), tm
@@ -1040,12 +1041,14 @@ def test_projection_fast_path_never_disagrees(env, gname):
 
 
 @pytest.mark.parametrize("H,W,M", [(5, 300, 7), (8, 512, 20), (33, 1000, 100), (16, 4000, 50), (128, 2048, 30), (128, 4096, 30),
-                                   (7, 301, 9), (12, 1030, 40), (20, 2051, 60)])   # widths that are no multiple of four: quads at 4-byte alignment, row-end quads by element
+                                   (7, 301, 9), (12, 1030, 40), (20, 2051, 60),   # widths that are no multiple of four: quads at 4-byte alignment, row-end quads by element
+                                   (49, 4016, 254)])   # 193 scatter tiles (the last one of 176 pixels) x 128 words: one tile past count_scan_kernel's LDS budget
 def test_odd_geometries_fused(env, H, W, M):
     """Fused entry (ground fit inside) on image shapes that are no multiple of any tile size the kernels use
     (4x32 FPS / assign tiles, 1024-pixel scatter tiles, 32768-pixel projection bands, RANSAC chunks), with
-    cluster counts from 7 to 100, and on images of 8 record bins (the binned projection's limit) and of 16 (the fused entry
-    then projects with device atomics and a separate initialisation launch): every output equals the oracle's."""
+    cluster counts from 7 to 254, on images of 8 record bins (the binned projection's limit) and of 16 (the fused entry
+    then projects with device atomics and a separate initialisation launch), and on one whose tile x label table at 254 clusters is past
+    the one-launch count's LDS budget (histogram + scan as two launches): every output equals the oracle's."""
     torch, ops, orc, synth = env["torch"], env["ops"], env["orc"], env["synth"]
     g = orc.LidarGeom(H, W, 360.0, 3.0, -25.0)
     tm = ops.transform_map(g.H, g.W, g.horizontal_FOV, g.vertical_max, g.vertical_min)
@@ -1070,6 +1073,7 @@ def test_odd_geometries_fused(env, H, W, M):
         assert _beq(buf.ri[i].cpu().numpy(), o["range_image"])
         assert np.array_equal(buf.cen_pix[i].cpu().numpy(), o["fps_pix"]), (H, W, i)
         assert np.array_equal(buf.seg[i].cpu().numpy(), o["seg_idx"].astype(np.uint8)), (H, W, i)
+        assert _beq(buf.model[i, : o["model_param"].shape[0]].cpu().numpy(), o["model_param"].astype(np.float32)), (H, W, i)
         assert n == o["q"].shape[0] and np.array_equal(buf.q16[i, :n].cpu().numpy(), o["q"].astype(np.int16))
     # the sparse frame: projection and ground fit still agree (FPS with fewer candidates than clusters is undefined
     # in the reference -- indices repeat -- so only the stages before it are compared)
@@ -1234,7 +1238,7 @@ def _mixed_groups(env, specs, M=100):
     groups = []
     for k, (name, n, over) in enumerate(specs):
         g, geom, tm = _geom(env, name)
-        gd = orc.GEOMS[name]
+        gd = name if isinstance(name, dict) else orc.GEOMS[name]
         frames = [synth.make_frame(5100 + 31 * k + i, g.H, g.W, vmax_deg=gd["vmax_deg"], vmin_deg=gd["vmin_deg"]).numpy() for i in range(n)]
         offs = np.zeros(n + 1, np.int64)
         offs[1:] = np.cumsum([f.shape[0] for f in frames])
@@ -1257,7 +1261,14 @@ _MIXED_CASES = {
     "every_group_different": lambda ops: [("Velodyne32E", 2, dict(ground_seed=-1)), ("VelodyneVLP16", 3, dict(fps_bruteforce=True, model_method="plane")),
                                           ("Velodyne64E", 2, dict(nonuniform=ops.nonuniform_cfg(0.04))), ("VelodyneVLP16", 2, dict(fps_fma=1))],
     "one_group": lambda ops: [("Velodyne32E", 3, dict(model_method="plane"))],
+    # 254 clusters and one group of 193 scatter tiles (P % 1024 = 176): that group's tile x label table is one tile past count_scan_kernel's
+    # LDS budget, so the call counts EVERY group with model_hist_multi_kernel + model_scan_multi_kernel; all four model / framework pairs
+    "past_the_lds_budget_a": lambda ops: [(_BIG_GEOM, 2, dict(model_method="plane", plane_seed=5, nonuniform=ops.nonuniform_cfg(0.04))), ("VelodyneVLP16", 2, {})],
+    "past_the_lds_budget_b": lambda ops: [("VelodyneVLP16", 2, dict(model_method="plane", plane_seed=5)), (_BIG_GEOM, 2, dict(nonuniform=ops.nonuniform_cfg(0.04)))],
+    "past_the_lds_budget_c": lambda ops: [(_BIG_GEOM, 2, dict(model_method="plane", plane_seed=5)), ("VelodyneVLP16", 2, dict(nonuniform=ops.nonuniform_cfg(0.04)))],
 }
+_BIG_GEOM = dict(H=49, W=4016, hfov_deg=360, vmax_deg=3.0, vmin_deg=-25.0)
+_MIXED_M = dict.fromkeys(("past_the_lds_budget_a", "past_the_lds_budget_b", "past_the_lds_budget_c"), 254)   # (every other case: 100)
 
 
 @pytest.mark.gpu
@@ -1265,13 +1276,14 @@ _MIXED_CASES = {
 def test_compress_batch_mixed_equals_the_groups_alone(env, case):
     """rpcc_compress_batch_mixed (variable H x W inside one call; the ground RANSAC, FPS and plane-fit launches shared by the groups):
     every output buffer of every group is bit for bit what rpcc_compress_batch gives for that group alone -- which the tests above
-    hold to the oracle -- for the uniform / point and non-uniform / plane paths, for groups whose settings differ, and for one group."""
+    hold to the oracle -- for the uniform / point and non-uniform / plane paths, for groups whose settings differ, for one group, and for
+    a call whose label table is past the one-launch count's LDS budget (that group is held to the oracle here)."""
     torch, ops = env["torch"], env["ops"]
-    specs = _MIXED_CASES[case](ops)
-    alone = _mixed_groups(env, specs)
+    specs, M = _MIXED_CASES[case](ops), _MIXED_M.get(case, 100)
+    alone = _mixed_groups(env, specs, M)
     for a in alone:
         ops.compress_batch(**a)
-    mixed = _mixed_groups(env, specs)
+    mixed = _mixed_groups(env, specs, M)
     ops.compress_batch_mixed(mixed)
     torch.cuda.synchronize()
     for k, (a, m) in enumerate(zip(alone, mixed)):
@@ -1284,6 +1296,19 @@ def test_compress_batch_mixed_equals_the_groups_alone(env, case):
         assert all(np.array_equal(qa[i, :nz[i]], qm[i, :nz[i]]) for i in range(ba.B)), (case, k)
         if a.get("nonuniform") is not None:
             assert np.array_equal(ba.salience.cpu().numpy(), bm.salience.cpu().numpy()) and np.array_equal(ba.key_point_map.cpu().numpy(), bm.key_point_map.cpu().numpy())
+        if isinstance(specs[k][0], dict):      # no other test holds a group of this size and cluster count to the oracle: labels, rows, integers, levels
+            orc, g, tm = env["orc"], _geom(env, specs[k][0])[0], a["tm"].cpu().numpy()
+            xyz, offs, fid, gms = a["xyz"].cpu().numpy(), a["offsets"].cpu().numpy(), a["frame_ids"].cpu().numpy(), m["ground"].cpu().numpy()
+            plane = a.get("model_method", "point") == "plane"
+            for i in range(bm.B):
+                o = orc.compress_frame(xyz[offs[i]:offs[i + 1]], g, tm, gms[i], dict(orc.DEFAULT_CFG, cluster_num=M, plane_angle_threshold=75),
+                                       uniform=a.get("nonuniform") is None, plane=dict(angle_deg=75, seed=5, frame=int(fid[i])) if plane else None)
+                mp, n = np.asarray(o["model_param"]).astype(np.float32), int(nz[i])
+                assert np.array_equal(bm.seg[i].cpu().numpy(), o["seg_idx"].astype(np.uint8)), (case, k, i)
+                assert _beq(bm.model[i, :mp.shape[0]].cpu().numpy(), mp), (case, k, i)
+                assert n == o["q"].shape[0] and np.array_equal(qm[i, :n], o["q"].astype(np.int16)), (case, k, i)
+                if a.get("nonuniform") is not None:
+                    assert np.array_equal(bm.salience[i, :o["salience"].shape[0]].cpu().numpy(), o["salience"].astype(np.uint8)), (case, k, i)
 
 
 @pytest.mark.gpu

@@ -31,6 +31,7 @@ BUNZIP2_SRC, BUNZIP2_DEPS, BUNZIP2_LIB = _side_library("csrc_bunzip2", "bunzip2_
 BZIP2_SRC, BZIP2_DEPS, BZIP2_LIB = _side_library("csrc_bzip2", "bzip2_kernels.hip", "rpcc_bzip2.h", "librpcc_bzip2.so")   # bzip2 encoder
 FILTER_SRC, FILTER_DEPS, FILTER_LIB = _side_library("csrc_filter", "radius_filter.hip", "rpcc_filter.h", "librpcc_filter.so")   # radius outlier removal
 RANS_SRC, RANS_DEPS, RANS_LIB = _side_library("csrc_rans", "rans_kernels.hip", "rpcc_rans.h", "librpcc_rans.so")   # chunk-parallel rANS back-end
+RECORDS_SRC, RECORDS_DEPS, RECORDS_LIB = _side_library("csrc_records", "records_kernels.hip", "rpcc_records.h", "librpcc_records.so")   # NCLT record unpack
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -121,6 +122,11 @@ def build_rans(force=False, verbose=False):
     return _hipcc(RANS_SRC, RANS_LIB, RANS_DEPS, force, verbose)
 
 
+def build_records(force=False, verbose=False):
+    """librpcc_records.so: the NCLT record unpack kernel (csrc_records/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(RECORDS_SRC, RECORDS_LIB, RECORDS_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -135,6 +141,7 @@ def build(force=False, verbose=False):
     build_bzip2(force, verbose)
     build_filter(force, verbose)
     build_rans(force, verbose)
+    build_records(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

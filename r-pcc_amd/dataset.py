@@ -1,13 +1,16 @@
 """Data access -- mirror of the reference's dataset/__init__.py:52-69 (build_dataset) and
 dataset/dataset.py (DatasetTemplate): .bin / .npy / .txt readers, the lidar registry and the
 range-image loader.  use_radius_outlier_removal (dataset/dataset.py:29-35, Open3D's remove_radius_outlier(nb_points=3,
-radius=1)) runs on the GPU through outlier.remove_radius_outlier (librpcc_filter.so).  Dataset-specific
-converters (dataset/datasets/*.py) and the Open3D formats (.ply/.pcd read, .pcd write) are out of scope."""
+radius=1)) runs on the GPU through outlier.remove_radius_outlier (librpcc_filter.so).  Of the reference's
+dataset-specific classes (dataset/datasets/*.py) the one with logic of its own is here: NcltDataset reads NCLT's velodyne_sync
+records (nclt_dataset.py:36-63) through records.unpack_host, bit-equal to the reference's preprocessing; the
+other three only call Open3D on .pcd files.  The Open3D formats (.ply/.pcd read, .pcd write) are out of scope."""
 import os
 import struct
 
 import numpy as np
 
+from . import records
 from .transformer import PCTransformer
 
 _CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lidar_cfg")
@@ -24,7 +27,9 @@ __dataset_cfg__ = {
     "NCLT": __lidar_cfg__["Velodyne32E"],
     "Oxford": __lidar_cfg__["Velodyne32E"],
     "HKUSTCampus": __lidar_cfg__["VelodyneVLP16"],
+    "NCLT_sync": __lidar_cfg__["Velodyne32E"],      # NCLT as downloaded: velodyne_sync records (point_format "nclt"); "NCLT" reads the preprocessed float .bin
 }
+__dataset_point_format__ = {"NCLT_sync": "nclt"}
 
 
 class DatasetTemplate:
@@ -124,12 +129,32 @@ class DatasetTemplate:
             assert False, "File type not correct."
 
 
+class NcltDataset(DatasetTemplate):
+    """dataset/datasets/nclt_dataset.py: the files are NCLT velodyne_sync records (8 bytes per point, records.py), not float rows.
+    load_data is load_original_utf8_data in the dtype the reference's preprocessing stores (float32); load_rows adds the record's
+    intensity byte as the fourth column, where the preprocessing writes 0.  A record file ends in .bin like a float file: the format is
+    this class, never guessed from the name or the size."""
+
+    @staticmethod
+    def load_data(file):
+        return NcltDataset.load_rows(file)[:, :3]
+
+    @staticmethod
+    def load_rows(file):
+        return records.unpack_host(records.read_records(file))
+
+
 def build_dataset(datalist=None, dataset_name=None, lidar_type=None, use_radius_outlier_removal=False, device="cuda:0",
-                  channel_distribute_csv=None):
+                  channel_distribute_csv=None, point_format=None):
     """dataset/__init__.py:52-69.  channel_distribute_csv: the lidar's per-beam elevation table (DatasetTemplate.__init__ of the reference
-    passes it to PCTransformer; its registry never sets it)."""
+    passes it to PCTransformer; its registry never sets it).  point_format: None -- float points, by the file's extension --, or "nclt":
+    NcltDataset, whose files are velodyne_sync records (the registry name "NCLT_sync" implies it)."""
+    records.check_point_format(point_format)
+    if dataset_name is not None and point_format is None:
+        point_format = __dataset_point_format__.get(dataset_name)
+    cls = NcltDataset if point_format == "nclt" else DatasetTemplate
     if dataset_name is not None:
-        return DatasetTemplate(datalist, __dataset_cfg__[dataset_name], channel_distribute_csv, use_radius_outlier_removal, device)
+        return cls(datalist, __dataset_cfg__[dataset_name], channel_distribute_csv, use_radius_outlier_removal, device)
     if lidar_type is not None:
-        return DatasetTemplate(datalist, __lidar_cfg__[lidar_type], channel_distribute_csv, use_radius_outlier_removal, device)
-    return DatasetTemplate(datalist, dataset_cfg=None, use_radius_outlier_removal=use_radius_outlier_removal)
+        return cls(datalist, __lidar_cfg__[lidar_type], channel_distribute_csv, use_radius_outlier_removal, device)
+    return cls(datalist, dataset_cfg=None, use_radius_outlier_removal=use_radius_outlier_removal)

@@ -21,19 +21,19 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, records
 from .compress_utils import BatchPayload, pack_bitstream, pack_frames  # noqa: F401
 from .utils import available_cpus
 
 
 class _Slot:
-    def __init__(self, bc, B, cap_points, device, cols=3):
+    def __init__(self, bc, B, cap_points, device, cols=3, nclt=False):
         P, K = bc.T.H * bc.T.W, bc.M + 2
         self.B, self.cap, self.cols = B, int(cap_points), int(cols)    # cols: floats per point in the staging / device input (3 or 4)
-        self.xyz_pin = torch.empty((self.cap, self.cols), dtype=torch.float32).pin_memory()
+        self.nclt = bool(nclt)      # ingest="nclt": records are staged and sent (8 bytes per point); xyz_dev [cap,4] is filled on the device
+        self._point_buffers(device)
         self.offs_pin = torch.zeros((B + 1,), dtype=torch.int64).pin_memory()
         self.fid_pin = torch.zeros((B,), dtype=torch.int64).pin_memory()
-        self.xyz_dev = torch.empty((self.cap, self.cols), dtype=torch.float32, device=device)
         self.offs_dev = torch.zeros((B + 1,), dtype=torch.int64, device=device)
         self.fid_dev = torch.zeros((B,), dtype=torch.int64, device=device)
         self.ground = torch.zeros((B, 4), dtype=torch.float64, device=device)
@@ -65,10 +65,20 @@ class _Slot:
         pixel): the point-count-sized buffers are replaced.  Only called while the slot is idle (nothing of it in flight);
         the projection workspace inside BatchBuffers follows by itself (ops.compress_batch)."""
         self.cap = int(cap_points)
-        self.xyz_pin = torch.empty((self.cap, self.cols), dtype=torch.float32).pin_memory()
-        self.xyz_dev = torch.empty((self.cap, self.cols), dtype=torch.float32, device=device)
+        self._point_buffers(device)
         self.qp = torch.empty((self.cap,), dtype=torch.int16, device=device)
         self.qp_pin = torch.empty((self.cap,), dtype=torch.int16).pin_memory()
+
+    def _point_buffers(self, device):
+        """The input buffers of cap points: the pinned staging and its device mirror -- floats, or with nclt the records, whose rows
+        exist on the device only (no pinned float staging)."""
+        if self.nclt:
+            self.xyz_pin = None
+            self.rec_pin = torch.empty((self.cap, records.RECORD_BYTES), dtype=torch.uint8).pin_memory()
+            self.rec_dev = torch.empty((self.cap, records.RECORD_BYTES), dtype=torch.uint8, device=device)
+        else:
+            self.xyz_pin = torch.empty((self.cap, self.cols), dtype=torch.float32).pin_memory()
+        self.xyz_dev = torch.empty((self.cap, self.cols), dtype=torch.float32, device=device)
 
 
 class StreamingCompressor:
@@ -82,9 +92,13 @@ class StreamingCompressor:
                              [N,4] arrays (one contiguous copy each) or .bin PATHS, which are read straight into the pinned
                              slot (file -> pinned buffer -> DMA, no pass over the points on the host); the kernels read
                              the rows with a 16-byte stride (rpcc_batch_io.point_stride_bytes = 16).  16 bytes per point
-                             cross the link instead of 12."""
-        assert ingest in ("xyz", "rows")
-        if bc.intensity_scale is not None and ingest != "rows":
+                             cross the link instead of 12.
+                   "nclt" -- NCLT velodyne_sync records (records.py: 8 bytes per point, the intensity byte among them): frames are
+                             record-file PATHS, read straight into a pinned record buffer, or uint8 [N,8] arrays; the records cross
+                             the link and records.unpack (librpcc_records.so) writes the stored rows on the device, on the compute
+                             stream in front of the batch call.  8 bytes per point cross the link; intensity_scale is allowed."""
+        assert ingest in ("xyz", "rows", "nclt")
+        if bc.intensity_scale is not None and ingest == "xyz":
             raise ValueError('StreamingCompressor: a BatchCompressor with intensity_scale needs ingest="rows" (the fourth column must reach the device); '
                              'ingest="xyz" drops it')
         self.ingest = ingest
@@ -104,7 +118,7 @@ class StreamingCompressor:
         self.enq_pool = ThreadPoolExecutor(1)
         self.side_stream = torch.cuda.Stream(device=self.device)     # late copies that must not queue behind the next batch
         self.seq_eager = max(1024, self.B * P // 16)                # index-sequence entries fetched with the batch (typical: P/20 per frame)
-        self.slots = [_Slot(bc, self.B, self.cap, self.device, cols=4 if ingest == "rows" else 3) for _ in range(self.depth)]
+        self.slots = [_Slot(bc, self.B, self.cap, self.device, cols=3 if ingest == "xyz" else 4, nclt=ingest == "nclt") for _ in range(self.depth)]
         self.prof = {"stage": 0.0, "enqueue": 0.0, "collect": 0.0, "drain": 0.0}   # host seconds per phase (diagnostics)
         self.stage_chunks = max(1, min(self.B, 16))      # staging tasks per batch: a few MB each (more, smaller tasks are slower)
 
@@ -112,15 +126,18 @@ class StreamingCompressor:
     def _stage(self, slot, frames, frame_ids):
         n = len(frames)
         assert 0 < n <= self.B
-        rows = self.ingest == "rows"
+        nclt = self.ingest == "nclt"
+        rows = self.ingest == "rows" or nclt      # whole stored elements, files read in place: float rows, or records
+        elem = records.RECORD_BYTES if nclt else 16     # bytes of one
         if rows:
             def rows_of(f):
                 if not isinstance(f, (str, os.PathLike)):
-                    return f.shape[0]
+                    return records.as_records(f).shape[0] if nclt else f.shape[0]
                 nbytes = os.path.getsize(f)
-                if nbytes % 16:   # the reference's np.fromfile(...).reshape(-1, 4) raises on such a file (dataset/dataset.py:48-50), and so does ingest="xyz"
-                    raise ValueError("%s: %d bytes is no whole number of (x, y, z, intensity) float32 rows" % (f, nbytes))
-                return nbytes // 16
+                if nbytes % elem:   # the reference's np.fromfile(...).reshape(-1, 4) raises on such a file (dataset/dataset.py:48-50), and so does ingest="xyz"
+                    raise ValueError("%s: %d bytes is no whole number of %s" % (f, nbytes, "%d-byte NCLT records" % elem if nclt else
+                                                                                 "(x, y, z, intensity) float32 rows"))
+                return nbytes // elem
             sizes = np.fromiter((rows_of(f) for f in frames), dtype=np.int64, count=n)
         else:
             sizes = np.fromiter((f.shape[0] for f in frames), dtype=np.int64, count=n)
@@ -130,7 +147,7 @@ class StreamingCompressor:
         if offs[n] > slot.cap:      # the slot is idle here (run() drained it): replace its point-sized buffers, with headroom
             slot.grow(int(offs[n]) + int(offs[n]) // 4, self.device)
             self.grown += 1
-        dst = slot.xyz_pin.numpy()
+        dst = (slot.rec_pin if nclt else slot.xyz_pin).numpy()
 
         def copy(lo, hi):
             for i in range(lo, hi):
@@ -139,7 +156,7 @@ class StreamingCompressor:
                     dst[offs[i]:offs[i + 1]] = f[:, :3]   # .bin rows are (x, y, z, intensity): the strided copy drops the 4th column (ingest="rows" keeps it)
                 elif isinstance(f, (str, os.PathLike)):       # the file's bytes land in the pinned slot: no pass over the points at all
                     with open(f, "rb", buffering=0) as fh:
-                        if os.fstat(fh.fileno()).st_size != 16 * int(offs[i + 1] - offs[i]):   # grew or shrank since it was sized
+                        if os.fstat(fh.fileno()).st_size != elem * int(offs[i + 1] - offs[i]):   # grew or shrank since it was sized
                             raise ValueError("%s changed size while the batch was staged" % f)
                         if offs[i + 1] == offs[i]:
                             continue
@@ -152,6 +169,8 @@ class StreamingCompressor:
                             got += m
                         if got != len(view):
                             raise ValueError("%s changed size while it was read" % f)
+                elif nclt:
+                    dst[offs[i]:offs[i + 1]] = records.as_records(f)      # (raises for what is no uint8 [N,8] array)
                 else:
                     assert f.ndim == 2 and f.shape[1] == 4 and f.dtype == np.float32, 'ingest="rows" takes [N,4] float32 rows or .bin paths'
                     dst[offs[i]:offs[i + 1]] = f           # contiguous rows: one memcpy
@@ -170,12 +189,17 @@ class StreamingCompressor:
         bc = self.bc
         torch.cuda.set_device(self.device)      # (runs on the enqueue thread)
         with torch.cuda.stream(self.copy_stream):
-            slot.xyz_dev[:npts].copy_(slot.xyz_pin[:npts], non_blocking=True)
+            if slot.nclt:
+                slot.rec_dev[:npts].copy_(slot.rec_pin[:npts], non_blocking=True)
+            else:
+                slot.xyz_dev[:npts].copy_(slot.xyz_pin[:npts], non_blocking=True)
             slot.offs_dev.copy_(slot.offs_pin, non_blocking=True)
             slot.fid_dev.copy_(slot.fid_pin, non_blocking=True)
             slot.h2d_done.record(self.copy_stream)
         with torch.cuda.stream(self.compute_stream):
             self.compute_stream.wait_event(slot.h2d_done)
+            if slot.nclt:     # the records -> the stored rows run_batch reads (16-byte stride), in front of it on this stream
+                records.unpack(slot.rec_dev[:npts], out=slot.xyz_dev[:npts])
             # (FPS: one ops.compress_batch; DBSCAN: projection, ground fit, dbscan_segment, ops.compress_batch_labels)
             bc.run_batch(slot.xyz_dev[:npts], slot.offs_dev, slot.ground, slot.buf, frame_ids=slot.fid_dev)
             bits, seq, nseq = ops.contour_encode(slot.buf.seg, bc.M, ws=slot.codec_ws)

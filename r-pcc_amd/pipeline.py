@@ -19,8 +19,12 @@ class BatchCompressor:
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
                  model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
                  device_entropy=False, device_bzip2=False, segment_method="FPS", DBSCAN_eps=1.5, max_labels=None,
-                 radius_outlier_removal=None, rans_delta=False, intensity_scale=None):
-        """intensity_scale (None: off, and no byte of any container changes): frames are [N,>=4] rows (x, y, z, intensity); after the
+                 radius_outlier_removal=None, rans_delta=False, intensity_scale=None, point_format=None):
+        """point_format (None: float points, and nothing changes): "nclt" -- compress / submit take every frame as uint8 [N,8] NCLT
+        velodyne_sync records (records.py); 8 bytes per point go up, records.unpack (librpcc_records.so) makes the stored rows on the
+        device and run_batch reads them like any [N,4] rows, so every other option works behind it; with intensity_scale the payload
+        is made of the records' intensity bytes (at scale 1 the byte itself).
+        intensity_scale (None: off, and no byte of any container changes): frames are [N,>=4] rows (x, y, z, intensity); after the
         batch call one ops.intensity_encode runs on the same point tensor and the batch's range images, and every container gets the
         'intensity' trailer (compress_utils.pack_bitstream), byte for byte the per-frame path's.  Independent of the segmentation.
         rans_delta (basic_compressor 'rans' only): the residual stream goes through the delta filter, as BasicCompressor(rans_delta=True)
@@ -32,6 +36,8 @@ class BatchCompressor:
         radius_outlier_removal: None, or (nb_points, radius) -- the reference's use_radius_outlier_removal is (3, 1.0): every frame's points go
         through outlier.radius_outlier_mask first and the removed ones enter the projection as NaN, which it skips: the containers are those
         of the compacted frames, with no compaction, no new point count and no read-back in between."""
+        from . import records
+        self.point_format = records.check_point_format(point_format)
         self.outlier = None
         if radius_outlier_removal is not None:
             nb_points, radius = radius_outlier_removal
@@ -208,6 +214,8 @@ class BatchCompressor:
 
     def _upload(self, frames, ground=None):
         """Host arrays of a batch -> device (xyz, offsets, ground or None) on the current stream."""
+        if self.point_format == "nclt":
+            return self._upload_records(frames, ground)
         offs = np.zeros(len(frames) + 1, np.int64)
         offs[1:] = np.cumsum([f.shape[0] for f in frames])
         cols = 3 if self.intensity_scale is None else 4     # (with intensity the rows go up as stored: the kernels read them with stride 16)
@@ -216,6 +224,19 @@ class BatchCompressor:
         xyz = torch.from_numpy(np.ascontiguousarray(np.concatenate([f[:, :cols] for f in frames]), dtype=np.float32)).to(self.device)
         gnd = None if ground is None else torch.from_numpy(np.asarray(ground, np.float64).reshape(-1, 4)).to(self.device)
         return xyz, torch.from_numpy(offs).to(self.device), gnd, int(offs[-1])
+
+    def _upload_records(self, frames, ground=None):
+        """point_format "nclt": the frames' records go up as they are, 8 bytes per point, and records.unpack writes the stored rows
+        on the current stream -> what _upload returns, the rows [sum N,4] in the place of xyz."""
+        from . import records
+        recs = [records.as_records(f) for f in frames]
+        offs = np.zeros(len(recs) + 1, np.int64)
+        offs[1:] = np.cumsum([r.shape[0] for r in recs])
+        host = np.concatenate(recs) if recs else np.zeros((0, records.RECORD_BYTES), np.uint8)
+        with torch.cuda.device(self.device):
+            rows = records.unpack(torch.from_numpy(host).to(self.device))
+        gnd = None if ground is None else torch.from_numpy(np.asarray(ground, np.float64).reshape(-1, 4)).to(self.device)
+        return rows, torch.from_numpy(offs).to(self.device), gnd, int(offs[-1])
 
     def _payload(self, n, npts, xyz, dev_out):
         """The two variable-length 16-bit streams leave the device with the frames back to back (rpcc_pack_payload), not as the padded
@@ -333,6 +354,9 @@ class MixedBatchCompressor:
         if kw.get("radius_outlier_removal") is not None:
             raise NotImplementedError("MixedBatchCompressor: radius_outlier_removal -- the mixed-geometry call takes the points as they are; "
                                       "filter them first (outlier.radius_outlier_mask), or use one BatchCompressor per lidar")
+        if kw.get("point_format") is not None:
+            raise NotImplementedError("MixedBatchCompressor: point_format %r -- the mixed-geometry call takes float points; unpack the "
+                                      "records first (records.unpack), or use one BatchCompressor(point_format=...) per lidar" % (kw["point_format"],))
         tabled = sorted(name for name, t in transformers.items() if getattr(t, "even_dist", True) is False)
         if tabled:
             raise NotImplementedError("MixedBatchCompressor: lidars %s have a per-beam elevation table (channel_distribute_csv) -- the "

@@ -52,6 +52,11 @@ def make_parser(datalist=False):
         p.add_argument("--original_point_cloud", default=None,
                        help="decompress.py --eval: the original point cloud file to compare the reconstruction with.")
     p.add_argument("--lidar", help="lidar type of this point cloud collection.")
+    p.add_argument("--input_format", choices=("float", "nclt"), default="float",
+                   help="the point files read: float -- .bin / .txt / .npy of float values, by extension (default); nclt -- NCLT velodyne_sync "
+                        "records as downloaded (8 bytes per point: uint16 x, y, z, uint8 intensity, uint8 laser), with no preprocessing step. "
+                        "compress tools: the input(s); decompress.py: --original_point_cloud.  A record file also ends in .bin: the format is "
+                        "never guessed.")
     p.add_argument("--channel_distribute_csv", default=None, metavar="FILE",
                    help="per-beam elevation table of the lidar (columns channel, vertical_angle in degrees; row h of the range image = line h), "
                         "for beams that are not evenly spaced: e.g. lidar_cfg/Velodyne_HDL_64E_beams.csv with --lidar Velodyne64E.")
@@ -93,6 +98,11 @@ def make_parser(datalist=False):
                    help="FPS ties between exactly equal distances resolved like the CUDA kernel's reduction tree (default: lowest "
                         "index); sets RPCC_FPS_TIE_CUDA.")
     return p
+
+
+def point_format_of(args):
+    """--input_format as build_dataset / BatchCompressor / StreamingCompressor name it: None (float points) or "nclt"."""
+    return "nclt" if getattr(args, "input_format", "float") == "nclt" else None
 
 
 def apply_fps_mode(args):
@@ -176,7 +186,8 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
     """cluster_num above 254 (labels as uint16): the per-stage mirror classes keep labels in a byte, so the frame goes through the batch front-end
     (pipeline.BatchCompressor -> rpcc_compress_batch_wide) as a batch of one.  Same container, same decoder."""
     from rpcc_amd.pipeline import BatchCompressor
-    dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
+    dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None),
+                            point_format=point_format_of(args))
     t0 = time.time()
     want_w = getattr(args, "intensity", False)
     if want_w:     # the rows as stored (filtered like the points): the batch front-end makes the payload from its own range image
@@ -233,7 +244,7 @@ def compress(args):
         return compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform)
     filtered = getattr(args, "use_radius_outlier_removal", False)
     dataset = build_dataset(lidar_type=args.lidar, use_radius_outlier_removal=filtered,
-                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
+                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None), point_format=point_format_of(args))
     model_num = segment_cfg["cluster_num"] + 1
     pc_seg = PointCloudSegment(dataset.transform_map, seed=args.seed, frame_id=frame_identity(args.input))
 

@@ -24,7 +24,7 @@ from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.loader import StreamingCompressor  # noqa: E402
 from rpcc_amd.pipeline import BatchCompressor  # noqa: E402
 from rpcc_amd.sharding import RoundGather, shard_indices  # noqa: E402
-from rpcc_amd.tools.compress import apply_fps_mode, make_parser, resolve_cfg  # noqa: E402
+from rpcc_amd.tools.compress import apply_fps_mode, make_parser, point_format_of, resolve_cfg  # noqa: E402
 from rpcc_amd.utils import available_cpus, frame_identity, local_rank_env, pin_rank_cpus  # noqa: E402
 
 
@@ -83,6 +83,24 @@ def init_gather_group(rank, world, local):
     return dist
 
 
+def resolve_ingest(want, names, intensity=False, point_format=None):
+    """The ingest mode of a whole datalist (--ingest, --intensity, --input_format; names: its file names) -> "rows", "xyz" or "nclt";
+    SystemExit for a combination the options exclude.  --input_format nclt always stages the records themselves (8 bytes per point,
+    the intensity byte among them), so it goes with --ingest auto only."""
+    all_bin = all(str(name).endswith(".bin") for name in names)
+    if point_format == "nclt":
+        if want != "auto":
+            raise SystemExit("--input_format nclt sends the 8-byte records to the device (ingest nclt) and does not go with --ingest %s" % want)
+        return "nclt"
+    if intensity:      # the fourth column must reach the device: the rows as stored
+        if not all_bin or want == "xyz":
+            raise SystemExit("--intensity needs a datalist of .bin files (float32 rows x, y, z, intensity)" + (" and not --ingest xyz" if want == "xyz" else ""))
+        want = "rows"
+    if want == "rows" and not all_bin:
+        raise SystemExit("--ingest rows needs a datalist of .bin files (float32 rows x, y, z, intensity)")
+    return "rows" if (len(names) > 0 and (want == "rows" or (want == "auto" and all_bin))) else "xyz"
+
+
 def compress(args, streaming_factory=None):
     """streaming_factory (tests): builds the object that turns batches into .rpcc strings -- loader.StreamingCompressor's constructor
     arguments and run() -- so that the sharding / gathering / file-writing logic of this driver can run on hosts without a GPU."""
@@ -99,8 +117,10 @@ def compress(args, streaming_factory=None):
         args.workers = max(1, min(args.workers, available_cpus()))
     apply_fps_mode(args)
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
+    if point_format_of(args) == "nclt" and getattr(args, "ingest", "auto") != "auto":     # (before anything is read or built)
+        resolve_ingest(args.ingest, [], point_format="nclt")
     dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device,
-                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
+                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None), point_format=point_format_of(args))
     bc = BatchCompressor(dataset.PCTransformer, cluster_num=segment_cfg["cluster_num"], accuracy=accuracy / 2,
                          ground_threshold=segment_cfg["ground_vertical_threshold"], uniform=uniform,
                          model_method=model_cfg["model_method"], compressor_cfg=dict(cfg),
@@ -114,15 +134,7 @@ def compress(args, streaming_factory=None):
     mine = shard_indices(len(dataset), rank, world)
     # the ingest mode follows from the WHOLE datalist -- the same decision on every rank, also on one whose shard is empty -- and is
     # settled before the process group forms, so that a datalist --ingest rows cannot take fails on all ranks together
-    want = getattr(args, "ingest", "auto")
-    all_bin = all(str(name).endswith(".bin") for name in dataset.data_list)
-    if getattr(args, "intensity", False):      # the fourth column must reach the device: the rows as stored
-        if not all_bin or want == "xyz":
-            raise SystemExit("--intensity needs a datalist of .bin files (float32 rows x, y, z, intensity)" + (" and not --ingest xyz" if want == "xyz" else ""))
-        want = "rows"
-    if want == "rows" and not all_bin:
-        raise SystemExit("--ingest rows needs a datalist of .bin files (float32 rows x, y, z, intensity)")
-    ingest = "rows" if (len(dataset) > 0 and (want == "rows" or (want == "auto" and all_bin))) else "xyz"
+    ingest = resolve_ingest(getattr(args, "ingest", "auto"), dataset.data_list, getattr(args, "intensity", False), point_format_of(args))
     gather = None
     if getattr(args, "gather", False):
         import torch
@@ -144,7 +156,7 @@ def compress(args, streaming_factory=None):
             for k, s in enumerate(range(0, len(mine), sc.B)):
                 names = [dataset.data_list[i] for i in mine[s:s + sc.B]]
                 names_of[k] = names
-                frames = names if ingest == "rows" else list(pool.map(dataset.load_data, names))
+                frames = names if ingest in ("rows", "nclt") else list(pool.map(dataset.load_data, names))     # paths: read in place by the loader
                 yield frames, [frame_identity(n) for n in names]
 
         def write_all(jobs):      # jobs: [(file name, bytes)]

@@ -17,7 +17,7 @@ import rpcc_amd  # noqa: E402,F401
 from rpcc_amd import ops  # noqa: E402
 from rpcc_amd.compress_utils import decompress_point_cloud, parse_intensity_payload, read_compressed_bitstream  # noqa: E402,F401
 from rpcc_amd.dataset import build_dataset  # noqa: E402
-from rpcc_amd.tools.compress import make_parser, print_intensity_error, print_quality, resolve_cfg  # noqa: E402
+from rpcc_amd.tools.compress import make_parser, point_format_of, print_intensity_error, print_quality, resolve_cfg  # noqa: E402
 
 
 def stream_cluster_num(segment_cfg):
@@ -108,7 +108,9 @@ def decompress(args):
     if args.eval and args.original_point_cloud is None:
         raise ValueError("--eval compares with the original point cloud: set --original_point_cloud")
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
-    dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
+    # (--input_format: how --original_point_cloud is read; the output is written as float values either way)
+    dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None),
+                            point_format=point_format_of(args))
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     t0 = time.time()
     want_w = getattr(args, "intensity", False)

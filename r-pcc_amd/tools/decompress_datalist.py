@@ -14,7 +14,7 @@ import rpcc_amd  # noqa: E402,F401
 from rpcc_amd.compress_utils import read_compressed_bitstream  # noqa: E402
 from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.sharding import shard_indices  # noqa: E402
-from rpcc_amd.tools.compress import make_parser, resolve_cfg  # noqa: E402
+from rpcc_amd.tools.compress import make_parser, point_format_of, resolve_cfg  # noqa: E402
 from rpcc_amd.tools.decompress import decode_frame, stream_cluster_num  # noqa: E402
 
 
@@ -53,8 +53,9 @@ def decompress(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
+    # (--input_format: how the dataset reads original point files; this tool reads none, its outputs are float .bin files either way)
     dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device,
-                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None))
+                            channel_distribute_csv=getattr(args, "channel_distribute_csv", None), point_format=point_format_of(args))
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     mine = list(shard_indices(len(dataset), rank, world))
     if getattr(args, "batch_decode", False):

@@ -32,6 +32,7 @@ BZIP2_SRC, BZIP2_DEPS, BZIP2_LIB = _side_library("csrc_bzip2", "bzip2_kernels.hi
 FILTER_SRC, FILTER_DEPS, FILTER_LIB = _side_library("csrc_filter", "radius_filter.hip", "rpcc_filter.h", "librpcc_filter.so")   # radius outlier removal
 RANS_SRC, RANS_DEPS, RANS_LIB = _side_library("csrc_rans", "rans_kernels.hip", "rpcc_rans.h", "librpcc_rans.so")   # chunk-parallel rANS back-end
 RECORDS_SRC, RECORDS_DEPS, RECORDS_LIB = _side_library("csrc_records", "records_kernels.hip", "rpcc_records.h", "librpcc_records.so")   # NCLT record unpack
+ROWS_SRC, ROWS_DEPS, ROWS_LIB = _side_library("csrc_rows", "rows_kernels.hip", "rpcc_rows.h", "librpcc_rows.so")   # decoded batch -> .bin rows
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -127,6 +128,11 @@ def build_records(force=False, verbose=False):
     return _hipcc(RECORDS_SRC, RECORDS_LIB, RECORDS_DEPS, force, verbose)
 
 
+def build_rows(force=False, verbose=False):
+    """librpcc_rows.so: the .bin row packer (csrc_rows/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(ROWS_SRC, ROWS_LIB, ROWS_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -142,6 +148,7 @@ def build(force=False, verbose=False):
     build_filter(force, verbose)
     build_rans(force, verbose)
     build_records(force, verbose)
+    build_rows(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

@@ -13,15 +13,19 @@ therefore overlaps the three parts for consecutive batches:
 
 submit(n+1) -- with the default depth of 4 also submit(n+2) -- is issued before collect(n), so the copy engine always has a
 staged batch waiting.  Slots (staging, device input, BatchBuffers, output) form a ring of `depth`.
+
+StreamingDecompressor is the way back: .rpcc files in, .bin files out, a chunk per stream with up to `depth` chunks in flight; only the
+files' bytes (rows.pack on the device) and a few words per frame come back, and the pool reads and writes files meanwhile.
 """
 import os
+import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import ops, records
+from . import _lib, ops, records
 from .compress_utils import BatchPayload, pack_bitstream, pack_frames  # noqa: F401
 from .utils import available_cpus
 
@@ -305,3 +309,144 @@ class StreamingCompressor:
             total += finish(submitted.pop(0))
         total += drain()
         return total
+
+
+class _DecodeSlot:
+    """What one chunk in flight owns: its stream, the chunk-sized images it is decoded into, and the pinned buffers its results land in."""
+
+    def __init__(self, bd, device):
+        n, P = bd.chunk, bd.T.H * bd.T.W
+        self.stream = torch.cuda.Stream(device=device)
+        with torch.cuda.device(device):
+            self.images = bd.rows_buffers(n)
+        self.status_pin = torch.empty((n,), dtype=torch.int32).pin_memory()
+        self.offsets_pin = torch.empty((n + 1,), dtype=torch.int64).pin_memory()
+        self.nonzero_pin = torch.empty((n,), dtype=torch.int32).pin_memory()
+        self.rows_pin = torch.empty((n * P, 4), dtype=torch.float32).pin_memory()     # every pixel kept: the most a chunk can hold
+        self.small_done = torch.cuda.Event()
+        self.rows_dev = None
+        self.writes = []        # futures of the .bin files being written from rows_pin
+
+
+class StreamingDecompressor:
+    """The decode counterpart of StreamingCompressor.  bd: pipeline.BatchDecompressor (geometry, cluster count, framework, entropy back-end,
+    intensity); depth: chunks in flight, each on its own stream with its own pinned buffers; workers: host threads, which read the .rpcc
+    files of later chunks and write the .bin files of earlier ones while the device works.  A chunk is bd.chunk frames: its containers go up
+    in one copy, are decoded into chunk-sized images that never leave the device, and rows.pack turns those into the files' bytes --
+    status, offsets, non-zero counts and rows[:total] are all that comes back.  One process, no children."""
+
+    def __init__(self, bd, depth=3, workers=None, pool=None):
+        self.bd, self.depth, self.device = bd, max(1, int(depth)), bd.device
+        self.pool = pool or ThreadPoolExecutor(workers or min(32, available_cpus()))
+        self.slots = [_DecodeSlot(bd, self.device) for _ in range(self.depth)]
+
+    @staticmethod
+    def _read(path):
+        with open(path, "rb") as f:
+            return f.read()
+
+    @staticmethod
+    def _write(out_path, rows):
+        d = os.path.dirname(out_path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        rows.tofile(out_path)
+
+    def _enqueue(self, slot, blobs):
+        n = len(blobs)
+        with torch.cuda.stream(slot.stream):
+            status, offsets, rows, nonzero = self.bd.decompress_rows_device(blobs, images=slot.images)
+            slot.status_pin[:n].copy_(status, non_blocking=True)
+            slot.offsets_pin[:n + 1].copy_(offsets, non_blocking=True)
+            slot.nonzero_pin[:n].copy_(nonzero, non_blocking=True)
+            slot.small_done.record(slot.stream)
+        slot.rows_dev = rows
+
+    def _finish(self, slot, blobs, paths, out_paths, first, on_frame):
+        """The chunk's rows to the host and its files to the pool, frame by frame in order; raises at the first frame that is refused."""
+        n = len(blobs)
+        slot.small_done.synchronize()
+        offsets = slot.offsets_pin.numpy()[:n + 1].copy()
+        total = int(offsets[n])
+        with torch.cuda.stream(slot.stream):
+            slot.rows_pin[:total].copy_(slot.rows_dev[:total], non_blocking=True)
+        slot.stream.synchronize()
+        slot.rows_dev = None
+        host = slot.rows_pin.numpy()
+        for i, st in enumerate(slot.status_pin.numpy()[:n].tolist()):
+            if st == _lib.STREAM_OK:
+                rows, nz = host[offsets[i]: offsets[i + 1]], int(slot.nonzero_pin[i])
+            else:
+                try:
+                    if not self.bd.falls_back(st):
+                        raise self.bd.refusal(st, first + i)
+                    rows, nz = self.bd.rows_fallback(blobs[i], first + i)
+                except ValueError as e:
+                    raise ValueError("%s: %s" % (paths[i], e)) from e
+            slot.writes.append(self.pool.submit(self._write, out_paths[i], rows))
+            if on_frame is not None:
+                on_frame(first + i, rows.shape[0], nz)
+
+    @staticmethod
+    def _settle(slot):
+        """The slot's files are on disk (raises what a write raised); its pinned rows are free again."""
+        writes, slot.writes = slot.writes, []
+        for f in writes:
+            f.result()
+
+    def run(self, paths, out_paths, on_frame=None):
+        """Decodes the .rpcc files `paths` to the .bin files `out_paths` (directories are made), chunk by chunk with up to `depth` chunks in
+        flight.  on_frame(index, rows, nonzero) is called in input order for every frame whose file is on its way.  A frame that cannot be
+        decoded raises ValueError naming its path: every frame before it has its complete file, the frame itself and those after it in the
+        list have none that this call began.  Returns the number of frames."""
+        paths, out_paths = list(paths), list(out_paths)
+        assert len(paths) == len(out_paths)
+        step = self.bd.chunk
+        chunks = [(c0, min(c0 + step, len(paths))) for c0 in range(0, len(paths), step)]
+        reads = {}
+
+        def prefetch(k):
+            if k < len(chunks) and k not in reads:
+                reads[k] = [self.pool.submit(self._read, p) for p in paths[chunks[k][0]: chunks[k][1]]]
+
+        flying = []     # FIFO of (slot, blobs, c0, c1): on the device, not yet finished
+        done = 0
+        try:
+            for k in range(min(self.depth, len(chunks))):
+                prefetch(k)
+            for k, (c0, c1) in enumerate(chunks):
+                slot = self.slots[k % self.depth]
+                while any(f[0] is slot for f in flying):      # (depth 1: the slot's previous chunk first)
+                    s, blobs, a, b = flying.pop(0)
+                    self._finish(s, blobs, paths[a:b], out_paths[a:b], a, on_frame)
+                    done = b
+                self._settle(slot)
+                blobs = [f.result() for f in reads.pop(k)]
+                prefetch(k + self.depth)
+                self._enqueue(slot, blobs)
+                flying.append((slot, blobs, c0, c1))
+                while len(flying) >= self.depth and self.depth > 1:
+                    s, blobs, a, b = flying.pop(0)
+                    self._finish(s, blobs, paths[a:b], out_paths[a:b], a, on_frame)
+                    done = b
+            while flying:
+                s, blobs, a, b = flying.pop(0)
+                self._finish(s, blobs, paths[a:b], out_paths[a:b], a, on_frame)
+                done = b
+        finally:
+            # whatever happened: nothing of this call is left running -- streams drained, pending reads dropped, begun files completed
+            for s in self.slots:
+                s.stream.synchronize()
+                s.rows_dev = None
+            for futs in reads.values():
+                for f in futs:
+                    f.cancel()
+            err = None
+            for s in self.slots:
+                try:
+                    self._settle(s)
+                except Exception as e:      # noqa: BLE001 -- a failed write is reported unless a decode error is already on its way
+                    err = err or e
+            if err is not None and sys.exc_info()[0] is None:
+                raise err
+        return done

@@ -593,6 +593,75 @@ class BatchDecompressor:
                 self._chunk_device(blobs[c0: c1], tuple(None if o is None else o[c0: c1] for o in out), None if uploaded is None else uploaded[c0 // self.chunk])
         return out
 
+    def rows_buffers(self, n):
+        """The device buffers one chunk of at most n frames is decoded into on its way to rows: decompress_device's outputs, chunk-sized."""
+        H, W, dev = self.T.H, self.T.W, self.device
+        out = (torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n, H, W), dtype=ops.label_dtype(self.M), device=dev),
+               torch.empty((n, H, W), dtype=torch.float32, device=dev), torch.empty((n, H, W, 3), dtype=torch.float32, device=dev))
+        return out + ((torch.empty((n, H, W), dtype=torch.float32, device=dev),) if self.intensity else ())
+
+    def decompress_rows_device(self, blobs, uploaded=None, images=None):
+        """The .bin rows of the batch instead of its images (rows.py, librpcc_rows.so).  -> (status i32 [B], offsets i64 [B+1], rows f32 [B*H*W,4],
+        nonzero i32 [B]) GPU tensors, queued on the current stream and not waited for: frame b is rows[offsets[b]:offsets[b+1]], the frames back
+        to back (a refused frame has no rows), nonzero[b] its pixels with a range != 0; with intensity=True the fourth column is the decoded
+        intensity, else +0.0.  Each chunk is decoded into the same chunk-sized images (images: rows_buffers(self.chunk) of the caller's, else
+        allocated here) and packed behind the chunk before: no image of the batch exists, here or on the host."""
+        from . import rows as R
+        B, P, dev = len(blobs), self.T.H * self.T.W, self.device
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+        out_rows = torch.empty((B * P, 4), dtype=torch.float32, device=dev)
+        nonzero = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            images = self.rows_buffers(min(self.chunk, B)) if images is None and B else images
+            base = None
+            for c0 in range(0, B, self.chunk):
+                n = min(self.chunk, B - c0)
+                out = tuple(o[:n] for o in images)
+                self._chunk_device(blobs[c0: c0 + n], out, None if uploaded is None else uploaded[c0 // self.chunk])
+                table, _, _ = R.pack(out[3], out[4] if self.intensity else None, out[2], rows=out_rows, nonzero=nonzero[c0: c0 + n], base=base)
+                status[c0: c0 + n] = out[0]
+                offsets[c0: c0 + n + 1] = table[: n + 1]
+                base = table[n: n + 1]
+        return status, offsets, out_rows, nonzero
+
+    def rows_fallback(self, blob, index):
+        """A frame the device decoder refused with a status decompress() falls back on: once more through decode_frame with the host library,
+        its rows by the numpy rule.  -> (rows f32 [n,4], nonzero).  Any other status, and what the host library refuses too: ValueError."""
+        from . import rows as R
+        from .tools.decompress import decode_frame
+        try:
+            rec, pc, _, *w = decode_frame(unpack_bitstream(blob, self.uniform, intensity=self.intensity), self.host_bc, self.T, self.cluster_num,
+                                          self.accuracy, self.level_acc, self.uniform, intensity=self.intensity)
+        except (ValueError, OSError, EOFError) as e:
+            raise ValueError("frame %d: %s" % (index, e)) from e
+        return R.pack_host(pc, w[0] if w else None), int((rec != 0).sum())
+
+    def falls_back(self, st):
+        """decompress()'s rule: E_ENTROPY, and E_PLANE on a DBSCAN stream (more rows than the cap), go through the per-frame path."""
+        return st == _lib.STREAM_E_ENTROPY or (st == _lib.STREAM_E_PLANE and self.per_frame_rows)
+
+    def refusal(self, st, index):
+        return ValueError("frame %d: %s (status %d)" % (index, STREAM_TEXT.get(int(st), "refused"), int(st)))
+
+    def decompress_rows(self, blobs):
+        """-> [float32 [n_b,4] host arrays]: the rows tools/decompress_datalist.py writes to <name>.bin, byte for byte.  Per chunk only status,
+        offsets and rows[:total] cross the link (a caller that wants the point counts too takes them from decompress_rows_device).  The fallback and the errors are decompress()'s."""
+        res = []
+        for c0 in range(0, len(blobs), self.chunk):
+            part = blobs[c0: c0 + self.chunk]
+            status, offsets, rows, _ = self.decompress_rows_device(part)
+            status, offsets = status.cpu().numpy(), offsets.cpu().numpy()
+            host = rows[: int(offsets[-1])].cpu().numpy()
+            for i, st in enumerate(status):
+                if st == _lib.STREAM_OK:
+                    res.append(host[offsets[i]: offsets[i + 1]])
+                elif self.falls_back(st):
+                    res.append(self.rows_fallback(part[i], c0 + i)[0])
+                else:
+                    raise self.refusal(st, c0 + i)
+        return res
+
     def decompress(self, blobs, want_points=True):
         """-> [(rec f32 [H,W], pc f32 [H,W,3] or None, seg [H,W])] as tools/decompress.py:decode_frame returns them, a chunk's arrays in one
         copy each.  A frame whose entropy streams the device decoder refuses (E_ENTROPY: bzip2 with trailing bytes or the randomised bit, a

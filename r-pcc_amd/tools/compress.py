@@ -22,6 +22,13 @@ from rpcc_amd.utils import frame_identity, load_compressor_cfg  # noqa: E402
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+class _StreamDecode(argparse.Action):
+    """--stream_decode: sets batch_decode as well (the streamed path is the batch decoder with chunks in flight)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.stream_decode = namespace.batch_decode = True
+
+
 def make_parser(datalist=False):
     p = argparse.ArgumentParser()
     if datalist:
@@ -42,6 +49,10 @@ def make_parser(datalist=False):
         p.add_argument("--batch_decode", action="store_true",
                        help="decompress_datalist.py: decode every chunk of files through pipeline.BatchDecompressor (one entropy launch and one "
                             "fused decode call per chunk); the output files are the same.")
+        p.add_argument("--stream_decode", action=_StreamDecode, nargs=0, default=False,
+                       help="decompress_datalist.py: --batch_decode with several chunks in flight (loader.StreamingDecompressor): the .bin rows are "
+                            "packed on the device and only they cross the link, while host threads read later files and write earlier ones; the "
+                            "output files are the same.  Implies --batch_decode.")
         p.add_argument("--max_labels", type=int, default=None,
                        help="segment_method DBSCAN: the largest label a frame may use in the batch kernels (default and at most 1023; up to 255: "
                             "byte labels on the device).  compress_datalist.py refuses a frame with more; decompress_datalist.py --batch_decode "

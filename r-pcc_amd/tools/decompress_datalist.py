@@ -34,6 +34,8 @@ def decompress_batched(args, dataset, mine, cluster_num, accuracy, level_acc, un
     cap = (getattr(args, "max_labels", None) or 1023) if cluster_num is None else None
     bd = BatchDecompressor(dataset.PCTransformer, cluster_num, accuracy, uniform=uniform, level_acc=level_acc, basic_compressor=basic_compressor,
                            max_labels=cap, intensity=getattr(args, "intensity", False))
+    if getattr(args, "stream_decode", False):
+        return decompress_streamed(args, bd, [dataset.data_list[i] for i in mine])
     for c0 in range(0, len(mine), CHUNK):
         names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
         blobs = []
@@ -48,8 +50,19 @@ def decompress_batched(args, dataset, mine, cluster_num, accuracy, level_acc, un
                 print("%s -> %s (%d points)" % (name, out, int((rec != 0).sum())))
 
 
+def decompress_streamed(args, bd, names):
+    """--stream_decode: this rank's shard through loader.StreamingDecompressor -- the .bin rows are made on the device, several chunks are
+    in flight, and the pool's threads (--workers; left at 1, the loader's own default) read and write files meanwhile.  The same files as
+    --batch_decode."""
+    from rpcc_amd.loader import StreamingDecompressor
+    outs = [output_path(args, name) for name in names]
+    report = (lambda i, rows, nonzero: print("%s -> %s (%d points)" % (names[i], outs[i], nonzero))) if args.output else None
+    workers = int(getattr(args, "workers", 1) or 1)
+    StreamingDecompressor(bd, workers=workers if workers > 1 else None).run(names, outs, on_frame=report)
+
+
 def decompress(args):
-    rank = int(os.environ.get("RANK", "0"))
+    rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)

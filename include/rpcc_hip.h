@@ -177,6 +177,40 @@ int rpcc_intensity_encode(const float *rows, const int64_t *offsets, int64_t tot
 int rpcc_intensity_decode(const uint8_t *payload, int64_t payload_stride, const int32_t *nbytes, const void *labels, int label_bytes, int B,
                           int P, float *intensity, int32_t *status, void *stream);
 
+/* ---- subpixel: where inside its cell a pixel's owner lies, 1 .. 4 bits per axis ---------------- *
+ * A decoded point lies on the centre ray of its pixel; these entries carry the offset the projection rounds away.  The specification is
+ * stated once, in tests/subpixel_ref.py (new exports under interface version 105; no existing struct or argument changes):
+ *   owner     the intensity channel's: the row whose depth the projection keeps (above)
+ *   offsets   the owner's x, y, z through the projection's fp32 sequence: off_az = colf - roundf(colf), taken before the column wraps (a
+ *             point that rounds to column W has column 0 and a negative offset); off_el = rowf - (float)row, taken after the row is
+ *             clamped to 0 .. H-1 (so it may lie outside +-0.5)
+ *   code      L = 1 << bits; t = (off + 0.5f) * (float)L (one fp32 add, one fp32 multiply); c = min(max((int)floorf(t), 0), L - 1);
+ *             it stands for the offset (c + 0.5) / L - 0.5 cells
+ *   payload   8 + 2n bytes: "RPS1", bits, three zero bytes, the az codes of the non-empty pixels in ascending pixel index, then their el
+ *             codes; one byte per code; n = pixels with ri != 0 = pixels whose label is not 1
+ * rpcc_subpixel_encode: rows / offsets / ri as rpcc_intensity_encode takes them; bits 1 .. 4.  Out: payload dev u8 rows of payload_stride
+ * >= 8 + 2P bytes (frame b: 8 + 2 n_b bytes are written, the rest is left as it is), nbytes dev i32 [B] = 8 + 2 n_b, codes dev u8 [B,P,2]
+ * (2-byte aligned) or NULL: (az, el) per pixel, 0 where empty; orphans dev i32 [B] = non-empty pixels no row owns (coded as 0, 0).
+ * scratch: rpcc_subpixel_scratch_bytes(B, P) bytes, no initialisation needed.
+ * rpcc_subpixel_decode: labels dev [B,P] of label_bytes 1 or 2, ri_rec dev f32 [B,P] the reconstructed ranges, tables dev f64
+ * [2H + 2W + 256]: cos / sin of the rows' altitudes (ca [H], sa [H]) and of the columns' azimuths (cz [W], sz [W]) as the transform map is
+ * built from them, then for bits = 1 .. 4 and code c = 0 .. 15 at ((bits - 1) * 16 + c) * 4: cos, sin of the elevation step
+ * ((c + 0.5) / L - 0.5) * vfov / (H-1) and cos, sin of the azimuth step ((c + 0.5) / L - 0.5) * hfov / W.  Out: points dev f32 [B,P,3]:
+ *   cosalt = ca*cde - sa*sde; sinalt = sa*cde + ca*sde; cosaz = cz*cda - sz*sda; sinaz = sz*cda + cz*sda          (fp64, un-fused)
+ *   x = (float)((double)r * (cosalt * cosaz)); y = (float)((double)r * (cosalt * sinaz)); z = (float)((double)r * sinalt)
+ * and +0.0 where the label is 1; status dev i32 [B] = RPCC_STREAM_OK, or RPCC_STREAM_E_SUBPIXEL (the frame's points are zeros, no code is
+ * used as an index) when nbytes[b] is outside 8 .. the row, the magic is missing, bits is outside 1 .. 4, a reserved byte is not 0,
+ * nbytes[b] != 8 + 2 (labels != 1), or any code is >= L.
+ * Argument errors return RPCC_ERR_ARG before the device is touched, as for the intensity entries; besides, H * W must stay below
+ * 2^30 - 4, so that 8 + 2 H W, the longest payload, fits the int32 of nbytes (rpcc_subpixel_scratch_bytes returns 0 above it). */
+#define RPCC_STREAM_E_SUBPIXEL 11 /* rpcc_subpixel_decode */
+size_t rpcc_subpixel_scratch_bytes(int B, int P);
+int rpcc_subpixel_encode(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, int bits,
+                         uint8_t *payload, int64_t payload_stride, int32_t *nbytes, uint8_t *codes, int32_t *orphans, void *scratch,
+                         size_t scratch_bytes, void *stream);
+int rpcc_subpixel_decode(const uint8_t *payload, int64_t payload_stride, const int32_t *nbytes, const void *labels, int label_bytes,
+                         const float *ri_rec, const double *tables, int H, int W, int B, float *points, int32_t *status, void *stream);
+
 /* ---- a4: ground plane ----------------------------------------------------------------------- *
  * replaces the ground branch of PointCloudSegment.segment: candidate selection + RANSAC
  * (utils/segment_utils.py:74-82,101-108).  The reference uses Open3D segment_plane on an unseeded

@@ -50,6 +50,7 @@ MAX_CLUSTERS_MID = 1022     # RPCC_MAX_CLUSTERS_MID: the tuned kernels on uint16
 STREAM_OK, STREAM_E_ENTROPY, STREAM_E_PLANE, STREAM_E_CONTOUR, STREAM_E_WIDTH = 0, 1, 2, 3, 4     # RPCC_STREAM_* (rpcc_decompress_batch)
 STREAM_E_NSEQ, STREAM_E_LABEL, STREAM_E_SALIENCE, STREAM_E_RESIDUAL, STREAM_E_CONTAINER = 5, 6, 7, 8, 9
 STREAM_E_INTENSITY = 10   # RPCC_STREAM_E_INTENSITY (rpcc_intensity_decode; no valid intensity trailer where one was asked for)
+STREAM_E_SUBPIXEL = 11    # RPCC_STREAM_E_SUBPIXEL (rpcc_subpixel_decode; no valid subpixel payload)
 LABELS_OK, LABELS_E_RANGE, LABELS_E_CAPPED = 0, 1, 2     # RPCC_LABELS_* (rpcc_compress_batch_labels)
 BEAM_MAX_H = 128       # RPCC_BEAM_MAX_H (csrc/beam_index.h): rows of a per-beam elevation table
 ABI_VERSION = 105      # RPCC_ABI_VERSION: the layout of rpcc_batch_io / rpcc_geom this binding was written for
@@ -86,6 +87,9 @@ _SIGS = {
     "rpcc_intensity_scratch_bytes": (C.c_size_t, [_I, _I]),
     "rpcc_intensity_encode": (C.c_int, [_VP, _VP, _I64, _I, Geom, _VP, _F, _VP, _I64, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "rpcc_intensity_decode": (C.c_int, [_VP, _I64, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
+    "rpcc_subpixel_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "rpcc_subpixel_encode": (C.c_int, [_VP, _VP, _I64, _I, Geom, _VP, _I, _VP, _I64, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "rpcc_subpixel_decode": (C.c_int, [_VP, _I64, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
     "rpcc_ground_ransac": (C.c_int, [_VP, _VP, _I, _I, C.c_uint32, _VP, _VP, _VP, _VP]),
     "rpcc_ground_mask": (C.c_int, [_VP, _VP, _VP, _D, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "rpcc_fps_table_bytes": (C.c_size_t, [_I, _I, _I]),

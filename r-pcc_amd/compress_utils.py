@@ -97,12 +97,15 @@ class QuantizationModule:
 
 def compress_point_cloud(basic_compressor, plane_param, cluster_idx, salience_level, nonzero_residual_quantized,
                          ground_residual_quantized=None, cluster_residual_quantized=None, point_cloud=None,
-                         range_image=None, full=False, intensity=None):
+                         range_image=None, full=False, intensity=None, subpixel=None):
     """utils/compress_utils.py:138-164: casts + contour + packbits + per-array entropy coding.  intensity (not the reference's): the
-    uint8 payload of ops.intensity_encode, coded like any other array and appended to the container by pack_bitstream."""
+    uint8 payload of ops.intensity_encode, coded like any other array and appended to the container by pack_bitstream.  subpixel: the
+    uint8 payload of ops.subpixel_encode, alike, behind it."""
     original_data = {"residual_quantized": np.asarray(nonzero_residual_quantized).astype(np.int16)}
     if intensity is not None:
         original_data["intensity"] = np.ascontiguousarray(intensity, dtype=np.uint8)
+    if subpixel is not None:
+        original_data["subpixel"] = np.ascontiguousarray(subpixel, dtype=np.uint8)
     if full:
         if point_cloud is not None:
             original_data["point_cloud"] = point_cloud.astype(np.float32)
@@ -131,19 +134,22 @@ SCHEMA = (Column("salience_level", np.dtype(np.uint8), lambda P, K: K, "nrow"),
           Column("idx_sequence", np.dtype(np.uint16), lambda P, K: 2 * P, "nseq"),
           Column("plane_param", np.dtype(np.float32), lambda P, K: 16 * K, "nrow"),
           Column("residual_quantized", np.dtype(np.int16), lambda P, K: 2 * P, "nnz"),
-          Column("intensity", np.dtype(np.uint8), lambda P, K: 8 + P, "nbytes"))
+          Column("intensity", np.dtype(np.uint8), lambda P, K: 8 + P, "nbytes"),
+          Column("subpixel", np.dtype(np.uint8), lambda P, K: 8 + 2 * P, "nsub"))
 INTENSITY_MAGIC = b"RPI1"
+SUBPIXEL_MAGIC = b"RPS1"
+TRAILERS = ("intensity", "subpixel")      # the optional columns behind the geometry, in file order
 
 
-def columns(uniform, intensity=False):
-    """The rows of SCHEMA a container holds, in file order: salience first with the non-uniform framework, intensity (the trailer no
-    reference reader looks at) last where it is carried."""
-    return SCHEMA[1 if uniform else 0: 6 if intensity else 5]
+def columns(uniform, intensity=False, subpixel=False):
+    """The rows of SCHEMA a container holds, in file order: salience first with the non-uniform framework, then the trailers no
+    reference reader looks at, where they are carried: intensity, then subpixel."""
+    return SCHEMA[1 if uniform else 0: 5] + tuple(c for c, on in zip(SCHEMA[5:], (intensity, subpixel)) if on)
 
 
 def _keys(uniform, data=()):
-    """The arrays of a container in file order; 'intensity' where the frame holds it."""
-    return tuple(c.name for c in columns(uniform, "intensity" in data))
+    """The arrays of a container in file order; 'intensity' and 'subpixel' where the frame holds them."""
+    return tuple(c.name for c in columns(uniform, "intensity" in data, "subpixel" in data))
 
 
 def payload_spans(blob, count):
@@ -160,12 +166,12 @@ def payload_spans(blob, count):
         off += 4 + n
 
 
-def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None):
+def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None, nsub=None):
     """Which elements of which buffer are frame b's column c, stated once for the host assembly (BatchPayload: arrays read back or pinned)
-    and for the device containers (addresses).  buffers: {column name: the batch's buffer}; counts [B,K], nnz / nseq / nbytes [B] -- all
+    and for the device containers (addresses).  buffers: {column name: the batch's buffer}; counts [B,K], nnz / nseq / nbytes / nsub [B] -- all
     numpy arrays or all torch tensors of one device.  -> {name: (start, length)}, int64 [B] of the same kind, in elements of the column's
-    dtype into the flattened buffer.  By the column's cut: 'row', 'nrow' and 'nbytes' columns are rows of a padded [B, ...] array -- the
-    whole row, its first nrow sub-rows, its first nbytes elements; 'nseq' and 'nnz' columns lie packed back to back, frame b at the sum of
+    dtype into the flattened buffer.  By the column's cut: 'row', 'nrow', 'nbytes' and 'nsub' columns are rows of a padded [B, ...] array -- the
+    whole row, its first nrow sub-rows, its first nbytes / nsub elements (the lengths of the intensity and the subpixel payloads); 'nseq' and 'nnz' columns lie packed back to back, frame b at the sum of
     the counts before it.  nrow = max(seg) + 1 (tools/compress.py:102) = 1 + the index of the last non-zero count; 0 for a row of zeros,
     which no frame has (its counts sum to P)."""
     if torch.is_tensor(counts):
@@ -173,7 +179,8 @@ def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None):
     else:
         xp, i64, ar = np, (lambda v: np.asarray(v, np.int64)), (lambda lo, hi: np.arange(lo, hi, dtype=np.int64))
     B, K = counts.shape
-    n = {"nrow": xp.amax(i64(counts != 0) * ar(1, K + 1), 1), "nseq": i64(nseq), "nnz": i64(nnz), "nbytes": None if nbytes is None else i64(nbytes)}
+    n = {"nrow": xp.amax(i64(counts != 0) * ar(1, K + 1), 1), "nseq": i64(nseq), "nnz": i64(nnz), "nbytes": None if nbytes is None else i64(nbytes),
+         "nsub": None if nsub is None else i64(nsub)}
     out = {}
     for c in cols:
         if c.cut in ("nseq", "nnz"):
@@ -187,13 +194,13 @@ def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None):
 
 class BatchPayload:
     """What the container of every frame of a batch is assembled from: views into the batch's host buffers -- a streaming slot's pinned
-    ones or the arrays BatchCompressor.collect read back -- cut by frame_slices.  cols: columns(...); buffers, counts, nnz, nseq, nbytes:
+    ones or the arrays BatchCompressor.collect read back -- cut by frame_slices.  cols: columns(...); buffers, counts, nnz, nseq, nbytes, nsub:
     frame_slices' (numpy), the buffers read as the columns' dtypes; n: the frames that count (the first n; default all).
     frame(b) -> the dict compress_point_cloud builds (utils/compress_utils.py:138-179), before the entropy coder: views, no copies."""
 
-    def __init__(self, cols, buffers, counts, nnz, nseq, nbytes=None, n=None):
+    def __init__(self, cols, buffers, counts, nnz, nseq, nbytes=None, n=None, nsub=None):
         self.n = len(nnz) if n is None else n
-        at = frame_slices(cols, buffers, counts, nnz, nseq, nbytes)
+        at = frame_slices(cols, buffers, counts, nnz, nseq, nbytes, nsub)
         # per column: the flattened buffer, the frames' first and last + 1 elements, the shape of a sub-row (the model's rows keep their [., 4])
         self.parts = [(c.name, buffers[c.name].reshape(-1).view(c.dtype), lo.tolist(), (lo + n_el).tolist(), (-1,) + tuple(buffers[c.name].shape[2:]))
                       for c in cols for lo, n_el in (at[c.name],)]
@@ -255,8 +262,68 @@ def encode_intensity(transformer, rows, range_image, scale, want_image=False):
     return payload[0, : int(nbytes[0])].cpu().numpy(), (image[0].cpu().numpy() if want_image else None)
 
 
+BEAM_TABLE_SUBPIXEL = ("subpixel with a per-beam elevation table (channel_distribute_csv): that projection's rule is 'the last point wins' and "
+                       "its rows are a search over the table, another owner rule and another row offset than the subpixel kernels'; use a lidar "
+                       "configuration with evenly spaced beams")
+
+
+def subpixel_payload(az, el, bits):
+    """The 'subpixel' array of a frame: b"RPS1" | bits | 0 0 0 | az codes uint8 [n] | el codes uint8 [n] of the non-empty pixels in raster order."""
+    az, el = np.ascontiguousarray(az, dtype=np.uint8).reshape(-1), np.ascontiguousarray(el, dtype=np.uint8).reshape(-1)
+    if az.shape != el.shape:
+        raise ValueError("subpixel payload: %d az codes, %d el codes" % (az.shape[0], el.shape[0]))
+    return np.frombuffer(SUBPIXEL_MAGIC + bytes([ops.check_subpixel_bits(bits), 0, 0, 0]) + az.tobytes() + el.tobytes(), dtype=np.uint8)
+
+
+def parse_subpixel_payload(data, n):
+    """-> (bits, az uint8 [n], el uint8 [n]) of a decoded 'subpixel' array; ValueError unless it starts with the magic, names 1 .. 4 bits,
+    has three zero bytes behind them, holds exactly 8 + 2n bytes (n: the pixels whose label is not 1) and no code >= 1 << bits."""
+    data = bytes(data)
+    if len(data) < 8 or data[:4] != SUBPIXEL_MAGIC:
+        raise ValueError("subpixel payload: no %r header (%d bytes)" % (SUBPIXEL_MAGIC, len(data)))
+    bits = data[4]
+    if not 1 <= bits <= 4:
+        raise ValueError("subpixel payload: %d bits per axis (1 .. 4)" % bits)
+    if data[5:8] != b"\0\0\0":
+        raise ValueError("subpixel payload: reserved bytes %r are not 0" % data[5:8])
+    if len(data) != 8 + 2 * n:
+        raise ValueError("subpixel payload: %d bytes for %d non-empty pixels (8 + 2 * %d expected)" % (len(data), n, n))
+    codes = np.frombuffer(data, dtype=np.uint8, offset=8)
+    if codes.size and int(codes.max()) >= 1 << bits:
+        raise ValueError("subpixel payload: code %d at %d bits" % (int(codes.max()), bits))
+    return bits, codes[:n], codes[n:]
+
+
+def encode_subpixel(transformer, rows, range_image, bits, want_codes=False):
+    """One frame's 'subpixel' array on the per-frame path: rows [N,>=3] (host), range_image [H,W] the image of these rows (host array or
+    device tensor) -> (uint8 [8 + 2n], the u8 [H,W,2] (az, el) codes or None), by ops.subpixel_encode."""
+    if getattr(transformer, "even_dist", True) is False:
+        raise NotImplementedError(BEAM_TABLE_SUBPIXEL)
+    dev, H, W = transformer.device, transformer.H, transformer.W
+    rows_d = torch.from_numpy(rows16(rows)).to(dev)
+    ri = range_image if torch.is_tensor(range_image) else torch.from_numpy(np.ascontiguousarray(range_image, dtype=np.float32)).to(dev)
+    offs = torch.tensor([0, rows_d.shape[0]], dtype=torch.int64, device=dev)
+    payload, nbytes, codes, orphans = ops.subpixel_encode(rows_d, offs, transformer.geom, ri.reshape(1, H, W).contiguous(), bits, want_codes=want_codes)
+    if int(orphans[0]):
+        raise RuntimeError("subpixel: %d non-empty pixels have no owner -- the range image is not the image of these rows" % int(orphans[0]))
+    return payload[0, : int(nbytes[0])].cpu().numpy(), (codes[0].cpu().numpy() if want_codes else None)
+
+
+def rows16(points):
+    """Host points [N,>=3] as the 16-byte rows f32 [N,4] the owner pass reads: the first four columns, or xyz and a zero fourth column."""
+    points = np.asarray(points)
+    if points.ndim != 2 or points.shape[1] < 3:
+        raise ValueError("points [N,>=3] are needed, got %s" % (points.shape,))
+    if points.shape[1] >= 4:
+        return np.ascontiguousarray(points[:, :4], dtype=np.float32)
+    out = np.zeros((points.shape[0], 4), np.float32)
+    out[:, :3] = points
+    return out
+
+
 def pack_bitstream(compressed_data, uniform=True):
-    """The .rpcc container (utils/compress_utils.py:167-179): [int32 length | bytes] per array; 'intensity' last where the dictionary holds it."""
+    """The .rpcc container (utils/compress_utils.py:167-179): [int32 length | bytes] per array; 'intensity', then 'subpixel', last where the
+    dictionary holds them."""
     keys = _keys(uniform, compressed_data)
     return b"".join(struct.pack("i", len(compressed_data[k])) + bytes(compressed_data[k]) for k in keys)
 
@@ -275,7 +342,7 @@ def pack_frames(basic_compressor, frames, uniform=True):
     if basic_compressor.batch_codec() and frames:   # every array of the chunk in one dumps_many / compress_many
         blobs = iter(basic_compressor.batch_codec()[1]([np.ascontiguousarray(od[k]) for od in frames for k in _keys(uniform, od)]))
         return [b"".join(struct.pack("i", len(b)) + b for b in (next(blobs) for _ in _keys(uniform, od))) for od in frames]
-    if host is None or len({"intensity" in od for od in frames}) > 1:   # (the host call takes one array count for the whole chunk)
+    if host is None or len({_keys(uniform, od) for od in frames}) > 1:   # (the host call takes one array count for the whole chunk)
         return [pack_bitstream(basic_compressor.compress_dict({k: od[k] for k in _keys(uniform, od)}), uniform=uniform) for od in frames]
     keys = _keys(uniform, frames[0])
     arrs = [np.ascontiguousarray(od[k]) for od in frames for k in keys]
@@ -296,9 +363,11 @@ def pack_frames(basic_compressor, frames, uniform=True):
     return [out[int(offs[i]): int(offs[i]) + int(out_len[i])].tobytes() for i in range(n)]
 
 
-def unpack_bitstream(blob, uniform=True, intensity=False):
+def unpack_bitstream(blob, uniform=True, intensity=False, subpixel=False):
     """intensity=True (a caller that asks for it): the dictionary also holds 'intensity', the coded trailer -- ValueError unless what
-    follows the known payloads is exactly one length-prefixed payload that ends the blob.  Without it: trailing bytes are ignored, as ever."""
+    follows the known payloads is exactly one length-prefixed payload that ends the blob.  Without it: trailing bytes are ignored, as ever.
+    subpixel=True: 'subpixel' alike.  The reader is told which trailers to expect: what follows the geometry must be exactly the trailers
+    asked for, in file order, ending the blob -- ValueError naming the flag that does not fit otherwise."""
     keys = _keys(uniform)
     spans = list(payload_spans(blob, len(keys)))
     off = sum(spans[-1]) if spans else 0      # where the walk ended
@@ -310,13 +379,23 @@ def unpack_bitstream(blob, uniform=True, intensity=False):
                              % (k, len(blob), "non-uniform" if uniform else "uniform"))
         raise ValueError("bitstream: payload '%s' claims %d bytes, %d are left" % (k, struct.unpack_from("i", blob, off)[0], len(blob) - off - 4))
     out = {k: blob[s: s + n] for k, (s, n) in zip(keys, spans)}
-    if intensity:
-        span = intensity_trailer_span(blob, uniform)
-        if span is None:
-            raise ValueError("bitstream: no intensity trailer after its %d payloads (%d bytes follow them; compressed without --intensity?)"
-                             % (len(out), len(blob) - off))
-        out["intensity"] = blob[span[0]: span[1]]
-    return out
+    want = tuple(t for t, on in zip(TRAILERS, (intensity, subpixel)) if on)
+    if not want:
+        return out
+    tail = list(payload_spans(blob, len(keys) + len(TRAILERS)))[len(keys):]      # the trailers the blob holds, two at most
+    if len(tail) >= len(want) and sum(tail[len(want) - 1]) == len(blob):
+        out.update({t: blob[s: s + n] for t, (s, n) in zip(want, tail)})
+        return out
+    if len(tail) > len(want) and sum(tail[-1]) == len(blob):                      # one trailer asked for, two end the blob
+        other = TRAILERS[1 - TRAILERS.index(want[0])]
+        raise ValueError("bitstream: two trailers follow its %d payloads and only %s was asked for (compressed with --%s too? the reader needs "
+                         "%s=True then)" % (len(out), want[0], other, other))
+    if len(tail) >= len(want):
+        raise ValueError("bitstream: %d bytes follow the %s trailer; the trailers asked for must end the container"
+                         % (len(blob) - sum(tail[len(want) - 1]), want[-1]))
+    flag = want[len(tail)]
+    raise ValueError("bitstream: no %s trailer after its %d payloads (%d bytes follow them; compressed without --%s?)"
+                     % (flag, len(out) + len(tail), len(blob) - (sum(tail[-1]) if tail else off), flag))
 
 
 def save_compressed_bitstream(file, compressed_data, uniform=True):
@@ -324,9 +403,9 @@ def save_compressed_bitstream(file, compressed_data, uniform=True):
         f.write(pack_bitstream(compressed_data, uniform))
 
 
-def read_compressed_bitstream(file, uniform=True, intensity=False):
+def read_compressed_bitstream(file, uniform=True, intensity=False, subpixel=False):
     with open(file, "rb") as f:
-        return unpack_bitstream(f.read(), uniform, intensity=intensity)
+        return unpack_bitstream(f.read(), uniform, intensity=intensity, subpixel=subpixel)
 
 
 def decompress_point_cloud(compressed_data, basic_compressor, model_num, H, W):

@@ -1037,20 +1037,11 @@ static inline bool intensity_shape_ok(int B, int64_t H, int64_t W) { return B > 
 
 extern "C" size_t rpcc_intensity_scratch_bytes(int B, int P) { return B > 0 && B <= RPCC_MAX_BATCH && P > 0 ? intensity_layout(nullptr, B, P).bytes : 0; }
 
-extern "C" int rpcc_intensity_encode(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, float scale,
-                                     uint8_t *payload, int64_t payload_stride, int32_t *nbytes, uint8_t *image, float *owner_intensity, int32_t *orphans,
-                                     void *scratch, size_t scratch_bytes, void *stream) {
-    ARG_TRY(intensity_shape_ok(B, g.H, g.W) && total >= 0 && total < ((int64_t)1 << 31));
-    ARG_TRY(g.horizontal_fov > 0.0f);   // (a column index is never negative)
-    ARG_TRY(offsets != nullptr && ri != nullptr && payload != nullptr && nbytes != nullptr && orphans != nullptr && scratch != nullptr);
-    ARG_TRY(total == 0 || rows != nullptr);
-    ARG_TRY((reinterpret_cast<uintptr_t>(rows) & 15u) == 0);   // rows are read with 16-byte loads
-    ARG_TRY(scale > 0.0f && scale <= 3.402823466e+38f);        // (false for NaN)
+// the owner of every non-empty pixel into l (fill, owner pass, and both again for the frames that hold a depth-0 point): the first half of
+// rpcc_intensity_encode and of rpcc_subpixel_encode
+static int intensity_owner_pass(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, const IntensityLayout l,
+                                hipStream_t st) {
     const int P = g.H * g.W;
-    ARG_TRY(payload_stride >= (int64_t)8 + P);
-    const IntensityLayout l = intensity_layout(scratch, B, P);
-    ARG_TRY(scratch_bytes >= l.bytes);
-    hipStream_t st = (hipStream_t)stream;
     const int64_t px = (int64_t)B * P;
     const unsigned fill_wgs = (unsigned)std::min<int64_t>((px + 255) / 256, 4096);
     intensity_fill_kernel<<<fill_wgs, 256, 0, st>>>(l.owner, l.lastz, l.flags, px, B, false, P);
@@ -1065,6 +1056,24 @@ extern "C" int rpcc_intensity_encode(const float *rows, const int64_t *offsets, 
         intensity_owner_kernel<true><<<std::min(wgs, 2048u), INT_THREADS, 0, st>>>(r4, offsets, total, B, g, pix_fast_cfg(g), rb, l.owner, l.lastz, l.flags);
         LAUNCH_CHECK();
     }
+    return RPCC_OK;
+}
+
+extern "C" int rpcc_intensity_encode(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, float scale,
+                                     uint8_t *payload, int64_t payload_stride, int32_t *nbytes, uint8_t *image, float *owner_intensity, int32_t *orphans,
+                                     void *scratch, size_t scratch_bytes, void *stream) {
+    ARG_TRY(intensity_shape_ok(B, g.H, g.W) && total >= 0 && total < ((int64_t)1 << 31));
+    ARG_TRY(g.horizontal_fov > 0.0f);   // (a column index is never negative)
+    ARG_TRY(offsets != nullptr && ri != nullptr && payload != nullptr && nbytes != nullptr && orphans != nullptr && scratch != nullptr);
+    ARG_TRY(total == 0 || rows != nullptr);
+    ARG_TRY((reinterpret_cast<uintptr_t>(rows) & 15u) == 0);   // rows are read with 16-byte loads
+    ARG_TRY(scale > 0.0f && scale <= 3.402823466e+38f);        // (false for NaN)
+    const int P = g.H * g.W;
+    ARG_TRY(payload_stride >= (int64_t)8 + P);
+    const IntensityLayout l = intensity_layout(scratch, B, P);
+    ARG_TRY(scratch_bytes >= l.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = intensity_owner_pass(rows, offsets, total, B, g, ri, l, st)) return rc;
     intensity_pack_kernel<<<B, INT_FRAME_THREADS, 0, st>>>(rows, offsets, total, P, ri, l.owner, scale, payload, payload_stride, nbytes, image, owner_intensity, orphans);
     LAUNCH_CHECK();
     return RPCC_OK;
@@ -1081,6 +1090,55 @@ extern "C" int rpcc_intensity_decode(const uint8_t *payload, int64_t payload_str
         intensity_decode_kernel<uint8_t><<<B, INT_FRAME_THREADS, 0, st>>>(payload, payload_stride, nbytes, static_cast<const uint8_t *>(labels), P, intensity, status);
     else
         intensity_decode_kernel<uint16_t><<<B, INT_FRAME_THREADS, 0, st>>>(payload, payload_stride, nbytes, static_cast<const uint16_t *>(labels), P, intensity, status);
+    LAUNCH_CHECK();
+    return RPCC_OK;
+}
+
+// ---- subpixel: where inside its cell the owner of every pixel lies, `bits` bits per axis ---------------------
+#include "subpixel_kernels.h"
+
+// 8 + 2 P, the longest payload, must fit the int32 of nbytes
+static inline bool subpixel_shape_ok(int B, int64_t H, int64_t W) { return intensity_shape_ok(B, H, W) && H * W < ((int64_t)1 << 30) - 4; }
+
+extern "C" size_t rpcc_subpixel_scratch_bytes(int B, int P) { return B > 0 && B <= RPCC_MAX_BATCH && P > 0 && P < (1 << 30) - 4 ? subpixel_layout(nullptr, B, P).bytes : 0; }
+
+extern "C" int rpcc_subpixel_encode(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, int bits,
+                                    uint8_t *payload, int64_t payload_stride, int32_t *nbytes, uint8_t *codes, int32_t *orphans, void *scratch,
+                                    size_t scratch_bytes, void *stream) {
+    ARG_TRY(subpixel_shape_ok(B, g.H, g.W) && total >= 0 && total < ((int64_t)1 << 31));
+    ARG_TRY(g.horizontal_fov > 0.0f);   // (a column index is never negative)
+    ARG_TRY(offsets != nullptr && ri != nullptr && payload != nullptr && nbytes != nullptr && orphans != nullptr && scratch != nullptr);
+    ARG_TRY(total == 0 || rows != nullptr);
+    ARG_TRY((reinterpret_cast<uintptr_t>(rows) & 15u) == 0);   // rows are read with 16-byte loads
+    ARG_TRY(bits >= 1 && bits <= 4);
+    ARG_TRY((reinterpret_cast<uintptr_t>(codes) & 1u) == 0);   // (az, el) pairs are stored as one 2-byte value
+    const int P = g.H * g.W;
+    ARG_TRY(payload_stride >= (int64_t)8 + 2 * (int64_t)P);
+    const SubpixelLayout l = subpixel_layout(scratch, B, P);
+    ARG_TRY(scratch_bytes >= l.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = intensity_owner_pass(rows, offsets, total, B, g, ri, l.own, st)) return rc;
+    uchar2 *cw = reinterpret_cast<uchar2 *>(codes ? codes : l.codes);
+    const unsigned code_wgs = (unsigned)std::min<int64_t>(((int64_t)B * P + SUB_THREADS - 1) / SUB_THREADS, 256 * 16);
+    subpixel_code_kernel<<<code_wgs, SUB_THREADS, 0, st>>>(reinterpret_cast<const float4 *>(rows), offsets, total, B, g, ri, l.own.owner, bits, cw);
+    LAUNCH_CHECK();
+    subpixel_pack_kernel<<<B, INT_FRAME_THREADS, 0, st>>>(offsets, total, P, ri, l.own.owner, cw, bits, payload, payload_stride, nbytes, orphans);
+    LAUNCH_CHECK();
+    return RPCC_OK;
+}
+
+extern "C" int rpcc_subpixel_decode(const uint8_t *payload, int64_t payload_stride, const int32_t *nbytes, const void *labels, int label_bytes,
+                                    const float *ri_rec, const double *tables, int H, int W, int B, float *points, int32_t *status, void *stream) {
+    ARG_TRY(subpixel_shape_ok(B, H, W));
+    ARG_TRY(payload != nullptr && nbytes != nullptr && labels != nullptr && ri_rec != nullptr && tables != nullptr && points != nullptr && status != nullptr);
+    ARG_TRY(label_bytes == 1 || label_bytes == 2);
+    ARG_TRY((reinterpret_cast<uintptr_t>(tables) & 7u) == 0);
+    ARG_TRY(payload_stride >= (int64_t)8 + 2 * (int64_t)H * W);
+    hipStream_t st = (hipStream_t)stream;
+    if (label_bytes == 1)
+        subpixel_decode_kernel<uint8_t><<<B, INT_FRAME_THREADS, 0, st>>>(payload, payload_stride, nbytes, static_cast<const uint8_t *>(labels), ri_rec, tables, H, W, points, status);
+    else
+        subpixel_decode_kernel<uint16_t><<<B, INT_FRAME_THREADS, 0, st>>>(payload, payload_stride, nbytes, static_cast<const uint16_t *>(labels), ri_rec, tables, H, W, points, status);
     LAUNCH_CHECK();
     return RPCC_OK;
 }

@@ -60,6 +60,9 @@ class _Slot:
         # bc.intensity_scale: the intensity payload rows (8 + n bytes of 8 + P each are meaningful), their lengths and orphan counts
         self.int_pin = torch.empty((B, 8 + P), dtype=torch.uint8).pin_memory() if bc.intensity_scale is not None else None
         self.int_n_pin = torch.zeros((2, B), dtype=torch.int32).pin_memory() if bc.intensity_scale is not None else None
+        # bc.subpixel_bits: the subpixel payload rows (8 + 2n bytes of 8 + 2P each are meaningful), their lengths and orphan counts
+        self.sub_pin = torch.empty((B, 8 + 2 * P), dtype=torch.uint8).pin_memory() if bc.subpixel_bits is not None else None
+        self.sub_n_pin = torch.zeros((2, B), dtype=torch.int32).pin_memory() if bc.subpixel_bits is not None else None
         self.h2d_done = torch.cuda.Event()
         self.done = torch.cuda.Event()
         self.n = 0
@@ -105,6 +108,9 @@ class StreamingCompressor:
         if bc.intensity_scale is not None and ingest == "xyz":
             raise ValueError('StreamingCompressor: a BatchCompressor with intensity_scale needs ingest="rows" (the fourth column must reach the device); '
                              'ingest="xyz" drops it')
+        if bc.subpixel_bits is not None and ingest == "xyz":
+            raise ValueError('StreamingCompressor: a BatchCompressor with subpixel_bits needs ingest="rows" (the owner pass reads 16-byte rows); '
+                             'ingest="xyz" stages packed points')
         self.ingest = ingest
         self.bc, self.B, self.depth = bc, int(batch), int(depth)
         self.device = bc.device
@@ -227,6 +233,11 @@ class StreamingCompressor:
                 slot.int_pin.copy_(pay, non_blocking=True)
                 slot.int_n_pin[0].copy_(nb, non_blocking=True)
                 slot.int_n_pin[1].copy_(orphans, non_blocking=True)
+            if slot.sub_pin is not None:      # (run_batch has run ops.subpixel_encode on the same rows)
+                pay, nb, orphans = slot.buf.subpixel
+                slot.sub_pin.copy_(pay, non_blocking=True)
+                slot.sub_n_pin[0].copy_(nb, non_blocking=True)
+                slot.sub_n_pin[1].copy_(orphans, non_blocking=True)
             slot.keep = (bits, seq, nseq)
             slot.done.record(self.compute_stream)
 
@@ -238,6 +249,8 @@ class StreamingCompressor:
             self.bc.check_status(slot.status_pin.numpy()[:slot.n])
         if slot.int_pin is not None:
             self.bc.check_orphans(slot.int_n_pin.numpy()[1, :slot.n])
+        if slot.sub_pin is not None:
+            self.bc.check_orphans(slot.sub_n_pin.numpy()[1, :slot.n], "subpixel")
         stot = int(slot.tot_pin[1])
         if stot > self.seq_eager:
             # an unusually long index sequence: the rest is fetched now, on a stream of its own (the compute stream already
@@ -248,9 +261,10 @@ class StreamingCompressor:
         # the columns' pinned buffers (compress_utils.SCHEMA), cut per frame by the rule BatchCompressor.collect uses (frame_slices)
         num = lambda t: None if t is None else t.numpy()
         bufs = dict(salience_level=num(slot.sal_pin), contour_map=num(slot.bits_pin), idx_sequence=num(slot.sp_pin), plane_param=num(slot.model_pin),
-                    residual_quantized=num(slot.qp_pin), intensity=num(slot.int_pin))
+                    residual_quantized=num(slot.qp_pin), intensity=num(slot.int_pin), subpixel=num(slot.sub_pin))
         return BatchPayload(self.bc.columns, bufs, num(slot.counts_pin), num(slot.nnz_pin), num(slot.nseq_pin),
-                            None if slot.int_pin is None else num(slot.int_n_pin)[0], n=slot.n)
+                            None if slot.int_pin is None else num(slot.int_n_pin)[0], n=slot.n,
+                            nsub=None if slot.sub_pin is None else num(slot.sub_n_pin)[0])
 
     def _encode_chunk(self, payload, lo, hi):
         bc = self.bc

@@ -189,6 +189,80 @@ def intensity_decode(payload, nbytes, seg, out=None, status=None):
     return out, status
 
 
+SUBPIXEL_TABLE_CODES = 16     # SUB_TABLE_CODES (csrc/subpixel_kernels.h): codes per bits row of the decoder's table
+
+
+def check_subpixel_bits(bits):
+    """The code width of the subpixel channel as the kernels take it: an integer 1 .. 4 (bits per axis)."""
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 1 <= int(bits) <= 4:
+        raise ValueError("subpixel bits %r: an integer 1 .. 4 is needed" % (bits,))
+    return int(bits)
+
+
+def subpixel_tables(H, W, horizontal_FOV, vertical_max, vertical_min):
+    """The decoder's table of rpcc_subpixel_decode (include/rpcc_hip.h), f64 [2H + 2W + 256], built from python floats as transform_map
+    builds its factors: cos / sin of every row's altitude and every column's azimuth, then for bits 1 .. 4 and every code the cos / sin of
+    the elevation step and of the azimuth step the code stands for."""
+    vfov = vertical_max - vertical_min
+    alt = [vfov * (h / (H - 1)) + vertical_min for h in range(H)]
+    azi = [horizontal_FOV * (w / W) for w in range(W)]
+    out = [math.cos(a) for a in alt] + [math.sin(a) for a in alt] + [math.cos(a) for a in azi] + [math.sin(a) for a in azi]
+    for bits in (1, 2, 3, 4):
+        L = 1 << bits
+        for c in range(SUBPIXEL_TABLE_CODES):
+            de = ((c + 0.5) / L - 0.5) * (vfov / (H - 1))
+            da = ((c + 0.5) / L - 0.5) * (horizontal_FOV / W)
+            out += [math.cos(de), math.sin(de), math.cos(da), math.sin(da)] if c < L else [0.0] * 4
+    return np.array(out, dtype=np.float64)
+
+
+def subpixel_encode(rows, offsets, geom, ri, bits, want_codes=False, payload=None, nbytes=None, codes=None, orphans=None, scratch=None):
+    """The subpixel payloads of a batch (rpcc_subpixel_encode; specification: tests/subpixel_ref.py).  rows f32 [total,4] (x, y, z and a
+    fourth column that is not read), offsets i64 [B+1], ri f32 [B,H,W] the range image ops.project / the batch call made of THESE rows,
+    bits 1 .. 4 -> (payload u8 [B, 8+2P]: b"RPS1" | bits | 0 0 0 | the az codes of the non-empty pixels in raster order | their el codes,
+    nbytes i32 [B] = 8 + 2n, codes u8 [B,H,W,2] or None, orphans i32 [B]: non-empty pixels no row owns -- 0 whenever ri is the image of
+    these rows).  The bytes of a payload row past nbytes are left as they were.  payload .. scratch: the caller's buffers."""
+    if rows.dim() != 2 or rows.shape[1] != 4:
+        raise ValueError("subpixel_encode: rows [total,%s]; the stored 16-byte rows [total,4] are needed (packed xyz: add a zero column)"
+                         % (rows.shape[1] if rows.dim() == 2 else "?"))
+    assert rows.dtype == torch.float32 and ri.dtype == torch.float32
+    bits = check_subpixel_bits(bits)
+    B, P, dev = offsets.numel() - 1, geom.H * geom.W, _dev(offsets)
+    rows = rows.contiguous()
+    if payload is None:
+        payload = torch.empty((B, 8 + 2 * P), dtype=torch.uint8, device=dev)
+    if nbytes is None:
+        nbytes = torch.empty((B,), dtype=torch.int32, device=dev)
+    if orphans is None:
+        orphans = torch.empty((B,), dtype=torch.int32, device=dev)
+    if want_codes and codes is None:
+        codes = torch.empty((B, geom.H, geom.W, 2), dtype=torch.uint8, device=dev)
+    if scratch is None:
+        scratch = torch.empty(_lib.lib().rpcc_subpixel_scratch_bytes(B, P), dtype=torch.uint8, device=dev)
+    check(_lib.lib().rpcc_subpixel_encode(ptr(rows) if rows.numel() else None, ptr(offsets), rows.shape[0], B, geom, ptr(ri), bits, ptr(payload),
+                                          payload.stride(0), ptr(nbytes), ptr(codes) if want_codes else None, ptr(orphans), ptr(scratch),
+                                          scratch.numel(), stream()))
+    return payload, nbytes, (codes if want_codes else None), orphans
+
+
+def subpixel_decode(payload, nbytes, seg, ri_rec, tables, out=None, status=None):
+    """The way back (rpcc_subpixel_decode): payload u8 [B, >= 8+2P] rows, nbytes i32 [B], seg [B,H,W] uint8 or uint16 label maps (label 1:
+    an empty pixel), ri_rec f32 [B,H,W] the reconstructed ranges, tables f64 the device copy of subpixel_tables (PCTransformer.subpixel_tables)
+    -> (points f32 [B,H,W,3], +0.0 where the label is 1; status i32 [B]: _lib.STREAM_OK, or _lib.STREAM_E_SUBPIXEL for a refused row: zeros)."""
+    B, H, W = seg.shape
+    assert payload.dtype == torch.uint8 and payload.dim() == 2 and payload.shape[0] == B and payload.stride(1) == 1
+    assert seg.dtype in (torch.uint8, torch.uint16) and nbytes.dtype == torch.int32 and nbytes.numel() == B
+    assert ri_rec.dtype == torch.float32 and ri_rec.numel() == B * H * W
+    assert tables.dtype == torch.float64 and tables.numel() == 2 * H + 2 * W + 4 * SUBPIXEL_TABLE_CODES * 4, "tables: PCTransformer.subpixel_tables() of this geometry"
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.float32, device=_dev(seg))
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=_dev(seg))
+    check(_lib.lib().rpcc_subpixel_decode(C.c_void_p(payload.data_ptr()), payload.stride(0), ptr(nbytes), ptr(seg), seg.element_size(), ptr(ri_rec),
+                                          ptr(tables), H, W, B, ptr(out), ptr(status), stream()))
+    return out, status
+
+
 def _frame_ids(frame_ids, B, device):
     """Stable per-frame identities (datalist indices) as a device i64 [B] tensor, or None."""
     if frame_ids is None:

@@ -9,7 +9,7 @@ import torch
 
 from . import entropy, ops
 from . import _lib
-from .compress_utils import (BACKENDS, BEAM_TABLE_INTENSITY, BasicCompressor, BatchPayload, columns, device_decoder, frame_slices, intensity_trailer_span,
+from .compress_utils import (BACKENDS, BEAM_TABLE_INTENSITY, BEAM_TABLE_SUBPIXEL, BasicCompressor, BatchPayload, columns, device_decoder, frame_slices, intensity_trailer_span,
                              pack_bitstream, pack_frames, payload_spans, unpack_bitstream)  # noqa: F401
 
 
@@ -19,7 +19,7 @@ class BatchCompressor:
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
                  model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
                  device_entropy=False, device_bzip2=False, segment_method="FPS", DBSCAN_eps=1.5, max_labels=None,
-                 radius_outlier_removal=None, rans_delta=False, intensity_scale=None, point_format=None):
+                 radius_outlier_removal=None, rans_delta=False, intensity_scale=None, point_format=None, subpixel_bits=None):
         """point_format (None: float points, and nothing changes): "nclt" -- compress / submit take every frame as uint8 [N,8] NCLT
         velodyne_sync records (records.py); 8 bytes per point go up, records.unpack (librpcc_records.so) makes the stored rows on the
         device and run_batch reads them like any [N,4] rows, so every other option works behind it; with intensity_scale the payload
@@ -27,6 +27,9 @@ class BatchCompressor:
         intensity_scale (None: off, and no byte of any container changes): frames are [N,>=4] rows (x, y, z, intensity); after the
         batch call one ops.intensity_encode runs on the same point tensor and the batch's range images, and every container gets the
         'intensity' trailer (compress_utils.pack_bitstream), byte for byte the per-frame path's.  Independent of the segmentation.
+        subpixel_bits (None: off, and no byte of any container changes; else 1 .. 4): after the batch call one ops.subpixel_encode runs on
+        the same point tensor and the batch's range images, and every container gets the 'subpixel' trailer behind the intensity one, byte
+        for byte the per-frame path's.  Frames may be [N,3]: they get a zero fourth column on the host, the rows go up with stride 16.
         rans_delta (basic_compressor 'rans' only): the residual stream goes through the delta filter, as BasicCompressor(rans_delta=True)
         codes it on the per-frame path.
         segment_method "DBSCAN" (cfgs/compressor.yaml: segment_method, DBSCAN_eps): the frames are segmented by dbscan.dbscan_segment and
@@ -59,6 +62,9 @@ class BatchCompressor:
         self.intensity_scale = None if intensity_scale is None else ops.check_intensity_scale(intensity_scale)
         if self.intensity_scale is not None and getattr(transformer, "even_dist", True) is False:
             raise NotImplementedError("BatchCompressor: " + BEAM_TABLE_INTENSITY)
+        self.subpixel_bits = None if subpixel_bits is None else ops.check_subpixel_bits(subpixel_bits)
+        if self.subpixel_bits is not None and getattr(transformer, "even_dist", True) is False:
+            raise NotImplementedError("BatchCompressor: " + BEAM_TABLE_SUBPIXEL)
         # a transformer built from a per-beam elevation table (channel_distribute_csv): the projection goes through its index -- the fused
         # call's, the DBSCAN path's and the streaming loader's alike (all run_batch / _group_args); nothing behind the projection changes
         if getattr(transformer, "even_dist", True) is False and not self.dbscan and self.M > _lib.MAX_CLUSTERS_MID:
@@ -116,11 +122,30 @@ class BatchCompressor:
         ops.intensity_encode(rows, offsets, self.T.geom, buf.ri, self.intensity_scale, payload=pay, nbytes=nb, orphans=orphans,
                              scratch=buf.intensity_scratch)
 
+    def run_subpixel(self, rows, offsets, buf):
+        """subpixel_bits: the batch's subpixel payloads into buf.subpixel = (payload u8 [B, 8+2P], nbytes i32 [B], orphans i32 [B]), on the
+        current stream.  rows: the 16-byte rows the range images in buf.ri were made of (the NaN-masked ones with the radius filter)."""
+        if self.subpixel_bits is None:
+            return
+        if getattr(buf, "subpixel", None) is None:
+            B, P = buf.B, buf.P
+            buf.subpixel = (torch.empty((B, 8 + 2 * P), dtype=torch.uint8, device=self.device), torch.empty((B,), dtype=torch.int32, device=self.device),
+                            torch.empty((B,), dtype=torch.int32, device=self.device))
+            buf.subpixel_scratch = torch.empty(_lib.lib().rpcc_subpixel_scratch_bytes(B, P), dtype=torch.uint8, device=self.device)
+        pay, nb, orphans = buf.subpixel
+        ops.subpixel_encode(rows, offsets, self.T.geom, buf.ri, self.subpixel_bits, payload=pay, nbytes=nb, orphans=orphans,
+                            scratch=buf.subpixel_scratch)
+
+    def run_trailers(self, rows, offsets, buf):
+        """The optional channels behind the batch call, in container order."""
+        self.run_intensity(rows, offsets, buf)
+        self.run_subpixel(rows, offsets, buf)
+
     @staticmethod
-    def check_orphans(orphans):
+    def check_orphans(orphans, channel="intensity"):
         if np.any(orphans):
-            raise _lib.RpccError("intensity: frames %s have non-empty pixels no row owns (the range image is not the image of these rows)"
-                                 % np.flatnonzero(orphans).tolist())
+            raise _lib.RpccError("%s: frames %s have non-empty pixels no row owns (the range image is not the image of these rows)"
+                                 % (channel, np.flatnonzero(orphans).tolist()))
 
     def run_batch(self, xyz, offsets, ground, buf, frame_ids=None, fit_ground=True):
         """The device work of one batch into buf, on the current stream, nothing waited for.  ground f64 [B,4]: fitted here (fit_ground: the
@@ -135,7 +160,7 @@ class BatchCompressor:
             ops.compress_batch(xyz, offsets, self.T.tm_dev, ground, buf, self.ground_threshold, self.acc,
                                ground_seed=self.seed if fit_ground else -1, frame_ids=frame_ids, model_method=self.model_method,
                                angle_threshold=angle, plane_seed=self.seed, nonuniform=nu, beams=self.beams)
-            self.run_intensity(xyz, offsets, buf)
+            self.run_trailers(xyz, offsets, buf)
             return
         from .dbscan import dbscan_segment
         tm = self.T.tm_dev
@@ -146,7 +171,7 @@ class BatchCompressor:
         labels, top = dbscan_segment(buf.ri, tm, ground, self.eps, min_points=10, check=False)
         ops.compress_batch_labels(buf.ri, tm, ground, labels, top, buf, self.acc, model_method=self.model_method, angle_threshold=angle,
                                   plane_seed=self.seed, frame_ids=frame_ids, nonuniform=nu)
-        self.run_intensity(xyz, offsets, buf)
+        self.run_trailers(xyz, offsets, buf)
 
     def check_status(self, status):
         """status: a batch's buf.status on the host (None for FPS).  Raises RpccError naming the refused frames (their places in the batch)
@@ -209,7 +234,7 @@ class BatchCompressor:
             return self._encode(dict(buf=buf, ground=g))
         args = self._group_args(self._filtered(xyz, offsets), offsets, ground, frame_ids)
         ops.compress_batch(ground_threshold=self.ground_threshold, acc=self.acc, **args)
-        self.run_intensity(args["xyz"], offsets, args["buf"])
+        self.run_trailers(args["xyz"], offsets, args["buf"])
         return self._encode(args)
 
     def _upload(self, frames, ground=None):
@@ -221,6 +246,9 @@ class BatchCompressor:
         cols = 3 if self.intensity_scale is None else 4     # (with intensity the rows go up as stored: the kernels read them with stride 16)
         if cols == 4 and any(f.ndim != 2 or f.shape[1] < 4 for f in frames):
             raise ValueError("BatchCompressor(intensity_scale=...): frames must be [N,>=4] rows (x, y, z, intensity)")
+        if cols == 3 and self.subpixel_bits is not None:     # the owner pass reads 16-byte rows: xyz and a zero fourth column where a frame has none
+            from .compress_utils import rows16
+            frames, cols = [rows16(f) for f in frames], 4
         xyz = torch.from_numpy(np.ascontiguousarray(np.concatenate([f[:, :cols] for f in frames]), dtype=np.float32)).to(self.device)
         gnd = None if ground is None else torch.from_numpy(np.asarray(ground, np.float64).reshape(-1, 4)).to(self.device)
         return xyz, torch.from_numpy(offs).to(self.device), gnd, int(offs[-1])
@@ -247,8 +275,9 @@ class BatchCompressor:
         buf.in_flight = True    # until collect() has read it (_buffers)
         # the batch's buffer of every column (compress_utils.SCHEMA; frame_slices cuts the frames out of them) and the per-frame counts
         pay, nbytes, _ = buf.intensity if self.intensity_scale is not None else (None, None, None)
-        bufs = dict(salience_level=sal, contour_map=bits, idx_sequence=sp, plane_param=buf.model, residual_quantized=qp, intensity=pay)
-        ctx = dict(n=n, buf=buf, bufs=bufs, counts=(buf.counts, buf.nnz, nseq, nbytes), tot=dict(nnz=qtot, nseq=stot),
+        spay, nsub, _ = buf.subpixel if self.subpixel_bits is not None else (None, None, None)
+        bufs = dict(salience_level=sal, contour_map=bits, idx_sequence=sp, plane_param=buf.model, residual_quantized=qp, intensity=pay, subpixel=spay)
+        ctx = dict(n=n, buf=buf, bufs=bufs, counts=(buf.counts, buf.nnz, nseq, nbytes, nsub), tot=dict(nnz=qtot, nseq=stot),
                    stream=torch.cuda.current_stream(self.device), keep=(xyz, g, seq))
         codec = self.bc.batch_codec()
         if codec:
@@ -257,9 +286,9 @@ class BatchCompressor:
 
     @property
     def columns(self):
-        return columns(self.uniform, self.intensity_scale is not None)
+        return columns(self.uniform, self.intensity_scale is not None, self.subpixel_bits is not None)
 
-    def _device_containers(self, codec, bufs, counts, nnz, nseq, nbytes):
+    def _device_containers(self, codec, bufs, counts, nnz, nseq, nbytes, nsub=None):
         """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), 'deflate' / 'gzip' with device_entropy (deflate_codec),
         'bzip2' with device_bzip2 (bzip2_codec) or 'rans' (rans_codec, a typed back-end: it is also told each column's element width, as
         the per-frame path takes it from the arrays' itemsize, and -- with rans_delta -- each column's filter, by the same rule from its
@@ -268,7 +297,7 @@ class BatchCompressor:
         asks nothing of the streams' format) on the current stream.  -> (containers, frame offsets / lengths)."""
         from . import lz4_codec
         (B, K), P, cols = counts.shape, self.T.H * self.T.W, self.columns
-        at = frame_slices(cols, bufs, counts, nnz, nseq, nbytes)
+        at = frame_slices(cols, bufs, counts, nnz, nseq, nbytes, nsub)
         # per frame, in container order: device address and bytes of every column
         addr = torch.stack([bufs[c.name].data_ptr() + c.dtype.itemsize * at[c.name][0] for c in cols], 1).reshape(-1)
         lens = torch.stack([c.dtype.itemsize * at[c.name][1] for c in cols], 1).reshape(-1)
@@ -297,22 +326,25 @@ class BatchCompressor:
                 fr = built[1].cpu().numpy()
             else:           # the columns' buffers, the packed ones as far as the batch filled them
                 bufs, tot, cols = ctx["bufs"], ctx["tot"], self.columns
-                counts, nnz, nseq, nbytes = (None if t is None else t.cpu().numpy() for t in ctx["counts"])
+                counts, nnz, nseq, nbytes, nsub = (None if t is None else t.cpu().numpy() for t in ctx["counts"])
                 host = {c.name: (bufs[c.name][: int(tot[c.cut].item())] if c.cut in tot else bufs[c.name]).cpu().numpy() for c in cols}
             status = buf.status.cpu().numpy() if self.dbscan else None
             orphans = buf.intensity[2].cpu().numpy() if self.intensity_scale is not None else None
+            sub_orphans = buf.subpixel[2].cpu().numpy() if self.subpixel_bits is not None else None
         finally:
             buf.in_flight = False   # everything collect() needs is on the host -- or the call failed: either way the slot is free again
         n = ctx["n"]
         self.check_status(status)
         if orphans is not None:
             self.check_orphans(orphans[:n])
+        if sub_orphans is not None:
+            self.check_orphans(sub_orphans[:n], "subpixel")
         if built:
             if (fr[1, :n] < 0).any():
                 raise RuntimeError("rpcc_lz4: the containers of frames %s were not built" % np.flatnonzero(fr[1, :n] < 0).tolist())
             h = built[0][: int((fr[0, :n] + fr[1, :n]).max()) if n else 0].cpu().numpy()
             return [h[o: o + l].tobytes() for o, l in zip(fr[0, :n], fr[1, :n])]
-        assemble = BatchPayload(cols, host, counts, nnz, nseq, nbytes).frame      # the object the streaming loader assembles from
+        assemble = BatchPayload(cols, host, counts, nnz, nseq, nbytes, nsub=nsub).frame      # the object the streaming loader assembles from
         # a few frames per task: one call into the host library per chunk (compress_utils.pack_frames)
         step = max(1, n // 64) if pool is not None else max(n, 1)
         chunk = lambda lo: pack_frames(self.bc, [assemble(b) for b in range(lo, min(lo + step, n))], uniform=self.uniform)
@@ -351,6 +383,9 @@ class MixedBatchCompressor:
         if kw.get("intensity_scale") is not None:
             raise NotImplementedError("MixedBatchCompressor: intensity_scale -- the mixed-geometry call carries no intensity; use one "
                                       "BatchCompressor(intensity_scale=...) per lidar")
+        if kw.get("subpixel_bits") is not None:
+            raise NotImplementedError("MixedBatchCompressor: subpixel_bits -- the mixed-geometry call carries no subpixel offsets; use one "
+                                      "BatchCompressor(subpixel_bits=...) per lidar")
         if kw.get("radius_outlier_removal") is not None:
             raise NotImplementedError("MixedBatchCompressor: radius_outlier_removal -- the mixed-geometry call takes the points as they are; "
                                       "filter them first (outlier.radius_outlier_mask), or use one BatchCompressor per lidar")
@@ -403,7 +438,8 @@ STREAM_TEXT = {_lib.STREAM_E_ENTROPY: "an entropy stream was refused by the devi
                _lib.STREAM_E_SALIENCE: "salience_level does not fit the model rows or the configured levels",
                _lib.STREAM_E_RESIDUAL: "residual_quantized does not hold one value per non-empty pixel of the label map",
                _lib.STREAM_E_CONTAINER: "the container's length prefixes do not fit its bytes",
-               _lib.STREAM_E_INTENSITY: "no valid intensity payload follows the geometry (compressed without intensity, or the payload does not fit the label map)"}
+               _lib.STREAM_E_INTENSITY: "no valid intensity payload follows the geometry (compressed without intensity, or the payload does not fit the label map; a "
+                                        "container that also carries the subpixel trailer gives its intensity on the per-frame path only)"}
 
 
 def container_spans(blob, uniform=True):
@@ -431,10 +467,13 @@ class BatchDecompressor:
     CHUNK_BUDGET_BYTES = 2 << 30   # device bytes one chunk may take: padded payloads, bzip2 work slots, work buffer and outputs
 
     def __init__(self, transformer, cluster_num, accuracy, uniform=True, level_acc=None, basic_compressor="bzip2", max_labels=None,
-                 intensity=False):
+                 intensity=False, subpixel=False):
         """intensity=True: every container must carry the 'intensity' trailer (BatchCompressor(intensity_scale=...), --intensity):
         decompress_device returns a fifth tensor, f32 [B,H,W], decompress 4-tuples; a frame without a valid trailer gets
         _lib.STREAM_E_INTENSITY (unless an earlier status applies) and a zero row.  The scale is read from each payload's header."""
+        if subpixel:
+            raise NotImplementedError("BatchDecompressor: subpixel -- the batch decoder back-projects along the pixels' centre rays; decode "
+                                      "containers with the subpixel trailer per frame (tools.decompress.decode_frame(..., subpixel=True))")
         self.intensity = bool(intensity)
         self.per_frame_rows = cluster_num is None     # DBSCAN streams
         if cluster_num is None:

@@ -24,7 +24,7 @@ from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.loader import StreamingCompressor  # noqa: E402
 from rpcc_amd.pipeline import BatchCompressor  # noqa: E402
 from rpcc_amd.sharding import RoundGather, shard_indices  # noqa: E402
-from rpcc_amd.tools.compress import apply_fps_mode, make_parser, point_format_of, resolve_cfg  # noqa: E402
+from rpcc_amd.tools.compress import apply_fps_mode, make_parser, point_format_of, resolve_cfg, subpixel_bits_of  # noqa: E402
 from rpcc_amd.utils import available_cpus, frame_identity, local_rank_env, pin_rank_cpus  # noqa: E402
 
 
@@ -83,8 +83,8 @@ def init_gather_group(rank, world, local):
     return dist
 
 
-def resolve_ingest(want, names, intensity=False, point_format=None):
-    """The ingest mode of a whole datalist (--ingest, --intensity, --input_format; names: its file names) -> "rows", "xyz" or "nclt";
+def resolve_ingest(want, names, intensity=False, point_format=None, subpixel=False):
+    """The ingest mode of a whole datalist (--ingest, --intensity, --subpixel, --input_format; names: its file names) -> "rows", "xyz" or "nclt";
     SystemExit for a combination the options exclude.  --input_format nclt always stages the records themselves (8 bytes per point,
     the intensity byte among them), so it goes with --ingest auto only."""
     all_bin = all(str(name).endswith(".bin") for name in names)
@@ -95,6 +95,11 @@ def resolve_ingest(want, names, intensity=False, point_format=None):
     if intensity:      # the fourth column must reach the device: the rows as stored
         if not all_bin or want == "xyz":
             raise SystemExit("--intensity needs a datalist of .bin files (float32 rows x, y, z, intensity)" + (" and not --ingest xyz" if want == "xyz" else ""))
+        want = "rows"
+    if subpixel:       # the owner pass reads 16-byte rows, and only .bin files are staged as such (a limit of the streaming loader: BatchCompressor pads [N,3] frames)
+        if not all_bin or want == "xyz":
+            raise SystemExit("--subpixel on a datalist needs .bin files: its kernels read 16-byte rows, which the streaming loader stages from .bin files "
+                             "only (the fourth column is not read)" + ("; --ingest xyz stages 12-byte points" if want == "xyz" else ""))
         want = "rows"
     if want == "rows" and not all_bin:
         raise SystemExit("--ingest rows needs a datalist of .bin files (float32 rows x, y, z, intensity)")
@@ -130,11 +135,13 @@ def compress(args, streaming_factory=None):
                          segment_method=segment_cfg["segment_method"], DBSCAN_eps=segment_cfg["DBSCAN_eps"],
                          max_labels=getattr(args, "max_labels", None),
                          radius_outlier_removal=(3, 1.0) if getattr(args, "use_radius_outlier_removal", False) else None,
-                         intensity_scale=args.intensity_scale if getattr(args, "intensity", False) else None)
+                         intensity_scale=args.intensity_scale if getattr(args, "intensity", False) else None,
+                         subpixel_bits=subpixel_bits_of(args))
     mine = shard_indices(len(dataset), rank, world)
     # the ingest mode follows from the WHOLE datalist -- the same decision on every rank, also on one whose shard is empty -- and is
     # settled before the process group forms, so that a datalist --ingest rows cannot take fails on all ranks together
-    ingest = resolve_ingest(getattr(args, "ingest", "auto"), dataset.data_list, getattr(args, "intensity", False), point_format_of(args))
+    ingest = resolve_ingest(getattr(args, "ingest", "auto"), dataset.data_list, getattr(args, "intensity", False), point_format_of(args),
+                            subpixel=subpixel_bits_of(args) is not None)
     gather = None
     if getattr(args, "gather", False):
         import torch

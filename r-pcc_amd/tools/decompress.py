@@ -15,7 +15,7 @@ import torch  # noqa: E402
 
 import rpcc_amd  # noqa: E402,F401
 from rpcc_amd import ops  # noqa: E402
-from rpcc_amd.compress_utils import decompress_point_cloud, parse_intensity_payload, read_compressed_bitstream  # noqa: E402,F401
+from rpcc_amd.compress_utils import decompress_point_cloud, parse_intensity_payload, parse_subpixel_payload, read_compressed_bitstream  # noqa: E402,F401
 from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.tools.compress import make_parser, point_format_of, print_intensity_error, print_quality, resolve_cfg  # noqa: E402
 
@@ -27,12 +27,14 @@ def stream_cluster_num(segment_cfg):
 
 
 def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy, level_acc, uniform, want_points=True, decoded=None,
-                 intensity=False):
+                 intensity=False, subpixel=False):
     """decompress_point_cloud + dequantise + predict + back-project (tools/decompress.py:79-112).  cluster_num None
     (DBSCAN, stream_cluster_num): the labels 0 .. rows - 1 of the stream's model rows.  decoded: blob_dict's arrays with the entropy
     stage already undone (basic_compressor.decompress_dicts over a chunk of frames).
     intensity=True: blob_dict holds the container's 'intensity' trailer (unpack_bitstream(..., intensity=True)); a fourth value is
-    returned, f32 [H,W], by ops.intensity_decode on the label map just recovered; ValueError when the payload is refused."""
+    returned, f32 [H,W], by ops.intensity_decode on the label map just recovered; ValueError when the payload is refused.
+    subpixel=True: blob_dict holds the 'subpixel' trailer (unpack_bitstream(..., subpixel=True)); the points come from ops.subpixel_decode
+    -- every non-empty pixel's ray turned by its two coded offsets -- instead of ops.backproject; ValueError when the payload is refused."""
     H, W = transformer.H, transformer.W
     d = basic_compressor.decompress_dict(blob_dict) if decoded is None else decoded
     # The .rpcc file stores no configuration (as in the reference): a wrong --lidar / cluster_num / framework shows up as
@@ -81,13 +83,27 @@ def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy
     if qq.size != n_nonempty:
         raise ValueError("residual_quantized holds %d values, the label map has %d non-empty pixels" % (qq.size, n_nonempty))
     q[0, : qq.size] = torch.from_numpy(qq.copy()).to(dev)
+    if subpixel:
+        if "subpixel" not in d:
+            raise ValueError("the bitstream holds no subpixel payload (compressed without --subpixel?)")
+        parse_subpixel_payload(d["subpixel"], n_nonempty)     # (the refusals in words; the device decoder checks the same)
+        tables = transformer.subpixel_tables()
+    centre_rays = want_points and not subpixel
     if uniform:
-        rec, pc = ops.decode(seg, q, model, transformer.tm_dev, accuracy, want_points=want_points)
+        rec, pc = ops.decode(seg, q, model, transformer.tm_dev, accuracy, want_points=centre_rays)
     else:
         sal = torch.zeros((1, K), dtype=torch.uint8, device=dev)
         sl = np.frombuffer(d["salience_level"], dtype=np.uint8)
         sal[0, : sl.size] = torch.from_numpy(sl.copy()).to(dev)
-        rec, pc = ops.decode(seg, q, model, transformer.tm_dev, list(level_acc), salience=sal, want_points=want_points)
+        rec, pc = ops.decode(seg, q, model, transformer.tm_dev, list(level_acc), salience=sal, want_points=centre_rays)
+    if subpixel and want_points:
+        pay = torch.from_numpy(np.frombuffer(d["subpixel"], dtype=np.uint8).copy()[None]).to(dev)
+        nbytes = torch.tensor([pay.shape[1]], dtype=torch.int32, device=dev)
+        if pay.shape[1] < 8 + 2 * P:      # rpcc_subpixel_decode takes rows of at least 8 + 2P bytes
+            pay = torch.cat([pay, torch.zeros((1, 8 + 2 * P - pay.shape[1]), dtype=torch.uint8, device=dev)], 1)
+        pc, status = ops.subpixel_decode(pay, nbytes, seg, rec.reshape(1, H, W).contiguous(), tables)
+        if int(status[0]) != 0:
+            raise ValueError("subpixel payload refused by the device decoder (status %d)" % int(status[0]))
     out = rec[0].cpu().numpy(), (pc[0].cpu().numpy() if pc is not None else None), seg[0].cpu().numpy()
     if not intensity:
         return out
@@ -113,10 +129,10 @@ def decompress(args):
                             point_format=point_format_of(args))
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     t0 = time.time()
-    want_w = getattr(args, "intensity", False)
-    cd = read_compressed_bitstream(args.input, uniform=uniform, intensity=want_w)
+    want_w, want_s = getattr(args, "intensity", False), getattr(args, "subpixel", None) is not None
+    cd = read_compressed_bitstream(args.input, uniform=uniform, intensity=want_w, subpixel=want_s)
     rec, pc, seg, *w = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
-                                    level_acc, uniform, intensity=want_w)
+                                    level_acc, uniform, intensity=want_w, subpixel=want_s)
     t1 = time.time()
     dataset.save_point_cloud_to_file(args.output, pc.reshape(-1, 3), intensity=w[0].reshape(-1) if want_w else None)
     print("\nDecompression finished.")
@@ -125,7 +141,7 @@ def decompress(args):
     print("    Points: ", int((rec != 0).sum()))
     if args.eval:
         print("\nStart evaluation...")
-        point_cloud, range_image, _ = dataset.load_range_image_points_from_file(args.original_point_cloud)
+        point_cloud, range_image, original = dataset.load_range_image_points_from_file(args.original_point_cloud)
         n_points = int((range_image != 0).sum())
         dif = np.abs(rec - range_image[..., 0])
         bits = os.path.getsize(args.input) * 8
@@ -134,7 +150,7 @@ def decompress(args):
         print("    Compression Ratio: ", (n_points * 32 * 3) / bits)
         print("    Depth Error (mean): ", float(np.mean(dif)))
         print("    Depth Error (max): ", float(np.max(dif)))
-        print_quality(point_cloud, pc)
+        print_quality(original if want_s else point_cloud, pc, refined=want_s)
         if want_w:
             print_intensity_error(dataset.PCTransformer, dataset.load_rows(args.original_point_cloud), range_image[..., 0], w[0])
 

@@ -65,6 +65,10 @@ def decompress(args):
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
+    if getattr(args, "batch_decode", False) and getattr(args, "subpixel", None) is not None:     # (before anything is read or built)
+        raise NotImplementedError("--%s with --subpixel: the batch decoder back-projects along the pixels' centre rays; decode containers with "
+                                  "the subpixel trailer without --batch_decode / --stream_decode (the per-frame path)"
+                                  % ("stream_decode" if getattr(args, "stream_decode", False) else "batch_decode"))
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
     # (--input_format: how the dataset reads original point files; this tool reads none, its outputs are float .bin files either way)
     dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device,
@@ -75,11 +79,11 @@ def decompress(args):
         return decompress_batched(args, dataset, mine, stream_cluster_num(segment_cfg), accuracy, level_acc, uniform, basic_compressor)
     for c0 in range(0, len(mine), CHUNK):
         names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
-        want_w = getattr(args, "intensity", False)
-        cds = [read_compressed_bitstream(name, uniform=uniform, intensity=want_w) for name in names]
+        want_w, want_s = getattr(args, "intensity", False), getattr(args, "subpixel", None) is not None
+        cds = [read_compressed_bitstream(name, uniform=uniform, intensity=want_w, subpixel=want_s) for name in names]
         for name, cd, d in zip(names, cds, basic_compressor.decompress_dicts(cds)):   # the chunk's entropy stage in one call where the back-end has one
             rec, pc, _, *w = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
-                                          level_acc, uniform, decoded=d, intensity=want_w)
+                                          level_acc, uniform, decoded=d, intensity=want_w, subpixel=want_s)
             rel = name[1:] if name.startswith("/") else name
             out = os.path.join(args.output_dir, rel)
             out = out.replace(out.split(".")[-1], "bin")

@@ -47,6 +47,7 @@ class PCTransformer:
         self.geom = ops.make_geom(self.H, self.W, self.horizontal_FOV, self.vertical_max, self.vertical_min)
         self._tm_dev = None
         self._beams_dev = None
+        self._subpixel_dev = None
 
     def create_transform_map(self):
         """dataset/transformer.py:41-54."""
@@ -61,6 +62,17 @@ class PCTransformer:
         if self._beams_dev is None:
             self._beams_dev = ops.beam_index(self.vertical_angle, self.device)
         return self._beams_dev
+
+    def subpixel_tables(self):
+        """The f64 table ops.subpixel_decode reads (ops.subpixel_tables), built once and uploaded once.  Evenly spaced beams only: the
+        subpixel channel's rows are the even projection's."""
+        if not self.even_dist:
+            from .compress_utils import BEAM_TABLE_SUBPIXEL
+            raise NotImplementedError(BEAM_TABLE_SUBPIXEL)
+        if self._subpixel_dev is None:
+            self._subpixel_dev = torch.from_numpy(ops.subpixel_tables(self.H, self.W, self.horizontal_FOV, self.vertical_max,
+                                                                      self.vertical_min)).to(self.device)
+        return self._subpixel_dev
 
     @property
     def tm_dev(self):

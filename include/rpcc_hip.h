@@ -211,6 +211,43 @@ int rpcc_subpixel_encode(const float *rows, const int64_t *offsets, int64_t tota
 int rpcc_subpixel_decode(const uint8_t *payload, int64_t payload_stride, const int32_t *nbytes, const void *labels, int label_bytes,
                          const float *ri_rec, const double *tables, int H, int W, int B, float *points, int32_t *status, void *stream);
 
+/* ---- hidden_points: the points that share a pixel with its owner ---------------------------------- *
+ * The range image keeps one point per pixel; these entries carry the others.  The specification is stated once, in tests/hidden_ref.py
+ * (new exports under interface version 105; no existing struct or argument changes):
+ *   skipped   a row whose depth from the projection's sequence is NaN, infinite or 0, as rpcc_project skips it
+ *   owner     the intensity channel's (above); every other row whose pixel is non-empty is a hidden point of that pixel -- a row of equal
+ *             depth bits that comes later, a row in front of a later depth-0 row of its pixel (it may be nearer than the owner)
+ *   range     k = rintf(d / step), one IEEE fp32 division, half to even; a point with !(k <= 65535) is not carried; the decoded range is
+ *             (float)k * step, one fp32 multiply: |r - d| <= step * (0.5 + k * 2^-23)
+ *   lateral   bits 0 .. 4; for bits > 0 the subpixel codes of the point's own off_az / off_el against its pixel, else 0
+ *   order     key = k << 8 | az << 4 | el; by pixel in raster order, then by key; at most the 255 smallest keys of a pixel are carried
+ *   uncarried hidden points in an empty pixel (ri == 0), with k past 65535 or past the 255 of their pixel: counted per frame, never an error
+ *   payload   "RPH1", bits, three zero bytes, step as little-endian f32, m as little-endian u32, one count byte per non-empty pixel in
+ *             raster order [n], the k values as little-endian u16 [m], and for bits > 0 the az codes [m] and the el codes [m]:
+ *             16 + n + 2m bytes, or 16 + n + 4m
+ * rpcc_hidden_encode: rows / offsets / ri as rpcc_intensity_encode takes them; step finite and > 0; bits 0 .. 4.  Out: payload dev u8 rows
+ * of payload_stride >= 16 + P bytes -- 16 + P + 4 N holds every frame of at most N rows; a frame whose payload is longer than the row
+ * gets nbytes -1 and only its header and count plane are written --, nbytes dev i32 [B], orphans dev i32 [B] as for the subpixel entry,
+ * uncarried dev i32 [B].  scratch: rpcc_hidden_scratch_bytes(B, P, total) bytes, no initialisation needed.  Atomics count and hand out
+ * slots only; the bytes do not depend on scheduling.
+ * rpcc_hidden_decode: labels dev [B,P] of label_bytes 1 or 2, tm dev f32 [P,3] the transform map (bits 0: r * tm, the multiply of
+ * rpcc_backproject), tables as rpcc_subpixel_decode takes them or NULL (bits > 0: the pixel's ray turned by the two offsets through the
+ * same fp64 expressions).  Out: points dev f32 [B, capacity, 3], frame b's m_b points in payload order, the rest left as it is; count dev
+ * i32 [B] = m_b; status dev i32 [B] = RPCC_STREAM_OK, or RPCC_STREAM_E_HIDDEN (count 0, no point written, no byte used as an index) unless
+ * 16 <= nbytes[b] <= payload_stride, the magic matches, bits <= 4 and the reserved bytes are 0, step is finite and > 0, the labels other
+ * than 1 number n, nbytes[b] is the length above, the counts sum to m, m <= capacity, every az / el code is below 2^bits, and tables is
+ * not NULL when bits > 0.
+ * Argument errors return RPCC_ERR_ARG before the device is touched, as for the subpixel entries; besides, 16 + P + 4 total must stay
+ * below 2^31 (rpcc_hidden_scratch_bytes returns 0 above it). */
+#define RPCC_STREAM_E_HIDDEN 12 /* rpcc_hidden_decode */
+size_t rpcc_hidden_scratch_bytes(int B, int P, int64_t total);
+int rpcc_hidden_encode(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, float step, int bits,
+                       uint8_t *payload, int64_t payload_stride, int32_t *nbytes, int32_t *orphans, int32_t *uncarried, void *scratch,
+                       size_t scratch_bytes, void *stream);
+int rpcc_hidden_decode(const uint8_t *payload, int64_t payload_stride, const int32_t *nbytes, const void *labels, int label_bytes,
+                       const float *tm, const double *tables, int H, int W, int B, float *points, int64_t capacity, int32_t *count,
+                       int32_t *status, void *stream);
+
 /* ---- a4: ground plane ----------------------------------------------------------------------- *
  * replaces the ground branch of PointCloudSegment.segment: candidate selection + RANSAC
  * (utils/segment_utils.py:74-82,101-108).  The reference uses Open3D segment_plane on an unseeded

@@ -51,6 +51,7 @@ STREAM_OK, STREAM_E_ENTROPY, STREAM_E_PLANE, STREAM_E_CONTOUR, STREAM_E_WIDTH = 
 STREAM_E_NSEQ, STREAM_E_LABEL, STREAM_E_SALIENCE, STREAM_E_RESIDUAL, STREAM_E_CONTAINER = 5, 6, 7, 8, 9
 STREAM_E_INTENSITY = 10   # RPCC_STREAM_E_INTENSITY (rpcc_intensity_decode; no valid intensity trailer where one was asked for)
 STREAM_E_SUBPIXEL = 11    # RPCC_STREAM_E_SUBPIXEL (rpcc_subpixel_decode; no valid subpixel payload)
+STREAM_E_HIDDEN = 12      # RPCC_STREAM_E_HIDDEN (rpcc_hidden_decode; no valid hidden_points payload)
 LABELS_OK, LABELS_E_RANGE, LABELS_E_CAPPED = 0, 1, 2     # RPCC_LABELS_* (rpcc_compress_batch_labels)
 BEAM_MAX_H = 128       # RPCC_BEAM_MAX_H (csrc/beam_index.h): rows of a per-beam elevation table
 ABI_VERSION = 105      # RPCC_ABI_VERSION: the layout of rpcc_batch_io / rpcc_geom this binding was written for
@@ -90,6 +91,9 @@ _SIGS = {
     "rpcc_subpixel_scratch_bytes": (C.c_size_t, [_I, _I]),
     "rpcc_subpixel_encode": (C.c_int, [_VP, _VP, _I64, _I, Geom, _VP, _I, _VP, _I64, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "rpcc_subpixel_decode": (C.c_int, [_VP, _I64, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
+    "rpcc_hidden_scratch_bytes": (C.c_size_t, [_I, _I, _I64]),
+    "rpcc_hidden_encode": (C.c_int, [_VP, _VP, _I64, _I, Geom, _VP, _F, _I, _VP, _I64, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "rpcc_hidden_decode": (C.c_int, [_VP, _I64, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _VP, _I64, _VP, _VP, _VP]),
     "rpcc_ground_ransac": (C.c_int, [_VP, _VP, _I, _I, C.c_uint32, _VP, _VP, _VP, _VP]),
     "rpcc_ground_mask": (C.c_int, [_VP, _VP, _VP, _D, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "rpcc_fps_table_bytes": (C.c_size_t, [_I, _I, _I]),

@@ -97,15 +97,17 @@ class QuantizationModule:
 
 def compress_point_cloud(basic_compressor, plane_param, cluster_idx, salience_level, nonzero_residual_quantized,
                          ground_residual_quantized=None, cluster_residual_quantized=None, point_cloud=None,
-                         range_image=None, full=False, intensity=None, subpixel=None):
+                         range_image=None, full=False, intensity=None, subpixel=None, hidden_points=None):
     """utils/compress_utils.py:138-164: casts + contour + packbits + per-array entropy coding.  intensity (not the reference's): the
     uint8 payload of ops.intensity_encode, coded like any other array and appended to the container by pack_bitstream.  subpixel: the
-    uint8 payload of ops.subpixel_encode, alike, behind it."""
+    uint8 payload of ops.subpixel_encode, alike, behind it.  hidden_points: the uint8 payload of ops.hidden_encode, alike, last."""
     original_data = {"residual_quantized": np.asarray(nonzero_residual_quantized).astype(np.int16)}
     if intensity is not None:
         original_data["intensity"] = np.ascontiguousarray(intensity, dtype=np.uint8)
     if subpixel is not None:
         original_data["subpixel"] = np.ascontiguousarray(subpixel, dtype=np.uint8)
+    if hidden_points is not None:
+        original_data["hidden_points"] = np.ascontiguousarray(hidden_points, dtype=np.uint8)
     if full:
         if point_cloud is not None:
             original_data["point_cloud"] = point_cloud.astype(np.float32)
@@ -136,20 +138,23 @@ SCHEMA = (Column("salience_level", np.dtype(np.uint8), lambda P, K: K, "nrow"),
           Column("residual_quantized", np.dtype(np.int16), lambda P, K: 2 * P, "nnz"),
           Column("intensity", np.dtype(np.uint8), lambda P, K: 8 + P, "nbytes"),
           Column("subpixel", np.dtype(np.uint8), lambda P, K: 8 + 2 * P, "nsub"))
+# The hidden_points column stands beside SCHEMA: its bound needs the frame's point count N besides P (16 + P + 4 N)
+HIDDEN_COLUMN = Column("hidden_points", np.dtype(np.uint8), lambda P, K, N=0: 16 + P + 4 * N, "nhid")
 INTENSITY_MAGIC = b"RPI1"
 SUBPIXEL_MAGIC = b"RPS1"
-TRAILERS = ("intensity", "subpixel")      # the optional columns behind the geometry, in file order
+HIDDEN_MAGIC = b"RPH1"
+TRAILERS = ("intensity", "subpixel", "hidden_points")      # the optional columns behind the geometry, in file order
 
 
-def columns(uniform, intensity=False, subpixel=False):
+def columns(uniform, intensity=False, subpixel=False, hidden_points=False):
     """The rows of SCHEMA a container holds, in file order: salience first with the non-uniform framework, then the trailers no
-    reference reader looks at, where they are carried: intensity, then subpixel."""
-    return SCHEMA[1 if uniform else 0: 5] + tuple(c for c, on in zip(SCHEMA[5:], (intensity, subpixel)) if on)
+    reference reader looks at, where they are carried: intensity, then subpixel, then hidden_points (HIDDEN_COLUMN)."""
+    return SCHEMA[1 if uniform else 0: 5] + tuple(c for c, on in zip(SCHEMA[5:] + (HIDDEN_COLUMN,), (intensity, subpixel, hidden_points)) if on)
 
 
 def _keys(uniform, data=()):
-    """The arrays of a container in file order; 'intensity' and 'subpixel' where the frame holds them."""
-    return tuple(c.name for c in columns(uniform, "intensity" in data, "subpixel" in data))
+    """The arrays of a container in file order; 'intensity', 'subpixel' and 'hidden_points' where the frame holds them."""
+    return tuple(c.name for c in columns(uniform, "intensity" in data, "subpixel" in data, "hidden_points" in data))
 
 
 def payload_spans(blob, count):
@@ -166,12 +171,13 @@ def payload_spans(blob, count):
         off += 4 + n
 
 
-def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None, nsub=None):
+def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None, nsub=None, nhid=None):
     """Which elements of which buffer are frame b's column c, stated once for the host assembly (BatchPayload: arrays read back or pinned)
     and for the device containers (addresses).  buffers: {column name: the batch's buffer}; counts [B,K], nnz / nseq / nbytes / nsub [B] -- all
     numpy arrays or all torch tensors of one device.  -> {name: (start, length)}, int64 [B] of the same kind, in elements of the column's
     dtype into the flattened buffer.  By the column's cut: 'row', 'nrow', 'nbytes' and 'nsub' columns are rows of a padded [B, ...] array -- the
-    whole row, its first nrow sub-rows, its first nbytes / nsub elements (the lengths of the intensity and the subpixel payloads); 'nseq' and 'nnz' columns lie packed back to back, frame b at the sum of
+    whole row, its first nrow sub-rows, its first nbytes / nsub / nhid elements (the lengths of the intensity, the subpixel and the hidden_points
+    payloads; nhid cuts the 'hidden_points' column alike); 'nseq' and 'nnz' columns lie packed back to back, frame b at the sum of
     the counts before it.  nrow = max(seg) + 1 (tools/compress.py:102) = 1 + the index of the last non-zero count; 0 for a row of zeros,
     which no frame has (its counts sum to P)."""
     if torch.is_tensor(counts):
@@ -180,7 +186,7 @@ def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None, nsub=None):
         xp, i64, ar = np, (lambda v: np.asarray(v, np.int64)), (lambda lo, hi: np.arange(lo, hi, dtype=np.int64))
     B, K = counts.shape
     n = {"nrow": xp.amax(i64(counts != 0) * ar(1, K + 1), 1), "nseq": i64(nseq), "nnz": i64(nnz), "nbytes": None if nbytes is None else i64(nbytes),
-         "nsub": None if nsub is None else i64(nsub)}
+         "nsub": None if nsub is None else i64(nsub), "nhid": None if nhid is None else i64(nhid)}
     out = {}
     for c in cols:
         if c.cut in ("nseq", "nnz"):
@@ -194,13 +200,13 @@ def frame_slices(cols, buffers, counts, nnz, nseq, nbytes=None, nsub=None):
 
 class BatchPayload:
     """What the container of every frame of a batch is assembled from: views into the batch's host buffers -- a streaming slot's pinned
-    ones or the arrays BatchCompressor.collect read back -- cut by frame_slices.  cols: columns(...); buffers, counts, nnz, nseq, nbytes, nsub:
+    ones or the arrays BatchCompressor.collect read back -- cut by frame_slices.  cols: columns(...); buffers, counts, nnz, nseq, nbytes, nsub, nhid:
     frame_slices' (numpy), the buffers read as the columns' dtypes; n: the frames that count (the first n; default all).
     frame(b) -> the dict compress_point_cloud builds (utils/compress_utils.py:138-179), before the entropy coder: views, no copies."""
 
-    def __init__(self, cols, buffers, counts, nnz, nseq, nbytes=None, n=None, nsub=None):
+    def __init__(self, cols, buffers, counts, nnz, nseq, nbytes=None, n=None, nsub=None, nhid=None):
         self.n = len(nnz) if n is None else n
-        at = frame_slices(cols, buffers, counts, nnz, nseq, nbytes, nsub)
+        at = frame_slices(cols, buffers, counts, nnz, nseq, nbytes, nsub, nhid)
         # per column: the flattened buffer, the frames' first and last + 1 elements, the shape of a sub-row (the model's rows keep their [., 4])
         self.parts = [(c.name, buffers[c.name].reshape(-1).view(c.dtype), lo.tolist(), (lo + n_el).tolist(), (-1,) + tuple(buffers[c.name].shape[2:]))
                       for c in cols for lo, n_el in (at[c.name],)]
@@ -309,6 +315,73 @@ def encode_subpixel(transformer, rows, range_image, bits, want_codes=False):
     return payload[0, : int(nbytes[0])].cpu().numpy(), (codes[0].cpu().numpy() if want_codes else None)
 
 
+BEAM_TABLE_HIDDEN = ("hidden_points with a per-beam elevation table (channel_distribute_csv): that projection's rule is 'the last point wins' and "
+                     "its rows are a search over the table, another owner rule and another row offset than the hidden_points kernels'; use a lidar "
+                     "configuration with evenly spaced beams")
+
+
+def hidden_payload(bits, step, counts, k, az=None, el=None):
+    """The 'hidden_points' array of a frame: b"RPH1" | bits | 0 0 0 | step f32 | m u32 | counts uint8 [n] of the non-empty pixels in raster
+    order | the range codes as little-endian uint16 [m] | for bits > 0 the az codes uint8 [m] and the el codes uint8 [m]."""
+    bits = ops.check_hidden_bits(bits)
+    counts, k = np.ascontiguousarray(counts, dtype=np.uint8).reshape(-1), np.ascontiguousarray(k, dtype="<u2").reshape(-1)
+    if int(counts.sum(dtype=np.int64)) != k.shape[0]:
+        raise ValueError("hidden_points payload: the counts sum to %d, %d range codes" % (int(counts.sum(dtype=np.int64)), k.shape[0]))
+    body = counts.tobytes() + k.tobytes()
+    if bits:
+        az, el = np.ascontiguousarray(az, dtype=np.uint8).reshape(-1), np.ascontiguousarray(el, dtype=np.uint8).reshape(-1)
+        if az.shape != k.shape or el.shape != k.shape:
+            raise ValueError("hidden_points payload: %d range codes, %d az codes, %d el codes" % (k.shape[0], az.shape[0], el.shape[0]))
+        body += az.tobytes() + el.tobytes()
+    head = HIDDEN_MAGIC + bytes([bits, 0, 0, 0]) + struct.pack("<f", ops.check_hidden_step(step)) + struct.pack("<I", k.shape[0])
+    return np.frombuffer(head + body, dtype=np.uint8)
+
+
+def parse_hidden_payload(data, n):
+    """-> (bits, step, counts uint8 [n], k uint16 [m], az uint8 [m], el uint8 [m]) of a decoded 'hidden_points' array; ValueError unless it
+    holds a header, starts with the magic, names 0 .. 4 bits, has three zero bytes behind them, a finite step > 0, exactly 16 + n + 2m
+    bytes (16 + n + 4m with lateral codes; n: the pixels whose label is not 1), counts that sum to m and no lateral code >= 1 << bits."""
+    data = bytes(data)
+    if len(data) < 16 or data[:4] != HIDDEN_MAGIC:
+        raise ValueError("hidden_points payload: no %r header (%d bytes)" % (HIDDEN_MAGIC, len(data)))
+    bits = data[4]
+    if bits > 4:
+        raise ValueError("hidden_points payload: %d bits per axis (0 .. 4)" % bits)
+    if data[5:8] != b"\0\0\0":
+        raise ValueError("hidden_points payload: reserved bytes %r are not 0" % data[5:8])
+    step = np.frombuffer(data, dtype="<f4", count=1, offset=8)[0]
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError("hidden_points payload: step %r is not finite and > 0" % float(step))
+    (m,) = struct.unpack_from("<I", data, 12)
+    w = 4 if bits else 2
+    if len(data) != 16 + n + w * m:
+        raise ValueError("hidden_points payload: %d bytes for %d non-empty pixels and %d points (16 + %d + %d * %d expected)" % (len(data), n, m, n, w, m))
+    counts = np.frombuffer(data, dtype=np.uint8, count=n, offset=16)
+    if int(counts.sum(dtype=np.int64)) != m:
+        raise ValueError("hidden_points payload: the counts sum to %d, the header names %d points" % (int(counts.sum(dtype=np.int64)), m))
+    k = np.frombuffer(data, dtype="<u2", count=m, offset=16 + n)
+    lat = np.frombuffer(data, dtype=np.uint8, count=2 * m if bits else 0, offset=16 + n + 2 * m)
+    if lat.size and int(lat.max()) >= 1 << bits:
+        raise ValueError("hidden_points payload: code %d at %d bits" % (int(lat.max()), bits))
+    return bits, np.float32(step), counts, k, (lat[:m] if bits else np.zeros(m, np.uint8)), (lat[m:] if bits else np.zeros(m, np.uint8))
+
+
+def encode_hidden(transformer, rows, range_image, step, bits=0):
+    """One frame's 'hidden_points' array on the per-frame path: rows [N,>=3] (host), range_image [H,W] the image of these rows (host array
+    or device tensor), step the fp32 quantiser step, bits 0 .. 4 -> (uint8 [16 + n + 2m] or [16 + n + 4m], uncarried int), by ops.hidden_encode."""
+    if getattr(transformer, "even_dist", True) is False:
+        raise NotImplementedError(BEAM_TABLE_HIDDEN)
+    dev, H, W = transformer.device, transformer.H, transformer.W
+    rows_d = torch.from_numpy(rows16(rows)).to(dev)
+    ri = range_image if torch.is_tensor(range_image) else torch.from_numpy(np.ascontiguousarray(range_image, dtype=np.float32)).to(dev)
+    offs = torch.tensor([0, rows_d.shape[0]], dtype=torch.int64, device=dev)
+    payload, nbytes, orphans, uncarried = ops.hidden_encode(rows_d, offs, transformer.geom, ri.reshape(1, H, W).contiguous(), step, bits,
+                                                           max_rows=rows_d.shape[0])
+    if int(orphans[0]):
+        raise RuntimeError("hidden_points: %d non-empty pixels have no owner -- the range image is not the image of these rows" % int(orphans[0]))
+    return payload[0, : int(nbytes[0])].cpu().numpy(), int(uncarried[0])
+
+
 def rows16(points):
     """Host points [N,>=3] as the 16-byte rows f32 [N,4] the owner pass reads: the first four columns, or xyz and a zero fourth column."""
     points = np.asarray(points)
@@ -322,8 +395,8 @@ def rows16(points):
 
 
 def pack_bitstream(compressed_data, uniform=True):
-    """The .rpcc container (utils/compress_utils.py:167-179): [int32 length | bytes] per array; 'intensity', then 'subpixel', last where the
-    dictionary holds them."""
+    """The .rpcc container (utils/compress_utils.py:167-179): [int32 length | bytes] per array; 'intensity', then 'subpixel', then
+    'hidden_points', last where the dictionary holds them."""
     keys = _keys(uniform, compressed_data)
     return b"".join(struct.pack("i", len(compressed_data[k])) + bytes(compressed_data[k]) for k in keys)
 
@@ -363,10 +436,10 @@ def pack_frames(basic_compressor, frames, uniform=True):
     return [out[int(offs[i]): int(offs[i]) + int(out_len[i])].tobytes() for i in range(n)]
 
 
-def unpack_bitstream(blob, uniform=True, intensity=False, subpixel=False):
+def unpack_bitstream(blob, uniform=True, intensity=False, subpixel=False, hidden_points=False):
     """intensity=True (a caller that asks for it): the dictionary also holds 'intensity', the coded trailer -- ValueError unless what
     follows the known payloads is exactly one length-prefixed payload that ends the blob.  Without it: trailing bytes are ignored, as ever.
-    subpixel=True: 'subpixel' alike.  The reader is told which trailers to expect: what follows the geometry must be exactly the trailers
+    subpixel=True: 'subpixel' alike; hidden_points=True: 'hidden_points' alike.  The reader is told which trailers to expect: what follows the geometry must be exactly the trailers
     asked for, in file order, ending the blob -- ValueError naming the flag that does not fit otherwise."""
     keys = _keys(uniform)
     spans = list(payload_spans(blob, len(keys)))
@@ -379,17 +452,23 @@ def unpack_bitstream(blob, uniform=True, intensity=False, subpixel=False):
                              % (k, len(blob), "non-uniform" if uniform else "uniform"))
         raise ValueError("bitstream: payload '%s' claims %d bytes, %d are left" % (k, struct.unpack_from("i", blob, off)[0], len(blob) - off - 4))
     out = {k: blob[s: s + n] for k, (s, n) in zip(keys, spans)}
-    want = tuple(t for t, on in zip(TRAILERS, (intensity, subpixel)) if on)
+    want = tuple(t for t, on in zip(TRAILERS, (intensity, subpixel, hidden_points)) if on)
     if not want:
         return out
-    tail = list(payload_spans(blob, len(keys) + len(TRAILERS)))[len(keys):]      # the trailers the blob holds, two at most
+    tail = list(payload_spans(blob, len(keys) + len(TRAILERS)))[len(keys):]      # the trailers the blob holds, three at most
     if len(tail) >= len(want) and sum(tail[len(want) - 1]) == len(blob):
         out.update({t: blob[s: s + n] for t, (s, n) in zip(want, tail)})
         return out
-    if len(tail) > len(want) and sum(tail[-1]) == len(blob):                      # one trailer asked for, two end the blob
-        other = TRAILERS[1 - TRAILERS.index(want[0])]
-        raise ValueError("bitstream: two trailers follow its %d payloads and only %s was asked for (compressed with --%s too? the reader needs "
-                         "%s=True then)" % (len(out), want[0], other, other))
+    if len(tail) > len(want) and sum(tail[-1]) == len(blob):                      # more trailers end the blob than were asked for
+        if len(tail) == 2 and len(want) == 1 and want[0] in TRAILERS[:2]:         # one of the two older flags, two trailers: the text it always had,
+            other = TRAILERS[1 - TRAILERS.index(want[0])]                         # and behind it the third flag, which explains such a blob as well
+            raise ValueError("bitstream: two trailers follow its %d payloads and only %s was asked for (compressed with --%s too? the reader needs "
+                             "%s=True then); or with --hidden_points: hidden_points=True" % (len(out), want[0], other, other))
+        missing = [t for t in TRAILERS if t not in want]                          # every one of them, or one of them: the container names no payload
+        glue =" and " if len(tail) - len(want) == len(missing) else " or "
+        raise ValueError("bitstream: %s trailers follow its %d payloads and only %s asked for (compressed with --%s too? the reader needs "
+                         "%s then)" % (("one", "two", "three")[len(tail) - 1], len(out), " and ".join(want) + (" was" if len(want) == 1 else " were"),
+                                       (glue + "--").join(missing), glue.join(m + "=True" for m in missing)))
     if len(tail) >= len(want):
         raise ValueError("bitstream: %d bytes follow the %s trailer; the trailers asked for must end the container"
                          % (len(blob) - sum(tail[len(want) - 1]), want[-1]))
@@ -403,9 +482,9 @@ def save_compressed_bitstream(file, compressed_data, uniform=True):
         f.write(pack_bitstream(compressed_data, uniform))
 
 
-def read_compressed_bitstream(file, uniform=True, intensity=False, subpixel=False):
+def read_compressed_bitstream(file, uniform=True, intensity=False, subpixel=False, hidden_points=False):
     with open(file, "rb") as f:
-        return unpack_bitstream(f.read(), uniform, intensity=intensity, subpixel=subpixel)
+        return unpack_bitstream(f.read(), uniform, intensity=intensity, subpixel=subpixel, hidden_points=hidden_points)
 
 
 def decompress_point_cloud(compressed_data, basic_compressor, model_num, H, W):

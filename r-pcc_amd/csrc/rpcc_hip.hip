@@ -1143,6 +1143,69 @@ extern "C" int rpcc_subpixel_decode(const uint8_t *payload, int64_t payload_stri
     return RPCC_OK;
 }
 
+// ---- hidden_points: the points that share a pixel with its owner, a range code and `bits` bits per axis each ---------------------
+#include "hidden_kernels.h"
+
+// 16 + P + 4 total, the longest payload, must fit the int32 of nbytes
+static inline bool hidden_sizes_ok(int B, int64_t P, int64_t total) {
+    return B > 0 && B <= RPCC_MAX_BATCH && P > 0 && P < ((int64_t)1 << 30) - 4 && total >= 0 && (int64_t)HID_HEADER + P + 4 * total < ((int64_t)1 << 31);
+}
+
+extern "C" size_t rpcc_hidden_scratch_bytes(int B, int P, int64_t total) { return hidden_sizes_ok(B, P, total) ? hidden_layout(nullptr, B, P, total).bytes : 0; }
+
+extern "C" int rpcc_hidden_encode(const float *rows, const int64_t *offsets, int64_t total, int B, rpcc_geom g, const float *ri, float step, int bits,
+                                  uint8_t *payload, int64_t payload_stride, int32_t *nbytes, int32_t *orphans, int32_t *uncarried, void *scratch,
+                                  size_t scratch_bytes, void *stream) {
+    ARG_TRY(subpixel_shape_ok(B, g.H, g.W) && hidden_sizes_ok(B, (int64_t)g.H * g.W, total));
+    ARG_TRY(g.horizontal_fov > 0.0f);   // (a column index is never negative)
+    ARG_TRY(offsets != nullptr && ri != nullptr && payload != nullptr && nbytes != nullptr && orphans != nullptr && uncarried != nullptr && scratch != nullptr);
+    ARG_TRY(total == 0 || rows != nullptr);
+    ARG_TRY((reinterpret_cast<uintptr_t>(rows) & 15u) == 0);   // rows are read with 16-byte loads
+    ARG_TRY(step > 0.0f && step <= 3.402823466e+38f);          // (false for NaN)
+    ARG_TRY(bits >= 0 && bits <= 4);
+    const int P = g.H * g.W;
+    ARG_TRY(payload_stride >= (int64_t)HID_HEADER + P);        // header and count plane; a frame whose codes do not fit gets nbytes -1
+    const HiddenLayout l = hidden_layout(scratch, B, P, total);
+    ARG_TRY(scratch_bytes >= l.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = intensity_owner_pass(rows, offsets, total, B, g, ri, l.own, st)) return rc;
+    HIP_TRY(hipMemsetAsync(l.zeroed, 0, l.zeroed_bytes, st));
+    const float4 *r4 = reinterpret_cast<const float4 *>(rows);
+    const unsigned row_wgs = (unsigned)std::min<int64_t>((total + HID_THREADS - 1) / HID_THREADS, 256 * 16);
+    if (total > 0) {
+        hidden_count_kernel<<<row_wgs, HID_THREADS, 0, st>>>(r4, offsets, total, B, g, ri, l.own.owner, step, bits, l.cnt, l.lost, l.keys, l.pix);
+        LAUNCH_CHECK();
+    }
+    hidden_scan_kernel<<<B, INT_FRAME_THREADS, 0, st>>>(offsets, total, P, ri, l.own.owner, l.cnt, l.lost, step, bits, l.start, l.fstart, l.info, payload,
+                                                        payload_stride, nbytes, orphans, uncarried);
+    LAUNCH_CHECK();
+    if (total > 0) {
+        hidden_scatter_kernel<<<row_wgs, HID_THREADS, 0, st>>>(offsets, total, B, P, l.keys, l.pix, l.start, l.cursor, l.skey, l.spix);
+        LAUNCH_CHECK();
+        hidden_rank_kernel<<<row_wgs, HID_THREADS, 0, st>>>(offsets, total, B, P, l.cnt, l.start, l.fstart, l.info, l.skey, l.spix, bits, payload, payload_stride);
+        LAUNCH_CHECK();
+    }
+    return RPCC_OK;
+}
+
+extern "C" int rpcc_hidden_decode(const uint8_t *payload, int64_t payload_stride, const int32_t *nbytes, const void *labels, int label_bytes,
+                                  const float *tm, const double *tables, int H, int W, int B, float *points, int64_t capacity, int32_t *count,
+                                  int32_t *status, void *stream) {
+    ARG_TRY(subpixel_shape_ok(B, H, W));
+    ARG_TRY(payload != nullptr && nbytes != nullptr && labels != nullptr && tm != nullptr && count != nullptr && status != nullptr);
+    ARG_TRY(capacity >= 0 && capacity < ((int64_t)1 << 31) && (capacity == 0 || points != nullptr));
+    ARG_TRY(label_bytes == 1 || label_bytes == 2);
+    ARG_TRY((reinterpret_cast<uintptr_t>(tables) & 7u) == 0);   // (NULL: frames with lateral codes are refused)
+    ARG_TRY(payload_stride >= HID_HEADER);
+    hipStream_t st = (hipStream_t)stream;
+    if (label_bytes == 1)
+        hidden_decode_kernel<uint8_t><<<B, INT_FRAME_THREADS, 0, st>>>(payload, payload_stride, nbytes, static_cast<const uint8_t *>(labels), tm, tables, H, W, capacity, points, count, status);
+    else
+        hidden_decode_kernel<uint16_t><<<B, INT_FRAME_THREADS, 0, st>>>(payload, payload_stride, nbytes, static_cast<const uint16_t *>(labels), tm, tables, H, W, capacity, points, count, status);
+    LAUNCH_CHECK();
+    return RPCC_OK;
+}
+
 #include "beam_index.h"
 #include "beams_kernels.h"
 

@@ -108,6 +108,19 @@ __global__ __launch_bounds__(INT_FRAME_THREADS) void subpixel_pack_kernel(const 
     }
 }
 
+// the ray of pixel (h, w) turned by the offsets the codes (a, e) stand for, times the range r: the angle sums in fp64, every product and
+// sum rounded on its own (step: the table row of this bits); shared by the subpixel decoder and the hidden-points decoder
+__device__ __forceinline__ void subpixel_turn_ray(const double *__restrict__ ca, const double *__restrict__ sa, const double *__restrict__ cz,
+                                                  const double *__restrict__ sz, const double *__restrict__ step, int h, int w, uint32_t a, uint32_t e,
+                                                  double r, float &x, float &y, float &z) {
+    const double cde = step[4 * e], sde = step[4 * e + 1], cda = step[4 * a + 2], sda = step[4 * a + 3];
+    const double cosalt = ca[h] * cde - sa[h] * sde, sinalt = sa[h] * cde + ca[h] * sde;
+    const double cosaz = cz[w] * cda - sz[w] * sda, sinaz = sz[w] * cda + cz[w] * sda;
+    x = (float)(r * (cosalt * cosaz));
+    y = (float)(r * (cosalt * sinaz));
+    z = (float)(r * sinalt);
+}
+
 // tables: f64 [2 H + 2 W + 4 * SUB_TABLE_CODES * 4] = ca [H], sa [H], cz [W], sz [W], then per bits 1 .. 4 and code c: cos / sin of the
 // elevation step, cos / sin of the azimuth step (ops.subpixel_tables)
 template <class L>
@@ -164,13 +177,7 @@ __global__ __launch_bounds__(INT_FRAME_THREADS) void subpixel_decode_kernel(cons
                 const uint32_t a = in[8 + rank], e = in[8 + n + rank];   // rank < n; both < Lc <= SUB_TABLE_CODES
                 rank++;
                 const int h = (p0 + k) / W, w = (p0 + k) - h * W;
-                const double cde = step[4 * e], sde = step[4 * e + 1], cda = step[4 * a + 2], sda = step[4 * a + 3];
-                const double cosalt = ca[h] * cde - sa[h] * sde, sinalt = sa[h] * cde + ca[h] * sde;
-                const double cosaz = cz[w] * cda - sz[w] * sda, sinaz = sz[w] * cda + cz[w] * sda;
-                const double r = (double)ri_rec[px0 + p0 + k];
-                x = (float)(r * (cosalt * cosaz));
-                y = (float)(r * (cosalt * sinaz));
-                z = (float)(r * sinalt);
+                subpixel_turn_ray(ca, sa, cz, sz, step, h, w, a, e, (double)ri_rec[px0 + p0 + k], x, y, z);
             }
             float *o = points + 3 * (px0 + p0 + k);
             o[0] = x; o[1] = y; o[2] = z;

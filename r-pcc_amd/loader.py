@@ -63,6 +63,11 @@ class _Slot:
         # bc.subpixel_bits: the subpixel payload rows (8 + 2n bytes of 8 + 2P each are meaningful), their lengths and orphan counts
         self.sub_pin = torch.empty((B, 8 + 2 * P), dtype=torch.uint8).pin_memory() if bc.subpixel_bits is not None else None
         self.sub_n_pin = torch.zeros((2, B), dtype=torch.int32).pin_memory() if bc.subpixel_bits is not None else None
+        # bc.hidden_points: the hidden_points payload rows (16 + P + 4 rows of the batch's largest frame; made when the first batch is
+        # enqueued and whenever the device rows grow), their lengths, orphan and uncarried counts
+        self.hid_pin = None
+        self.hid_n_pin = torch.zeros((3, B), dtype=torch.int32).pin_memory() if bc.hidden_points else None
+        self.hid_rows = 0      # rows of the largest frame staged
         self.h2d_done = torch.cuda.Event()
         self.done = torch.cuda.Event()
         self.n = 0
@@ -110,6 +115,9 @@ class StreamingCompressor:
                              'ingest="xyz" drops it')
         if bc.subpixel_bits is not None and ingest == "xyz":
             raise ValueError('StreamingCompressor: a BatchCompressor with subpixel_bits needs ingest="rows" (the owner pass reads 16-byte rows); '
+                             'ingest="xyz" stages packed points')
+        if bc.hidden_points and ingest == "xyz":
+            raise ValueError('StreamingCompressor: a BatchCompressor with hidden_points needs ingest="rows" (the owner pass reads 16-byte rows); '
                              'ingest="xyz" stages packed points')
         self.ingest = ingest
         self.bc, self.B, self.depth = bc, int(batch), int(depth)
@@ -192,6 +200,7 @@ class StreamingCompressor:
         fid[:n] = np.asarray(frame_ids if frame_ids is not None else np.arange(n), np.int64)[:n]
         slot.fid_pin.numpy()[:] = fid
         slot.n = n
+        slot.hid_rows = int(sizes.max()) if n else 0
         return int(offs[n])
 
     # ---- device part: H2D on the copy stream, everything else on the compute stream ------------------------------------
@@ -211,7 +220,7 @@ class StreamingCompressor:
             if slot.nclt:     # the records -> the stored rows run_batch reads (16-byte stride), in front of it on this stream
                 records.unpack(slot.rec_dev[:npts], out=slot.xyz_dev[:npts])
             # (FPS: one ops.compress_batch; DBSCAN: projection, ground fit, dbscan_segment, ops.compress_batch_labels)
-            bc.run_batch(slot.xyz_dev[:npts], slot.offs_dev, slot.ground, slot.buf, frame_ids=slot.fid_dev)
+            bc.run_batch(slot.xyz_dev[:npts], slot.offs_dev, slot.ground, slot.buf, frame_ids=slot.fid_dev, max_rows=slot.hid_rows)
             bits, seq, nseq = ops.contour_encode(slot.buf.seg, bc.M, ws=slot.codec_ws)
             ops.pack_payload(slot.buf.q16, slot.buf.nnz, packed=slot.qp, capacity=slot.cap, total=slot.tot[0:1])
             ops.pack_payload(seq.view(torch.int16), nseq, packed=slot.sp, capacity=slot.sp.numel(), total=slot.tot[1:2])
@@ -238,6 +247,13 @@ class StreamingCompressor:
                 slot.sub_pin.copy_(pay, non_blocking=True)
                 slot.sub_n_pin[0].copy_(nb, non_blocking=True)
                 slot.sub_n_pin[1].copy_(orphans, non_blocking=True)
+            if slot.hid_n_pin is not None:    # (run_batch has run ops.hidden_encode on the same rows)
+                pay, nb, orphans, uncarried = slot.buf.hidden
+                if slot.hid_pin is None or slot.hid_pin.shape != pay.shape:     # the slot is idle until `done`: nobody reads the old mirror
+                    slot.hid_pin = torch.empty(tuple(pay.shape), dtype=torch.uint8).pin_memory()
+                slot.hid_pin.copy_(pay, non_blocking=True)
+                for k, t in enumerate((nb, orphans, uncarried)):
+                    slot.hid_n_pin[k].copy_(t, non_blocking=True)
             slot.keep = (bits, seq, nseq)
             slot.done.record(self.compute_stream)
 
@@ -251,6 +267,8 @@ class StreamingCompressor:
             self.bc.check_orphans(slot.int_n_pin.numpy()[1, :slot.n])
         if slot.sub_pin is not None:
             self.bc.check_orphans(slot.sub_n_pin.numpy()[1, :slot.n], "subpixel")
+        if slot.hid_n_pin is not None:
+            self.bc.check_hidden(*(slot.hid_n_pin.numpy()[k, :slot.n] for k in range(3)), slot.hid_pin.numpy()[:slot.n, 12:16])
         stot = int(slot.tot_pin[1])
         if stot > self.seq_eager:
             # an unusually long index sequence: the rest is fetched now, on a stream of its own (the compute stream already
@@ -261,10 +279,12 @@ class StreamingCompressor:
         # the columns' pinned buffers (compress_utils.SCHEMA), cut per frame by the rule BatchCompressor.collect uses (frame_slices)
         num = lambda t: None if t is None else t.numpy()
         bufs = dict(salience_level=num(slot.sal_pin), contour_map=num(slot.bits_pin), idx_sequence=num(slot.sp_pin), plane_param=num(slot.model_pin),
-                    residual_quantized=num(slot.qp_pin), intensity=num(slot.int_pin), subpixel=num(slot.sub_pin))
+                    residual_quantized=num(slot.qp_pin), intensity=num(slot.int_pin), subpixel=num(slot.sub_pin),
+                    hidden_points=num(slot.hid_pin) if slot.hid_n_pin is not None else None)
         return BatchPayload(self.bc.columns, bufs, num(slot.counts_pin), num(slot.nnz_pin), num(slot.nseq_pin),
                             None if slot.int_pin is None else num(slot.int_n_pin)[0], n=slot.n,
-                            nsub=None if slot.sub_pin is None else num(slot.sub_n_pin)[0])
+                            nsub=None if slot.sub_pin is None else num(slot.sub_n_pin)[0],
+                            nhid=None if slot.hid_n_pin is None else num(slot.hid_n_pin)[0])
 
     def _encode_chunk(self, payload, lo, hi):
         bc = self.bc
@@ -349,7 +369,10 @@ class StreamingDecompressor:
     in one copy, are decoded into chunk-sized images that never leave the device, and rows.pack turns those into the files' bytes --
     status, offsets, non-zero counts and rows[:total] are all that comes back.  One process, no children."""
 
-    def __init__(self, bd, depth=3, workers=None, pool=None):
+    def __init__(self, bd, depth=3, workers=None, pool=None, hidden_points=False):
+        if hidden_points:
+            raise NotImplementedError("StreamingDecompressor: hidden_points -- the packed rows hold one point per pixel; decode containers with "
+                                      "the hidden_points trailer per frame (tools.decompress.decode_frame(..., hidden_points=True))")
         self.bd, self.depth, self.device = bd, max(1, int(depth)), bd.device
         self.pool = pool or ThreadPoolExecutor(workers or min(32, available_cpus()))
         self.slots = [_DecodeSlot(bd, self.device) for _ in range(self.depth)]

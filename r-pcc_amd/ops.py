@@ -263,6 +263,91 @@ def subpixel_decode(payload, nbytes, seg, ri_rec, tables, out=None, status=None)
     return out, status
 
 
+HIDDEN_HEADER = 16            # HID_HEADER (csrc/hidden_kernels.h): magic, bits, reserved, step, m
+
+
+def check_hidden_bits(bits):
+    """The lateral code width of the hidden_points channel: an integer 0 .. 4 (0: range codes only)."""
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 0 <= int(bits) <= 4:
+        raise ValueError("hidden_points bits %r: an integer 0 .. 4 is needed" % (bits,))
+    return int(bits)
+
+
+def check_hidden_step(step):
+    """The quantiser step of the hidden_points channel as the kernels take it: an fp32 value, finite and > 0."""
+    with np.errstate(over="ignore"):
+        s = float(np.float32(step))
+    if not (math.isfinite(s) and s > 0):
+        raise ValueError("hidden_points step %r: a finite float32 value > 0 is needed" % (step,))
+    return s
+
+
+def hidden_row_bytes(P, rows):
+    """The longest hidden_points payload of a frame of `rows` input rows: 16 + P + 4 rows."""
+    return HIDDEN_HEADER + int(P) + 4 * int(rows)
+
+
+def hidden_encode(rows, offsets, geom, ri, step, bits=0, max_rows=None, payload=None, nbytes=None, orphans=None, uncarried=None, scratch=None):
+    """The hidden_points payloads of a batch (rpcc_hidden_encode; specification: tests/hidden_ref.py).  rows f32 [total,4] (x, y, z and a
+    fourth column that is not read), offsets i64 [B+1], ri f32 [B,H,W] the range image ops.project / the batch call made of THESE rows,
+    step the fp32 quantiser step, bits 0 .. 4 the lateral code width -> (payload u8 [B, 16 + P + 4 max_rows]: b"RPH1" | bits | 0 0 0 |
+    step f32 | m u32 | a count byte per non-empty pixel in raster order | the range codes u16 [m] | for bits > 0 the az codes [m] and the
+    el codes [m]; nbytes i32 [B] = 16 + n + 2m or 16 + n + 4m; orphans i32 [B]; uncarried i32 [B]: hidden points in an empty pixel, past
+    range code 65535 or past the 255 of their pixel).  max_rows: the rows of the batch's largest frame (None: read from offsets, one
+    synchronisation).  The bytes of a payload row past nbytes are left as they were.  payload .. scratch: the caller's buffers."""
+    if rows.dim() != 2 or rows.shape[1] != 4:
+        raise ValueError("hidden_encode: rows [total,%s]; the stored 16-byte rows [total,4] are needed (packed xyz: add a zero column)"
+                         % (rows.shape[1] if rows.dim() == 2 else "?"))
+    assert rows.dtype == torch.float32 and ri.dtype == torch.float32
+    step, bits = check_hidden_step(step), check_hidden_bits(bits)
+    B, P, dev = offsets.numel() - 1, geom.H * geom.W, _dev(offsets)
+    rows = rows.contiguous()
+    if payload is None:
+        if max_rows is None:
+            max_rows = int((offsets[1:] - offsets[:-1]).max()) if B > 0 else 0
+        payload = torch.empty((B, hidden_row_bytes(P, max(int(max_rows), 0))), dtype=torch.uint8, device=dev)
+    if nbytes is None:
+        nbytes = torch.empty((B,), dtype=torch.int32, device=dev)
+    if orphans is None:
+        orphans = torch.empty((B,), dtype=torch.int32, device=dev)
+    if uncarried is None:
+        uncarried = torch.empty((B,), dtype=torch.int32, device=dev)
+    if scratch is None:
+        scratch = torch.empty(_lib.lib().rpcc_hidden_scratch_bytes(B, P, rows.shape[0]), dtype=torch.uint8, device=dev)
+    check(_lib.lib().rpcc_hidden_encode(ptr(rows) if rows.numel() else None, ptr(offsets), rows.shape[0], B, geom, ptr(ri), step, bits, ptr(payload),
+                                        payload.stride(0), ptr(nbytes), ptr(orphans), ptr(uncarried), ptr(scratch), scratch.numel(), stream()))
+    return payload, nbytes, orphans, uncarried
+
+
+def hidden_decode(payload, nbytes, seg, tm, tables=None, capacity=None, out=None, count=None, status=None):
+    """The way back (rpcc_hidden_decode): payload u8 [B, .] rows, nbytes i32 [B], seg [B,H,W] uint8 or uint16 label maps (label 1: an empty
+    pixel), tm f32 [H,W,3] the transform map (PCTransformer.tm_dev), tables f64 the device copy of subpixel_tables or None (a frame with
+    lateral codes is then refused) -> (points f32 [B, capacity, 3]: frame b's count[b] points in payload order, the rest left as it is;
+    count i32 [B]; status i32 [B]: _lib.STREAM_OK, or _lib.STREAM_E_HIDDEN for a refused row: count 0, nothing written).  capacity: the
+    most points a frame may hold (None: what the longest row could, (row bytes - 16) / 2)."""
+    B, H, W = seg.shape
+    assert payload.dtype == torch.uint8 and payload.dim() == 2 and payload.shape[0] == B and payload.stride(1) == 1
+    assert seg.dtype in (torch.uint8, torch.uint16) and nbytes.dtype == torch.int32 and nbytes.numel() == B
+    assert tm.dtype == torch.float32 and tm.numel() == H * W * 3 and tm.is_contiguous()
+    if tables is not None:
+        assert tables.dtype == torch.float64 and tables.numel() == 2 * H + 2 * W + 4 * SUBPIXEL_TABLE_CODES * 4, "tables: PCTransformer.subpixel_tables() of this geometry"
+    if out is not None:
+        capacity = out.shape[1]
+    elif capacity is None:
+        capacity = max((payload.shape[1] - HIDDEN_HEADER) // 2, 0)
+    if out is None:
+        out = torch.empty((B, capacity, 3), dtype=torch.float32, device=_dev(seg))
+    assert out.dtype == torch.float32 and out.shape == (B, capacity, 3) and out.is_contiguous()
+    if count is None:
+        count = torch.empty((B,), dtype=torch.int32, device=_dev(seg))
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=_dev(seg))
+    row = payload.stride(0) if B > 1 else payload.shape[1]     # (the stride of a dimension of one frame says nothing)
+    check(_lib.lib().rpcc_hidden_decode(C.c_void_p(payload.data_ptr()), row, ptr(nbytes), ptr(seg), seg.element_size(), ptr(tm),
+                                        ptr(tables), H, W, B, ptr(out) if capacity else None, capacity, ptr(count), ptr(status), stream()))
+    return out, count, status
+
+
 def _frame_ids(frame_ids, B, device):
     """Stable per-frame identities (datalist indices) as a device i64 [B] tensor, or None."""
     if frame_ids is None:

@@ -9,7 +9,7 @@ import torch
 
 from . import entropy, ops
 from . import _lib
-from .compress_utils import (BACKENDS, BEAM_TABLE_INTENSITY, BEAM_TABLE_SUBPIXEL, BasicCompressor, BatchPayload, columns, device_decoder, frame_slices, intensity_trailer_span,
+from .compress_utils import (BACKENDS, BEAM_TABLE_HIDDEN, BEAM_TABLE_INTENSITY, BEAM_TABLE_SUBPIXEL, BasicCompressor, BatchPayload, columns, device_decoder, frame_slices, intensity_trailer_span,
                              pack_bitstream, pack_frames, payload_spans, unpack_bitstream)  # noqa: F401
 
 
@@ -19,7 +19,8 @@ class BatchCompressor:
     def __init__(self, transformer, cluster_num=100, accuracy=0.02, ground_threshold=0.1, uniform=True,
                  model_method="point", compressor_cfg=None, basic_compressor="bzip2", device=None, seed=0,
                  device_entropy=False, device_bzip2=False, segment_method="FPS", DBSCAN_eps=1.5, max_labels=None,
-                 radius_outlier_removal=None, rans_delta=False, intensity_scale=None, point_format=None, subpixel_bits=None):
+                 radius_outlier_removal=None, rans_delta=False, intensity_scale=None, point_format=None, subpixel_bits=None,
+                 hidden_points=False):
         """point_format (None: float points, and nothing changes): "nclt" -- compress / submit take every frame as uint8 [N,8] NCLT
         velodyne_sync records (records.py); 8 bytes per point go up, records.unpack (librpcc_records.so) makes the stored rows on the
         device and run_batch reads them like any [N,4] rows, so every other option works behind it; with intensity_scale the payload
@@ -30,6 +31,10 @@ class BatchCompressor:
         subpixel_bits (None: off, and no byte of any container changes; else 1 .. 4): after the batch call one ops.subpixel_encode runs on
         the same point tensor and the batch's range images, and every container gets the 'subpixel' trailer behind the intensity one, byte
         for byte the per-frame path's.  Frames may be [N,3]: they get a zero fourth column on the host, the rows go up with stride 16.
+        hidden_points (False: off, and no byte of any container changes): after the batch call one ops.hidden_encode runs on the same point
+        tensor and the batch's range images -- step = accuracy * 2, lateral codes of subpixel_bits where that is set, else none -- and every
+        container gets the 'hidden_points' trailer last, byte for byte the per-frame path's: the points that share a pixel with the one the
+        range image keeps.  Frames may be [N,3], as for subpixel_bits.  The payload buffer is sized from the batch's largest frame.
         rans_delta (basic_compressor 'rans' only): the residual stream goes through the delta filter, as BasicCompressor(rans_delta=True)
         codes it on the per-frame path.
         segment_method "DBSCAN" (cfgs/compressor.yaml: segment_method, DBSCAN_eps): the frames are segmented by dbscan.dbscan_segment and
@@ -65,6 +70,12 @@ class BatchCompressor:
         self.subpixel_bits = None if subpixel_bits is None else ops.check_subpixel_bits(subpixel_bits)
         if self.subpixel_bits is not None and getattr(transformer, "even_dist", True) is False:
             raise NotImplementedError("BatchCompressor: " + BEAM_TABLE_SUBPIXEL)
+        self.hidden_points = bool(hidden_points)
+        self.hidden_uncarried = None    # per frame of the last batch collected: hidden points the trailer does not carry
+        self.hidden_carried = None      # ... and those it carries
+        self.hidden_totals = [0, 0]     # carried, uncarried over every batch collected
+        if self.hidden_points and getattr(transformer, "even_dist", True) is False:
+            raise NotImplementedError("BatchCompressor: " + BEAM_TABLE_HIDDEN)
         # a transformer built from a per-beam elevation table (channel_distribute_csv): the projection goes through its index -- the fused
         # call's, the DBSCAN path's and the streaming loader's alike (all run_batch / _group_args); nothing behind the projection changes
         if getattr(transformer, "even_dist", True) is False and not self.dbscan and self.M > _lib.MAX_CLUSTERS_MID:
@@ -136,10 +147,29 @@ class BatchCompressor:
         ops.subpixel_encode(rows, offsets, self.T.geom, buf.ri, self.subpixel_bits, payload=pay, nbytes=nb, orphans=orphans,
                             scratch=buf.subpixel_scratch)
 
-    def run_trailers(self, rows, offsets, buf):
-        """The optional channels behind the batch call, in container order."""
+    def run_hidden(self, rows, offsets, buf, max_rows=None):
+        """hidden_points: the batch's hidden_points payloads into buf.hidden = (payload u8 [B, 16 + P + 4 max_rows], nbytes i32 [B], orphans
+        i32 [B], uncarried i32 [B]), on the current stream.  rows: the 16-byte rows the range images in buf.ri were made of (the NaN-masked
+        ones with the radius filter).  max_rows: the rows of the batch's largest frame (None: no frame has more rows than the batch)."""
+        if not self.hidden_points:
+            return
+        B, P, total = buf.B, buf.P, int(rows.shape[0])
+        width = ops.hidden_row_bytes(P, total if max_rows is None else max_rows)
+        if getattr(buf, "hidden", None) is None or buf.hidden[0].shape[1] < width:
+            buf.hidden = (torch.empty((B, width), dtype=torch.uint8, device=self.device),) + tuple(
+                torch.empty((B,), dtype=torch.int32, device=self.device) for _ in range(3))
+        need = _lib.lib().rpcc_hidden_scratch_bytes(B, P, total)
+        if getattr(buf, "hidden_scratch", None) is None or buf.hidden_scratch.numel() < need:
+            buf.hidden_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        pay, nb, orphans, uncarried = buf.hidden
+        ops.hidden_encode(rows, offsets, self.T.geom, buf.ri, self.acc, self.subpixel_bits or 0, payload=pay, nbytes=nb, orphans=orphans,
+                          uncarried=uncarried, scratch=buf.hidden_scratch)
+
+    def run_trailers(self, rows, offsets, buf, max_rows=None):
+        """The optional channels behind the batch call, in container order.  max_rows: run_hidden's."""
         self.run_intensity(rows, offsets, buf)
         self.run_subpixel(rows, offsets, buf)
+        self.run_hidden(rows, offsets, buf, max_rows)
 
     @staticmethod
     def check_orphans(orphans, channel="intensity"):
@@ -147,8 +177,21 @@ class BatchCompressor:
             raise _lib.RpccError("%s: frames %s have non-empty pixels no row owns (the range image is not the image of these rows)"
                                  % (channel, np.flatnonzero(orphans).tolist()))
 
-    def run_batch(self, xyz, offsets, ground, buf, frame_ids=None, fit_ground=True):
-        """The device work of one batch into buf, on the current stream, nothing waited for.  ground f64 [B,4]: fitted here (fit_ground: the
+    def check_hidden(self, nbytes, orphans, uncarried, heads):
+        """A batch's hidden_points lengths, orphan and uncarried counts and the payload rows' bytes 12 .. 15 (m) on the host: raises for
+        orphans and for a payload row that was too short (nbytes -1: the buffer was not sized from the batch's largest frame); keeps the
+        batch's uncarried and carried counts per frame in self.hidden_uncarried / self.hidden_carried and adds them to self.hidden_totals."""
+        self.check_orphans(orphans, "hidden_points")
+        if np.any(np.asarray(nbytes) < 0):
+            raise _lib.RpccError("hidden_points: the payload rows of frames %s are too short for their points" % np.flatnonzero(np.asarray(nbytes) < 0).tolist())
+        self.hidden_uncarried = np.asarray(uncarried).copy()
+        self.hidden_carried = np.ascontiguousarray(heads).view("<u4").reshape(-1).astype(np.int64)
+        self.hidden_totals[0] += int(self.hidden_carried.sum())
+        self.hidden_totals[1] += int(self.hidden_uncarried.sum())
+
+    def run_batch(self, xyz, offsets, ground, buf, frame_ids=None, fit_ground=True, max_rows=None):
+        """The device work of one batch into buf, on the current stream, nothing waited for.  max_rows (hidden_points): the rows of the
+        batch's largest frame, which size the payload rows; None: the batch's row count, which no frame exceeds.  ground f64 [B,4]: fitted here (fit_ground: the
         seeded RANSAC, frame b drawing with seed + frame_ids[b]) or the caller's.  FPS: one ops.compress_batch.  DBSCAN: ops.project (packed
         xyz or the stored 16-byte rows), ops.ground_ransac with the per-frame path's seed and identities, dbscan_segment(min_points = 10,
         as the reference hard-codes it) without the read-back of its max_label, then ops.compress_batch_labels, whose per-frame status
@@ -160,7 +203,7 @@ class BatchCompressor:
             ops.compress_batch(xyz, offsets, self.T.tm_dev, ground, buf, self.ground_threshold, self.acc,
                                ground_seed=self.seed if fit_ground else -1, frame_ids=frame_ids, model_method=self.model_method,
                                angle_threshold=angle, plane_seed=self.seed, nonuniform=nu, beams=self.beams)
-            self.run_trailers(xyz, offsets, buf)
+            self.run_trailers(xyz, offsets, buf, max_rows)
             return
         from .dbscan import dbscan_segment
         tm = self.T.tm_dev
@@ -171,7 +214,7 @@ class BatchCompressor:
         labels, top = dbscan_segment(buf.ri, tm, ground, self.eps, min_points=10, check=False)
         ops.compress_batch_labels(buf.ri, tm, ground, labels, top, buf, self.acc, model_method=self.model_method, angle_threshold=angle,
                                   plane_seed=self.seed, frame_ids=frame_ids, nonuniform=nu)
-        self.run_trailers(xyz, offsets, buf)
+        self.run_trailers(xyz, offsets, buf, max_rows)
 
     def check_status(self, status):
         """status: a batch's buf.status on the host (None for FPS).  Raises RpccError naming the refused frames (their places in the batch)
@@ -223,18 +266,18 @@ class BatchCompressor:
         bits, seq, nseq = ops.contour_encode(buf.seg, self.M, ws=buf.codec_ws)
         return buf, args["ground"], bits, seq, nseq, sal
 
-    def compress_device(self, xyz, offsets, ground=None, frame_ids=None):
+    def compress_device(self, xyz, offsets, ground=None, frame_ids=None, max_rows=None):
         """Device part.  xyz f32 [sum N,3], offsets i64 [B+1] on the device.  Returns the BatchBuffers plus
         contour bits / index sequences (and salience for the non-uniform framework), all still in HBM.
-        frame_ids: stable identities of the frames (utils.frame_identity) for the seeded plane fits."""
+        frame_ids: stable identities of the frames (utils.frame_identity) for the seeded plane fits.  max_rows: run_batch's."""
         if self.dbscan:
             buf = self._buffers(offsets.numel() - 1)
             g = torch.zeros((buf.B, 4), dtype=torch.float64, device=self.device) if ground is None else ground
-            self.run_batch(xyz, offsets, g, buf, frame_ids, fit_ground=ground is None)
+            self.run_batch(xyz, offsets, g, buf, frame_ids, fit_ground=ground is None, max_rows=max_rows)
             return self._encode(dict(buf=buf, ground=g))
         args = self._group_args(self._filtered(xyz, offsets), offsets, ground, frame_ids)
         ops.compress_batch(ground_threshold=self.ground_threshold, acc=self.acc, **args)
-        self.run_trailers(args["xyz"], offsets, args["buf"])
+        self.run_trailers(args["xyz"], offsets, args["buf"], max_rows)
         return self._encode(args)
 
     def _upload(self, frames, ground=None):
@@ -246,7 +289,7 @@ class BatchCompressor:
         cols = 3 if self.intensity_scale is None else 4     # (with intensity the rows go up as stored: the kernels read them with stride 16)
         if cols == 4 and any(f.ndim != 2 or f.shape[1] < 4 for f in frames):
             raise ValueError("BatchCompressor(intensity_scale=...): frames must be [N,>=4] rows (x, y, z, intensity)")
-        if cols == 3 and self.subpixel_bits is not None:     # the owner pass reads 16-byte rows: xyz and a zero fourth column where a frame has none
+        if cols == 3 and (self.subpixel_bits is not None or self.hidden_points):     # the owner pass reads 16-byte rows: xyz and a zero fourth column where a frame has none
             from .compress_utils import rows16
             frames, cols = [rows16(f) for f in frames], 4
         xyz = torch.from_numpy(np.ascontiguousarray(np.concatenate([f[:, :cols] for f in frames]), dtype=np.float32)).to(self.device)
@@ -276,8 +319,10 @@ class BatchCompressor:
         # the batch's buffer of every column (compress_utils.SCHEMA; frame_slices cuts the frames out of them) and the per-frame counts
         pay, nbytes, _ = buf.intensity if self.intensity_scale is not None else (None, None, None)
         spay, nsub, _ = buf.subpixel if self.subpixel_bits is not None else (None, None, None)
-        bufs = dict(salience_level=sal, contour_map=bits, idx_sequence=sp, plane_param=buf.model, residual_quantized=qp, intensity=pay, subpixel=spay)
-        ctx = dict(n=n, buf=buf, bufs=bufs, counts=(buf.counts, buf.nnz, nseq, nbytes, nsub), tot=dict(nnz=qtot, nseq=stot),
+        hpay, nhid, _, _ = buf.hidden if self.hidden_points else (None, None, None, None)
+        bufs = dict(salience_level=sal, contour_map=bits, idx_sequence=sp, plane_param=buf.model, residual_quantized=qp, intensity=pay, subpixel=spay,
+                    hidden_points=hpay)
+        ctx = dict(n=n, buf=buf, bufs=bufs, counts=(buf.counts, buf.nnz, nseq, nbytes, nsub, nhid), tot=dict(nnz=qtot, nseq=stot),
                    stream=torch.cuda.current_stream(self.device), keep=(xyz, g, seq))
         codec = self.bc.batch_codec()
         if codec:
@@ -286,9 +331,9 @@ class BatchCompressor:
 
     @property
     def columns(self):
-        return columns(self.uniform, self.intensity_scale is not None, self.subpixel_bits is not None)
+        return columns(self.uniform, self.intensity_scale is not None, self.subpixel_bits is not None, self.hidden_points)
 
-    def _device_containers(self, codec, bufs, counts, nnz, nseq, nbytes, nsub=None):
+    def _device_containers(self, codec, bufs, counts, nnz, nseq, nbytes, nsub=None, nhid=None):
         """basic_compressor 'lz4' without the lz4 package (codec: lz4_codec), 'deflate' / 'gzip' with device_entropy (deflate_codec),
         'bzip2' with device_bzip2 (bzip2_codec) or 'rans' (rans_codec, a typed back-end: it is also told each column's element width, as
         the per-frame path takes it from the arrays' itemsize, and -- with rans_delta -- each column's filter, by the same rule from its
@@ -297,7 +342,7 @@ class BatchCompressor:
         asks nothing of the streams' format) on the current stream.  -> (containers, frame offsets / lengths)."""
         from . import lz4_codec
         (B, K), P, cols = counts.shape, self.T.H * self.T.W, self.columns
-        at = frame_slices(cols, bufs, counts, nnz, nseq, nbytes, nsub)
+        at = frame_slices(cols, bufs, counts, nnz, nseq, nbytes, nsub, nhid)
         # per frame, in container order: device address and bytes of every column
         addr = torch.stack([bufs[c.name].data_ptr() + c.dtype.itemsize * at[c.name][0] for c in cols], 1).reshape(-1)
         lens = torch.stack([c.dtype.itemsize * at[c.name][1] for c in cols], 1).reshape(-1)
@@ -305,7 +350,9 @@ class BatchCompressor:
         kw = dict(widths=[c.dtype.itemsize for c in cols] * B) if typed else {}
         if typed and self.bc.rans_delta:      # delta for the residual column only (rans_codec.delta_filter)
             kw["filters"] = [codec.delta_filter(c.dtype) for c in cols] * B
-        slots, dst_off, dst_len, _ = codec.encode_descriptors(addr, lens, [c.bound(P, K) for c in cols] * B, **kw)
+        # (the hidden_points column's bound is its buffer's row: 16 + P + 4 rows of the batch's largest frame)
+        bounds = [int(bufs[c.name].shape[1]) if c.cut == "nhid" else c.bound(P, K) for c in cols]
+        slots, dst_off, dst_len, _ = codec.encode_descriptors(addr, lens, bounds * B, **kw)
         cap = int(slots.numel()) + 4 * len(cols) * B
         out, frame = lz4_codec.pack_containers(slots, dst_off, dst_len, B, len(cols), cap)
         return out, frame, (addr, lens, slots, dst_off, dst_len)
@@ -313,7 +360,11 @@ class BatchCompressor:
     def submit(self, frames, ground=None, frame_ids=None):
         """Device part of compress() on the current stream, nothing waited for.  -> a context for collect()."""
         xyz, offs, gnd, npts = self._upload(frames, ground)
-        return self._payload(len(frames), npts, xyz, self.compress_device(xyz, offs, gnd, frame_ids))
+        max_rows = None
+        if self.hidden_points:      # the payload rows are sized from the batch's largest frame
+            from . import records
+            max_rows = max(((records.as_records(f) if self.point_format == "nclt" else f).shape[0] for f in frames), default=0)
+        return self._payload(len(frames), npts, xyz, self.compress_device(xyz, offs, gnd, frame_ids, max_rows=max_rows))
 
     def collect(self, ctx, pool=None):
         """Waits for submit()'s stream and assembles the .rpcc byte strings (host part: casts, container, entropy coder).
@@ -326,11 +377,12 @@ class BatchCompressor:
                 fr = built[1].cpu().numpy()
             else:           # the columns' buffers, the packed ones as far as the batch filled them
                 bufs, tot, cols = ctx["bufs"], ctx["tot"], self.columns
-                counts, nnz, nseq, nbytes, nsub = (None if t is None else t.cpu().numpy() for t in ctx["counts"])
+                counts, nnz, nseq, nbytes, nsub, nhid = (None if t is None else t.cpu().numpy() for t in ctx["counts"])
                 host = {c.name: (bufs[c.name][: int(tot[c.cut].item())] if c.cut in tot else bufs[c.name]).cpu().numpy() for c in cols}
             status = buf.status.cpu().numpy() if self.dbscan else None
             orphans = buf.intensity[2].cpu().numpy() if self.intensity_scale is not None else None
             sub_orphans = buf.subpixel[2].cpu().numpy() if self.subpixel_bits is not None else None
+            hid = tuple(t.cpu().numpy() for t in buf.hidden[1:] + (buf.hidden[0][:, 12:16],)) if self.hidden_points else None
         finally:
             buf.in_flight = False   # everything collect() needs is on the host -- or the call failed: either way the slot is free again
         n = ctx["n"]
@@ -339,12 +391,14 @@ class BatchCompressor:
             self.check_orphans(orphans[:n])
         if sub_orphans is not None:
             self.check_orphans(sub_orphans[:n], "subpixel")
+        if hid is not None:
+            self.check_hidden(*(h[:n] for h in hid))
         if built:
             if (fr[1, :n] < 0).any():
                 raise RuntimeError("rpcc_lz4: the containers of frames %s were not built" % np.flatnonzero(fr[1, :n] < 0).tolist())
             h = built[0][: int((fr[0, :n] + fr[1, :n]).max()) if n else 0].cpu().numpy()
             return [h[o: o + l].tobytes() for o, l in zip(fr[0, :n], fr[1, :n])]
-        assemble = BatchPayload(cols, host, counts, nnz, nseq, nbytes, nsub=nsub).frame      # the object the streaming loader assembles from
+        assemble = BatchPayload(cols, host, counts, nnz, nseq, nbytes, nsub=nsub, nhid=nhid).frame      # the object the streaming loader assembles from
         # a few frames per task: one call into the host library per chunk (compress_utils.pack_frames)
         step = max(1, n // 64) if pool is not None else max(n, 1)
         chunk = lambda lo: pack_frames(self.bc, [assemble(b) for b in range(lo, min(lo + step, n))], uniform=self.uniform)
@@ -386,6 +440,9 @@ class MixedBatchCompressor:
         if kw.get("subpixel_bits") is not None:
             raise NotImplementedError("MixedBatchCompressor: subpixel_bits -- the mixed-geometry call carries no subpixel offsets; use one "
                                       "BatchCompressor(subpixel_bits=...) per lidar")
+        if kw.get("hidden_points"):
+            raise NotImplementedError("MixedBatchCompressor: hidden_points -- the mixed-geometry call carries no hidden points; use one "
+                                      "BatchCompressor(hidden_points=True) per lidar")
         if kw.get("radius_outlier_removal") is not None:
             raise NotImplementedError("MixedBatchCompressor: radius_outlier_removal -- the mixed-geometry call takes the points as they are; "
                                       "filter them first (outlier.radius_outlier_mask), or use one BatchCompressor per lidar")
@@ -467,13 +524,16 @@ class BatchDecompressor:
     CHUNK_BUDGET_BYTES = 2 << 30   # device bytes one chunk may take: padded payloads, bzip2 work slots, work buffer and outputs
 
     def __init__(self, transformer, cluster_num, accuracy, uniform=True, level_acc=None, basic_compressor="bzip2", max_labels=None,
-                 intensity=False, subpixel=False):
+                 intensity=False, subpixel=False, hidden_points=False):
         """intensity=True: every container must carry the 'intensity' trailer (BatchCompressor(intensity_scale=...), --intensity):
         decompress_device returns a fifth tensor, f32 [B,H,W], decompress 4-tuples; a frame without a valid trailer gets
         _lib.STREAM_E_INTENSITY (unless an earlier status applies) and a zero row.  The scale is read from each payload's header."""
         if subpixel:
             raise NotImplementedError("BatchDecompressor: subpixel -- the batch decoder back-projects along the pixels' centre rays; decode "
                                       "containers with the subpixel trailer per frame (tools.decompress.decode_frame(..., subpixel=True))")
+        if hidden_points:
+            raise NotImplementedError("BatchDecompressor: hidden_points -- the batch decoder returns one point per pixel; decode containers "
+                                      "with the hidden_points trailer per frame (tools.decompress.decode_frame(..., hidden_points=True))")
         self.intensity = bool(intensity)
         self.per_frame_rows = cluster_num is None     # DBSCAN streams
         if cluster_num is None:

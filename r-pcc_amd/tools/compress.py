@@ -14,7 +14,7 @@ import numpy as np  # noqa: E402
 
 import rpcc_amd  # noqa: E402,F401
 from rpcc_amd.compress_utils import (BasicCompressor, QuantizationModule, compress_point_cloud,  # noqa: E402
-                                     decompress_point_cloud, encode_intensity, encode_subpixel, read_compressed_bitstream,
+                                     decompress_point_cloud, encode_hidden, encode_intensity, encode_subpixel, read_compressed_bitstream,
                                      save_compressed_bitstream)
 from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.segment_utils import PointCloudSegment  # noqa: E402
@@ -105,6 +105,13 @@ def make_parser(datalist=False):
                         "axis, one more array appended to the container where every other reader ignores it; decompress tools: --subpixel "
                         "(the bits are stored in the container) reads it and turns every decoded point off its pixel's centre ray by the "
                         "coded offsets.  --eval then compares the refined points with the original points, not with the pixel centres.")
+    p.add_argument("--hidden_points", action="store_true",
+                   help="compress tools: carry the points that share a pixel with the one the range image keeps (a quarter of a 64-beam sweep), "
+                        "a count per non-empty pixel and a 16-bit range code per point, one more array appended last to the container where "
+                        "every other reader ignores it; with --subpixel BITS every such point also carries lateral codes of that width.  "
+                        "decompress tools: read it and write these points behind the image points.  The trailer carries no intensity: with "
+                        "--intensity the fourth column of such a row is 0.  --eval then compares the original points with the image points "
+                        "plus the hidden points.")
     p.add_argument("--eval", action="store_true", help="evaluate the reconstruction quality.")
     p.add_argument("--cpu", action="store_true", help="accepted for compatibility; the HIP path has no CPU mode.")
     p.add_argument("--seed", type=int, default=0, help="seed of the ground / plane RANSAC (this build).")
@@ -177,14 +184,24 @@ def make_quantizer(cfg, accuracy, uniform):
                               less_sharp_num=cfg["less_sharp_num"], flat_num=cfg["flat_num"])
 
 
-def print_quality(point_cloud, point_cloud_rec, refined=False):
+def print_hidden_counts(carried, uncarried):
+    """--hidden_points: what the trailer carries, and what it does not when that is not nothing."""
+    print("    Hidden points carried: ", int(carried))
+    if int(uncarried):
+        print("    Hidden points not carried (empty pixel, range code past 65535, more than 255 in a pixel): ", int(uncarried))
+
+
+def print_quality(point_cloud, point_cloud_rec, refined=False, hidden=False):
     """The four metric lines of the reference's --eval (tools/compress.py:185-192, tools/decompress.py:146-150).  refined (--subpixel):
-    point_cloud is the original point list, not the back-projected range image, and a line says so."""
+    point_cloud is the original point list, not the back-projected range image, and a line says so.  hidden (--hidden_points):
+    point_cloud is the original point list and point_cloud_rec the image points followed by the hidden points, and a line says so."""
     from rpcc_amd.evaluate_metrics import calc_chamfer_distance, calc_point_to_point_plane_psnr
     chamfer = calc_chamfer_distance(point_cloud, point_cloud_rec, out=False)
     point_to_point, point_to_plane = calc_point_to_point_plane_psnr(point_cloud, point_cloud_rec, out=False)
     if refined:
         print("    (subpixel: the refined points against the original points)")
+    if hidden:
+        print("    (hidden_points: the image points and the hidden points against the original points)")
     print("    Chamfer Distance (mean): ", chamfer["mean"])
     print("    F1 score (threshold=0.02): ", chamfer["f_score"])
     print("    Point-to-Point PSNR (r=59.7): ", point_to_point["psnr_mean"])
@@ -223,7 +240,7 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
     dataset = build_dataset(lidar_type=args.lidar, channel_distribute_csv=getattr(args, "channel_distribute_csv", None),
                             point_format=point_format_of(args))
     t0 = time.time()
-    want_w, sub_bits = getattr(args, "intensity", False), subpixel_bits_of(args)
+    want_w, sub_bits, want_h = getattr(args, "intensity", False), subpixel_bits_of(args), getattr(args, "hidden_points", False)
     if want_w:     # the rows as stored (filtered like the points): the batch front-end makes the payload from its own range image
         frame = load_intensity_rows(dataset, args.input, getattr(args, "use_radius_outlier_removal", False))
     else:
@@ -236,7 +253,7 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
                          compressor_cfg=dict(cfg), basic_compressor=basic_compressor.method_name, seed=args.seed,
                          device_entropy=basic_compressor.device_entropy, device_bzip2=basic_compressor.device_bzip2,
                          rans_delta=basic_compressor.rans_delta, intensity_scale=args.intensity_scale if want_w else None,
-                         subpixel_bits=sub_bits)
+                         subpixel_bits=sub_bits, hidden_points=want_h)
     blob = bc.compress([frame], frame_ids=[frame_identity(args.input)])[0]
     with open(args.output, "wb") as f:
         f.write(blob)
@@ -250,13 +267,15 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
     print("\nCompression Results: ")
     print("    Compression ratio: ", (point_num * 32 * 3) / bits)
     print("    BPP: ", bits / point_num)
+    if want_h:
+        print_hidden_counts(bc.hidden_carried[0], bc.hidden_uncarried[0])
     if args.eval:
         from rpcc_amd.tools.decompress import decode_frame
         level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
         want_s = sub_bits is not None
-        rec, pc_s, _, *w = decode_frame(read_compressed_bitstream(args.output, uniform=uniform, intensity=want_w, subpixel=want_s), basic_compressor,
-                                        dataset.PCTransformer, segment_cfg["cluster_num"], accuracy, level_acc, uniform, want_points=want_s,
-                                        intensity=want_w, subpixel=want_s)
+        rec, pc_s, _, *w = decode_frame(read_compressed_bitstream(args.output, uniform=uniform, intensity=want_w, subpixel=want_s, hidden_points=want_h),
+                                        basic_compressor, dataset.PCTransformer, segment_cfg["cluster_num"], accuracy, level_acc, uniform,
+                                        want_points=want_s or want_h, intensity=want_w, subpixel=want_s, hidden_points=want_h)
         ri = buf.ri[0].cpu().numpy()
         dif = np.abs(rec - ri)   # every pixel, empty ones included, as compress() below and tools/compress.py:172-181
         bound = accuracy + (0.0 if uniform else 0.06) + 0.00001
@@ -266,8 +285,8 @@ def compress_wide(args, cfg, accuracy, segment_cfg, model_cfg, basic_compressor,
         if float(np.max(dif)) > bound:
             raise AssertionError("Reconstruction error... Please check...")
         T = dataset.PCTransformer
-        if want_s:
-            print_quality(frame[:, :3], pc_s, refined=True)
+        if want_s or want_h:
+            print_quality(frame[:, :3], pc_s, refined=want_s, hidden=want_h)
         else:
             print_quality(T.range_image_to_point_cloud(ri), T.range_image_to_point_cloud(rec))
         if want_w:
@@ -317,8 +336,17 @@ def compress(args):
             from rpcc_amd.outlier import remove_radius_outlier
             kept, _ = remove_radius_outlier(original_point_cloud, nb_points=3, radius=1)
         sub_payload, _ = encode_subpixel(dataset.PCTransformer, kept, range_image[..., 0], sub_bits)
+    want_h, hid_payload, hid_uncarried = getattr(args, "hidden_points", False), None, 0
+    if want_h:     # the same points; lateral codes of --subpixel's width where that is given
+        if kept is None:
+            kept = rows if rows is not None else original_point_cloud
+            if filtered and rows is None:
+                from rpcc_amd.outlier import remove_radius_outlier
+                kept, _ = remove_radius_outlier(original_point_cloud, nb_points=3, radius=1)
+        hid_payload, hid_uncarried = encode_hidden(dataset.PCTransformer, kept, range_image[..., 0], accuracy, sub_bits or 0)
     original_data, compressed_data = compress_point_cloud(basic_compressor, model_param, seg_idx, salience_level,
-                                                          residual_quantized, full=False, intensity=payload, subpixel=sub_payload)
+                                                          residual_quantized, full=False, intensity=payload, subpixel=sub_payload,
+                                                          hidden_points=hid_payload)
     t_basic_compressor = time.time()
     save_compressed_bitstream(args.output, compressed_data, uniform=uniform)
     t_save = time.time()
@@ -339,6 +367,8 @@ def compress(args):
     print("\nCompression Results: ")
     print("    Compression ratio: ", (point_num * 32 * 3) / bits)
     print("    BPP: ", bits / point_num)
+    if want_h:
+        print_hidden_counts(int(np.frombuffer(hid_payload[12:16].tobytes(), "<u4")[0]), hid_uncarried)
     print("\n")
 
     if args.eval:
@@ -355,19 +385,22 @@ def compress(args):
         print("    Depth Error (max): ", float(np.max(dif)))
         if float(np.max(dif)) > bound:
             raise AssertionError("Reconstruction error... Please check...")
-        if sub_bits is not None:
+        want_s = sub_bits is not None
+        if want_s or want_h:
             from rpcc_amd.tools.decompress import decode_frame
             level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
-            refined = decode_frame(read_compressed_bitstream(args.output, uniform=uniform, intensity=want_w, subpixel=True), basic_compressor,
-                                   dataset.PCTransformer, None if segment_cfg["segment_method"] == "DBSCAN" else segment_cfg["cluster_num"],
-                                   accuracy, level_acc, uniform, subpixel=True)[1]
-            print_quality(np.asarray(kept)[:, :3], refined, refined=True)
+            refined = decode_frame(read_compressed_bitstream(args.output, uniform=uniform, intensity=want_w, subpixel=want_s, hidden_points=want_h),
+                                   basic_compressor, dataset.PCTransformer,
+                                   None if segment_cfg["segment_method"] == "DBSCAN" else segment_cfg["cluster_num"],
+                                   accuracy, level_acc, uniform, subpixel=want_s, hidden_points=want_h)[1]
+            print_quality(np.asarray(kept)[:, :3], refined, refined=want_s, hidden=want_h)
         else:
             print_quality(point_cloud, dataset.PCTransformer.range_image_to_point_cloud(rec))
         if want_w:
             from rpcc_amd.tools.decompress import decode_frame
             level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
-            w = decode_frame(read_compressed_bitstream(args.output, uniform=uniform, intensity=True, subpixel=sub_bits is not None), basic_compressor, dataset.PCTransformer,
+            w = decode_frame(read_compressed_bitstream(args.output, uniform=uniform, intensity=True, subpixel=sub_bits is not None, hidden_points=want_h),
+                             basic_compressor, dataset.PCTransformer,
                              None if segment_cfg["segment_method"] == "DBSCAN" else segment_cfg["cluster_num"], accuracy, level_acc, uniform,
                              want_points=False, intensity=True)[3]
             print_intensity_error(dataset.PCTransformer, rows, range_image[..., 0], w)

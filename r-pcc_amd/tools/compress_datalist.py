@@ -83,8 +83,8 @@ def init_gather_group(rank, world, local):
     return dist
 
 
-def resolve_ingest(want, names, intensity=False, point_format=None, subpixel=False):
-    """The ingest mode of a whole datalist (--ingest, --intensity, --subpixel, --input_format; names: its file names) -> "rows", "xyz" or "nclt";
+def resolve_ingest(want, names, intensity=False, point_format=None, subpixel=False, hidden_points=False):
+    """The ingest mode of a whole datalist (--ingest, --intensity, --subpixel, --hidden_points, --input_format; names: its file names) -> "rows", "xyz" or "nclt";
     SystemExit for a combination the options exclude.  --input_format nclt always stages the records themselves (8 bytes per point,
     the intensity byte among them), so it goes with --ingest auto only."""
     all_bin = all(str(name).endswith(".bin") for name in names)
@@ -100,6 +100,11 @@ def resolve_ingest(want, names, intensity=False, point_format=None, subpixel=Fal
         if not all_bin or want == "xyz":
             raise SystemExit("--subpixel on a datalist needs .bin files: its kernels read 16-byte rows, which the streaming loader stages from .bin files "
                              "only (the fourth column is not read)" + ("; --ingest xyz stages 12-byte points" if want == "xyz" else ""))
+        want = "rows"
+    if hidden_points:  # --subpixel's limit: the same owner pass
+        if not all_bin or want == "xyz":
+            raise SystemExit("--hidden_points on a datalist needs .bin files: its kernels read 16-byte rows, which the streaming loader stages from .bin "
+                             "files only (the fourth column is not read)" + ("; --ingest xyz stages 12-byte points" if want == "xyz" else ""))
         want = "rows"
     if want == "rows" and not all_bin:
         raise SystemExit("--ingest rows needs a datalist of .bin files (float32 rows x, y, z, intensity)")
@@ -136,12 +141,12 @@ def compress(args, streaming_factory=None):
                          max_labels=getattr(args, "max_labels", None),
                          radius_outlier_removal=(3, 1.0) if getattr(args, "use_radius_outlier_removal", False) else None,
                          intensity_scale=args.intensity_scale if getattr(args, "intensity", False) else None,
-                         subpixel_bits=subpixel_bits_of(args))
+                         subpixel_bits=subpixel_bits_of(args), hidden_points=getattr(args, "hidden_points", False))
     mine = shard_indices(len(dataset), rank, world)
     # the ingest mode follows from the WHOLE datalist -- the same decision on every rank, also on one whose shard is empty -- and is
     # settled before the process group forms, so that a datalist --ingest rows cannot take fails on all ranks together
     ingest = resolve_ingest(getattr(args, "ingest", "auto"), dataset.data_list, getattr(args, "intensity", False), point_format_of(args),
-                            subpixel=subpixel_bits_of(args) is not None)
+                            subpixel=subpixel_bits_of(args) is not None, hidden_points=getattr(args, "hidden_points", False))
     gather = None
     if getattr(args, "gather", False):
         import torch
@@ -188,6 +193,9 @@ def compress(args, streaming_factory=None):
     print("rank %d/%d: %d frames in %.3f s (%.1f frames/s incl. file I/O and entropy coding), %d files / %d bytes written%s"
           % (rank, world, len(mine), dt, len(mine) / max(dt, 1e-9), stats["files"], stats["bytes"],
              " (gathered to rank 0 over the process group)" if gather is not None else ""))
+    if getattr(args, "hidden_points", False):
+        print("rank %d/%d: hidden points carried: %d%s" % (rank, world, bc.hidden_totals[0],
+                                                            ", not carried: %d" % bc.hidden_totals[1] if bc.hidden_totals[1] else ""))
     if gather is not None:
         import torch.distributed as dist
         dist.barrier()

@@ -15,7 +15,8 @@ import torch  # noqa: E402
 
 import rpcc_amd  # noqa: E402,F401
 from rpcc_amd import ops  # noqa: E402
-from rpcc_amd.compress_utils import decompress_point_cloud, parse_intensity_payload, parse_subpixel_payload, read_compressed_bitstream  # noqa: E402,F401
+from rpcc_amd.compress_utils import (decompress_point_cloud, parse_hidden_payload, parse_intensity_payload, parse_subpixel_payload,  # noqa: E402,F401
+                                     read_compressed_bitstream)
 from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.tools.compress import make_parser, point_format_of, print_intensity_error, print_quality, resolve_cfg  # noqa: E402
 
@@ -27,14 +28,18 @@ def stream_cluster_num(segment_cfg):
 
 
 def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy, level_acc, uniform, want_points=True, decoded=None,
-                 intensity=False, subpixel=False):
+                 intensity=False, subpixel=False, hidden_points=False):
     """decompress_point_cloud + dequantise + predict + back-project (tools/decompress.py:79-112).  cluster_num None
     (DBSCAN, stream_cluster_num): the labels 0 .. rows - 1 of the stream's model rows.  decoded: blob_dict's arrays with the entropy
     stage already undone (basic_compressor.decompress_dicts over a chunk of frames).
     intensity=True: blob_dict holds the container's 'intensity' trailer (unpack_bitstream(..., intensity=True)); a fourth value is
     returned, f32 [H,W], by ops.intensity_decode on the label map just recovered; ValueError when the payload is refused.
     subpixel=True: blob_dict holds the 'subpixel' trailer (unpack_bitstream(..., subpixel=True)); the points come from ops.subpixel_decode
-    -- every non-empty pixel's ray turned by its two coded offsets -- instead of ops.backproject; ValueError when the payload is refused."""
+    -- every non-empty pixel's ray turned by its two coded offsets -- instead of ops.backproject; ValueError when the payload is refused.
+    hidden_points=True: blob_dict holds the 'hidden_points' trailer (unpack_bitstream(..., hidden_points=True)); the points returned are
+    f32 [H*W + m, 3]: the image points in raster order, then the m hidden points in payload order, by ops.hidden_decode (on their pixel's
+    centre ray, or turned by their own lateral codes where the payload carries them); ValueError when the payload is refused.  The
+    intensity image stays [H,W]: the trailer carries no intensity."""
     H, W = transformer.H, transformer.W
     d = basic_compressor.decompress_dict(blob_dict) if decoded is None else decoded
     # The .rpcc file stores no configuration (as in the reference): a wrong --lidar / cluster_num / framework shows up as
@@ -88,6 +93,11 @@ def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy
             raise ValueError("the bitstream holds no subpixel payload (compressed without --subpixel?)")
         parse_subpixel_payload(d["subpixel"], n_nonempty)     # (the refusals in words; the device decoder checks the same)
         tables = transformer.subpixel_tables()
+    if hidden_points:
+        if "hidden_points" not in d:
+            raise ValueError("the bitstream holds no hidden_points payload (compressed without --hidden_points?)")
+        hid_bits, _, _, hid_k, _, _ = parse_hidden_payload(d["hidden_points"], n_nonempty)     # (the refusals in words; the device decoder checks the same)
+        hid_tables = transformer.subpixel_tables() if hid_bits else None
     centre_rays = want_points and not subpixel
     if uniform:
         rec, pc = ops.decode(seg, q, model, transformer.tm_dev, accuracy, want_points=centre_rays)
@@ -104,7 +114,15 @@ def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy
         pc, status = ops.subpixel_decode(pay, nbytes, seg, rec.reshape(1, H, W).contiguous(), tables)
         if int(status[0]) != 0:
             raise ValueError("subpixel payload refused by the device decoder (status %d)" % int(status[0]))
-    out = rec[0].cpu().numpy(), (pc[0].cpu().numpy() if pc is not None else None), seg[0].cpu().numpy()
+    pts = pc[0].cpu().numpy() if pc is not None else None
+    if hidden_points and want_points:
+        pay = torch.from_numpy(np.frombuffer(d["hidden_points"], dtype=np.uint8).copy()[None]).to(dev)
+        nbytes = torch.tensor([pay.shape[1]], dtype=torch.int32, device=dev)
+        hid, count, status = ops.hidden_decode(pay, nbytes, seg, transformer.tm_dev, hid_tables, capacity=hid_k.shape[0])
+        if int(status[0]) != 0:
+            raise ValueError("hidden_points payload refused by the device decoder (status %d)" % int(status[0]))
+        pts = np.concatenate([pts.reshape(-1, 3), hid[0, : int(count[0])].cpu().numpy()])
+    out = rec[0].cpu().numpy(), pts, seg[0].cpu().numpy()
     if not intensity:
         return out
     if "intensity" not in d:
@@ -120,6 +138,13 @@ def decode_frame(blob_dict, basic_compressor, transformer, cluster_num, accuracy
     return out + (w[0].cpu().numpy(),)
 
 
+def point_intensity(w, pc):
+    """The fourth column of the points decode_frame returned: the intensity image's values, then +0.0 for every hidden point behind them (the
+    hidden_points trailer carries no intensity)."""
+    w = np.asarray(w, dtype=np.float32).reshape(-1)
+    return np.concatenate([w, np.zeros(pc.reshape(-1, 3).shape[0] - w.shape[0], np.float32)])
+
+
 def decompress(args):
     if args.eval and args.original_point_cloud is None:
         raise ValueError("--eval compares with the original point cloud: set --original_point_cloud")
@@ -130,15 +155,18 @@ def decompress(args):
     level_acc = np.array([accuracy] * len(cfg["level_key_point_num"])) + np.array(cfg["level_delta_acc"])
     t0 = time.time()
     want_w, want_s = getattr(args, "intensity", False), getattr(args, "subpixel", None) is not None
-    cd = read_compressed_bitstream(args.input, uniform=uniform, intensity=want_w, subpixel=want_s)
+    want_h = getattr(args, "hidden_points", False)
+    cd = read_compressed_bitstream(args.input, uniform=uniform, intensity=want_w, subpixel=want_s, hidden_points=want_h)
     rec, pc, seg, *w = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
-                                    level_acc, uniform, intensity=want_w, subpixel=want_s)
+                                    level_acc, uniform, intensity=want_w, subpixel=want_s, hidden_points=want_h)
     t1 = time.time()
-    dataset.save_point_cloud_to_file(args.output, pc.reshape(-1, 3), intensity=w[0].reshape(-1) if want_w else None)
+    dataset.save_point_cloud_to_file(args.output, pc.reshape(-1, 3), intensity=point_intensity(w[0], pc) if want_w else None)
     print("\nDecompression finished.")
     print("reconstructed point cloud save in ", args.output)
     print("    Decode time: ", t1 - t0)
     print("    Points: ", int((rec != 0).sum()))
+    if want_h:
+        print("    Hidden points: ", pc.reshape(-1, 3).shape[0] - rec.size)
     if args.eval:
         print("\nStart evaluation...")
         point_cloud, range_image, original = dataset.load_range_image_points_from_file(args.original_point_cloud)
@@ -150,7 +178,7 @@ def decompress(args):
         print("    Compression Ratio: ", (n_points * 32 * 3) / bits)
         print("    Depth Error (mean): ", float(np.mean(dif)))
         print("    Depth Error (max): ", float(np.max(dif)))
-        print_quality(original if want_s else point_cloud, pc, refined=want_s)
+        print_quality(original if want_s or want_h else point_cloud, pc, refined=want_s, hidden=want_h)
         if want_w:
             print_intensity_error(dataset.PCTransformer, dataset.load_rows(args.original_point_cloud), range_image[..., 0], w[0])
 

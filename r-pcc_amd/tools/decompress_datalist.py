@@ -15,7 +15,7 @@ from rpcc_amd.compress_utils import read_compressed_bitstream  # noqa: E402
 from rpcc_amd.dataset import build_dataset  # noqa: E402
 from rpcc_amd.sharding import shard_indices  # noqa: E402
 from rpcc_amd.tools.compress import make_parser, point_format_of, resolve_cfg  # noqa: E402
-from rpcc_amd.tools.decompress import decode_frame, stream_cluster_num  # noqa: E402
+from rpcc_amd.tools.decompress import decode_frame, point_intensity, stream_cluster_num  # noqa: E402
 
 
 CHUNK = 32   # .rpcc files read and entropy-decoded together
@@ -69,6 +69,10 @@ def decompress(args):
         raise NotImplementedError("--%s with --subpixel: the batch decoder back-projects along the pixels' centre rays; decode containers with "
                                   "the subpixel trailer without --batch_decode / --stream_decode (the per-frame path)"
                                   % ("stream_decode" if getattr(args, "stream_decode", False) else "batch_decode"))
+    if getattr(args, "batch_decode", False) and getattr(args, "hidden_points", False):
+        raise NotImplementedError("--%s with --hidden_points: the batch decoder returns one point per pixel; decode containers with the "
+                                  "hidden_points trailer without --batch_decode / --stream_decode (the per-frame path)"
+                                  % ("stream_decode" if getattr(args, "stream_decode", False) else "batch_decode"))
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
     # (--input_format: how the dataset reads original point files; this tool reads none, its outputs are float .bin files either way)
     dataset = build_dataset(datalist=args.datalist, lidar_type=args.lidar, device=device,
@@ -80,15 +84,16 @@ def decompress(args):
     for c0 in range(0, len(mine), CHUNK):
         names = [dataset.data_list[i] for i in mine[c0: c0 + CHUNK]]
         want_w, want_s = getattr(args, "intensity", False), getattr(args, "subpixel", None) is not None
-        cds = [read_compressed_bitstream(name, uniform=uniform, intensity=want_w, subpixel=want_s) for name in names]
+        want_h = getattr(args, "hidden_points", False)
+        cds = [read_compressed_bitstream(name, uniform=uniform, intensity=want_w, subpixel=want_s, hidden_points=want_h) for name in names]
         for name, cd, d in zip(names, cds, basic_compressor.decompress_dicts(cds)):   # the chunk's entropy stage in one call where the back-end has one
             rec, pc, _, *w = decode_frame(cd, basic_compressor, dataset.PCTransformer, stream_cluster_num(segment_cfg), accuracy,
-                                          level_acc, uniform, decoded=d, intensity=want_w, subpixel=want_s)
+                                          level_acc, uniform, decoded=d, intensity=want_w, subpixel=want_s, hidden_points=want_h)
             rel = name[1:] if name.startswith("/") else name
             out = os.path.join(args.output_dir, rel)
             out = out.replace(out.split(".")[-1], "bin")
             os.makedirs(os.path.dirname(out), exist_ok=True)
-            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3), intensity=w[0].reshape(-1) if w else None)
+            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3), intensity=point_intensity(w[0], pc) if w else None)
             if args.output:
                 print("%s -> %s (%d points)" % (name, out, int((rec != 0).sum())))
 

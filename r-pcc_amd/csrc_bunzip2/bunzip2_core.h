@@ -426,12 +426,16 @@ BZ_FN int bunzip2_stream(BzShared &S, const int lane, const uint8_t *__restrict_
                     const unsigned long long m = BZ_BALLOT((uc >> b) & 1u);
                     peers &= ((uc >> b) & 1u) ? m : ~m;
                 }
+                uint32_t at = 0;
+                bool moves = false;          // the last of the byte's lanes moves its place on
                 if (live) {
                     const int rank = __builtin_popcountll(peers & below), all = __builtin_popcountll(peers);
-                    const uint32_t at = S.cftab[uc] + (uint32_t)rank;
-                    tt[at] = (uint32_t)i << 8 | uc;
-                    if (rank == all - 1) S.cftab[uc] = at + 1u;
+                    at = S.cftab[uc] + (uint32_t)rank;
+                    moves = rank == all - 1;
                 }
+                BZ_SYNC();                   // every lane of the byte has read its place before one of them writes it
+                if (moves) S.cftab[uc] = at + 1u;
+                if (live) tt[at] = (uint32_t)i << 8 | uc;
                 BZ_SYNC();
             }
         }

@@ -4,7 +4,8 @@ the GPU), built on the CPU once per process; every stream is seeded.
 valid()        name -> (stream, the bytes it decodes to)        golden_members()  the four arrays of tests/golden/example_64E.npz
 flips()        every single-bit flip of small_stream()          truncations()     every proper prefix of it but the empty one
 hand_built()   name -> (stream, dst_cap, nblock_max, status): one stream per rule, written with a small bit writer and block encoder
-FLIP_CAP, FLIP_BLOCK: the capacity and work-slot block length the flips and truncations are decoded with."""
+FLIP_CAP, FLIP_BLOCK: the capacity and work-slot block length the flips and truncations are decoded with.
+many_lane()    [(name, stream, dst_cap, work block length)]: the part of all these that the 64-thread host build runs"""
 import bz2
 import functools
 import os
@@ -80,6 +81,20 @@ def flips():
 def truncations():
     s, _ = small_stream()
     return [s[:k] for k in range(1, len(s))]
+
+
+# The many-lane host run (tests/test_bunzip2_core_host.py) costs a dozen thread barriers for every symbol, so it takes the valid streams
+# of at most MANY_LANE_STREAM bytes and every MANY_LANE_STRIDE-th flip and truncation.
+MANY_LANE_STREAM = 512
+MANY_LANE_STRIDE = 97
+
+
+def many_lane():
+    rows = [(name, s, cap, slot) for name, (s, cap, slot, _) in hand_built().items()] + [("empty", b"", 0, 0)]
+    rows += [(name, s, len(p), R.block_bound(int(s[3:4]), len(p))) for name, (s, p) in valid().items() if len(s) <= MANY_LANE_STREAM]
+    rows += [("flip%d" % k, s, FLIP_CAP, FLIP_BLOCK) for k, s in list(enumerate(flips()))[::MANY_LANE_STRIDE]]
+    rows += [("cut%d" % k, s, FLIP_CAP, FLIP_BLOCK) for k, s in list(enumerate(truncations()))[::MANY_LANE_STRIDE // 8]]
+    return rows
 
 
 # ---- a small bzip2 writer

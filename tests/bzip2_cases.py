@@ -110,3 +110,17 @@ def multi_block():
 
 def everything():
     return {**inputs(), **multi_block()}
+
+
+# The many-thread host run (tests/test_bzip2_core_host.py) wakes 1024 threads at every barrier, a few milliseconds each time, so it takes
+# the smallest input of each path -- nothing, one byte, runs at the RLE1 counts, a periodic block (equal rotations), a block whose
+# bytes are all distinct (no doubling round), three tables, two move-to-front chunks, two tiles of keys -- and one input of two blocks
+# at level 1: 100100 random bytes, no run of four among them, so the first block is full at 99981 and the second holds the other 119.
+MANY_THREAD = ("empty", "one", "rep4", "rep5", "rep260", "ab300", "all256", "zero_run_at_end", "nmtf200", "len%d" % (MTF_CHUNK + 1), "len%d" % (TILE + 1))
+
+
+@functools.lru_cache(maxsize=None)
+def many_thread():
+    c = {k: inputs()[k] for k in MANY_THREAD}
+    c["two_blocks"] = (rnd(17, 100100), 1)
+    return c

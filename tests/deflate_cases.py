@@ -20,12 +20,12 @@ def golden_arrays():
     return gen_golden_lz4.arrays()
 
 
-def far_pattern(distance):
-    """40000 bytes, zero but for one 20-byte pattern and its copy `distance` bytes later."""
+def far_pattern(distance, length=20):
+    """40000 bytes, zero but for one pattern of `length` bytes and its copy `distance` bytes later."""
     rng = np.random.default_rng(5)
     a = np.zeros(40000, np.uint8)
-    a[100:120] = rng.integers(1, 256, 20, dtype=np.uint8)
-    a[distance + 100: distance + 120] = a[100:120]
+    a[100:100 + length] = rng.integers(1, 256, length, dtype=np.uint8)
+    a[distance + 100: distance + 100 + length] = a[100:100 + length]
     return a.tobytes()
 
 

@@ -3,7 +3,8 @@ per process; every stream is seeded.
 
 valid()      name -> (stream, the bytes it decodes to, check(report)): each case says through inflate_ref's report what it is there for
 flips()      every single-bit flip of four small members         truncations()  every proper prefix of one, but the empty one
-hand_built() name -> (stream, dst_cap, status): one stream per status and per table rule, written with a small bit writer"""
+hand_built() name -> (stream, dst_cap, status): one stream per status and per table rule, written with a small bit writer
+many_lane()  [(name, stream, dst_cap)]: the part of all these that the 64-thread host build runs (tests/test_inflate_core_host.py)"""
 import functools
 import gzip
 import io
@@ -39,6 +40,13 @@ def _blocks(kind, lo, hi=None):
 def _match(distance, length):
     def check(rep):
         assert rep["max_distance"] == distance and rep["max_match"] == length, rep
+    return check
+
+
+def _far(distance):
+    """A match of 258 bytes at this distance, the largest of the stream: every lane of a copy step takes part at it."""
+    def check(rep):
+        assert rep["max_distance"] == distance and rep["max_match"] == 258 and rep["far_match"] >= 64, rep
     return check
 
 
@@ -85,6 +93,21 @@ def valid():
     out["zeros_ref"] = (deflate_ref.compress(src), src, _match(1, 258))
     src = deflate_cases.far_pattern(32768)
     out["far_32768"] = (deflate_ref.compress(src), src, _match(32768, 258))   # zlib itself stops at 32506
+    # at 32768 every lane of a copy step reads the ring slot it fills itself; at 32705 .. 32767 it reads one that another lane fills in
+    # the same step (lane + 32768 - distance), so the step's loads must all come before its stores; 32704 is the last distance without
+    for d in (32704, 32705, 32737, 32767):
+        src = deflate_cases.far_pattern(d, 258)
+        out["far_%d" % d] = (deflate_ref.compress(src), src, _far(d))
+    # short distances with whole-wave matches: the copy's periodic branch (k < P) below, at and above the wave's 64 lanes
+    for d in (2, 3, 63, 64, 65):
+        src = (rng.integers(1, 256, d, dtype=np.uint8).tobytes() * (700 // d + 2))[:700]
+        out["near_%d" % d] = (deflate_ref.compress(src), src, _far(d))
+    # 4100 periodic bytes, then 200 random ones: the byte that fills a piece of 4160 is a literal, stored by one lane just before the flush
+    src = (rng.integers(1, 256, 7, dtype=np.uint8).tobytes() * 600)[:4100] + rng.integers(0, 256, 200, dtype=np.uint8).tobytes()
+
+    def literal_fills_the_piece(rep):
+        assert rep["max_distance"] == 7 and set(rep["blocks"]) <= {FIXED, DYNAMIC}, rep
+    out["flush_at_literal"] = (_z(src, 9), src, literal_fills_the_piece)
     for name, a in deflate_cases.golden_arrays().items():
         src = np.ascontiguousarray(a).tobytes()
         chk = _turns(src, 5) if len(src) == 188106 else _any
@@ -128,6 +151,22 @@ def flips():
 def truncations():
     m, plain = small_members()[0]
     return [(m[:k], len(plain)) for k in range(1, len(m))]
+
+
+# The many-lane host run costs two thread barriers for every symbol, so it takes the streams of at most MANY_LANE_STREAM bytes (the far
+# matches are among them: 40000 bytes from 468), those of MANY_LANE_STORED (a stored byte costs no barrier, and only a stored block of
+# more than a piece flushes inside its own loop) and every MANY_LANE_STRIDE-th flip and truncation.
+MANY_LANE_STREAM = 2048
+MANY_LANE_STORED = ("level0_65536", "stored_blocks")
+MANY_LANE_STRIDE = 211
+
+
+def many_lane():
+    rows = [(name, s, cap) for name, (s, cap, _) in hand_built().items()] + [("empty", b"", 0)]
+    rows += [(name, s, len(p)) for name, (s, p, _) in valid().items() if len(s) <= MANY_LANE_STREAM or name in MANY_LANE_STORED]
+    rows += [("flip%d" % k, s, cap) for k, (s, cap) in list(enumerate(flips()))[::MANY_LANE_STRIDE]]
+    rows += [("cut%d" % k, s, cap) for k, (s, cap) in list(enumerate(truncations()))[::MANY_LANE_STRIDE // 8]]
+    return rows
 
 
 class Bits:

@@ -95,7 +95,7 @@ def inflate(data, cap=None, report=False):
     """-> (status, bytes produced) [, report]: data is one stream of rpcc_inflate_decode, cap its dst_cap (None: no limit)."""
     data = bytes(data)
     out = bytearray()
-    rep = {"blocks": [], "max_code_length": 0, "max_distance": 0, "min_match": None, "max_match": None}
+    rep = {"blocks": [], "max_code_length": 0, "max_distance": 0, "min_match": None, "max_match": None, "far_match": 0}
     try:
         _member(data, out, cap, rep)
         st = OK
@@ -211,6 +211,8 @@ def _member(d, out, cap, rep):
                     raise _Stop(E_OFFSET)
                 if ln > room():
                     raise _Stop(E_OVERRUN)
+                if dist >= rep["max_distance"]:       # far_match: the longest match at the largest distance
+                    rep["far_match"] = ln if dist > rep["max_distance"] else max(rep["far_match"], ln)
                 rep["max_distance"] = max(rep["max_distance"], dist)
                 rep["min_match"] = ln if rep["min_match"] is None else min(rep["min_match"], ln)
                 rep["max_match"] = ln if rep["max_match"] is None else max(rep["max_match"], ln)

@@ -80,7 +80,7 @@ def test_stream_work_bytes_is_the_layouts(built, tmp_path):
         assert lib.rpcc_bunzip2_stream_work_bytes(m) == R.work_bytes(m)
     src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
     # the wave of one lane as tests/bunzip2_host_main.cpp defines it, then a main that prints the layout and its inverse
-    probe = ('#include <cstdio>\n#include <cstdint>\n#include "rpcc_bunzip2.h"\n' + open(os.path.join(ROOT, "tests", "bunzip2_host_main.cpp")).read()
+    probe = ('#include <cstdio>\n#include <cstdint>\n#include <cstdlib>\n#include <cstring>\n#include "rpcc_bunzip2.h"\n' + open(os.path.join(ROOT, "tests", "bunzip2_host_main.cpp")).read()
              .split('#include "rpcc_bunzip2.h"')[1].split("int main")[0]
              + 'int main() { const int64_t m[] = {0, 1, 63, 64, 1999, 100000, 900000};\n'
                '  for (int64_t x : m) printf("%lld %lld %lld\\n", (long long)x, (long long)bz_work_layout(x).bytes, (long long)bz_work_block(bz_work_layout(x).bytes)); }\n')

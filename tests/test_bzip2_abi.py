@@ -77,7 +77,7 @@ def test_bound_and_work_layout_agree(built, tmp_path):
     assert R.bound(0) == 14 + 6450 + 3 and bzip2_codec.block_limit(1) == R.block_limit(1) == 99981
     src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
     # the workgroup of one thread as tests/bzip2_host_main.cpp defines it, then a main that prints the layout
-    probe = ('#include <cstdio>\n#include <cstdint>\n#include "rpcc_bzip2.h"\n' + open(os.path.join(ROOT, "tests", "bzip2_host_main.cpp")).read()
+    probe = ('#include <cstdio>\n#include <cstdint>\n#include <cstdlib>\n#include <cstring>\n#include "rpcc_bzip2.h"\n' + open(os.path.join(ROOT, "tests", "bzip2_host_main.cpp")).read()
              .split('#include "rpcc_bzip2.h"')[1].split("int main")[0]
              + 'int main() { const int64_t m[] = {0, 1, 15, 16, 17, 255, 256, 257, 1999, 99981, 235132, 899981};\n'
                '  for (int64_t x : m) { const BzeLayout w = bze_layout(x);\n'

@@ -470,7 +470,9 @@ def test_batch_compressor_equals_the_per_frame_path(e2e, method, kw, intensity, 
         rec, pc, seg, *w = e2e["dec"](cd, host, T, M, 2 * ACC, None, True, intensity=intensity, subpixel=subpixel, hidden_points=True)
         rec0, pc0, seg0, *w0 = e2e["dec"](cu.unpack_bitstream(base, intensity=intensity, subpixel=subpixel), host, T, M, 2 * ACC, None, True,
                                           intensity=intensity, subpixel=subpixel)                 # the container without the trailer: today's result
-        assert cu.unpack_bitstream(blob) == cu.unpack_bitstream(base)                             # a reader that asks for nothing reads the geometry as ever
+        # a reader that asks for nothing reads the geometry as ever (separate gzip.compress calls: but for the members' MTIME bytes)
+        plain = [{k: v[:4] + v[8:] if isinstance(v, bytes) and v[:3] == b"\x1f\x8b\x08" else v for k, v in cu.unpack_bitstream(c).items()} for c in (blob, base)]
+        assert plain[0] == plain[1]
         if intensity or subpixel:                                                                 # one that asks for the older trailers only is told what is missing
             with pytest.raises(ValueError, match="hidden_points=True"):
                 cu.unpack_bitstream(blob, intensity=intensity, subpixel=subpixel)

@@ -26,6 +26,12 @@ int rpcc_host_version(void);   /* 101 */
 int rpcc_host_pack_bz2(int nframes, int narrays, const void *const *src, const uint32_t *src_bytes, uint8_t *dst,
                        const uint64_t *dst_off, uint32_t *dst_bytes);
 
+/* The liblzf stream of a .pcd file's `DATA binary_compressed` body (r-pcc_amd/csrc_fields/lzf_decode.h; rpcc_amd/pointfile.py).
+ * src[0 .. src_bytes) -> dst[0 .. dst_bytes); *out_bytes: the bytes written.  Returns 0; 1 when the input ends inside a literal run or a
+ * match, 2 when a match starts before the first output byte, 3 when the output would pass dst_bytes; RPCC_HOST_ERR_ARG for a null
+ * pointer with a length.  Nothing past dst_bytes is written under any status. */
+int rpcc_lzf_decompress(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes, size_t *out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,8 @@ def host_lib():
                 raise OSError("reports interface version %d, this binding needs %d (stale build)" % (h.rpcc_host_version(), HOST_ABI))
             h.rpcc_host_pack_bz2.restype = C.c_int
             h.rpcc_host_pack_bz2.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            h.rpcc_lzf_decompress.restype = C.c_int      # (pointfile.lzf_decompress)
+            h.rpcc_lzf_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         except (OSError, AttributeError) as e:
             _host_failed = "librpcc_host.so (%s): %s" % (HOST_LIB_PATH, e)
             raise RpccError(_host_failed)

@@ -9,6 +9,9 @@ DEPS = [os.path.join(_HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(_
 LIB = os.path.join(_HERE, "lib", "librpcc_hip.so")
 HOST_SRC = os.path.join(_HERE, "csrc", "rpcc_host.c")
 HOST_LIB = os.path.join(_HERE, "lib", "librpcc_host.so")
+# the host LZF decoder of .pcd binary_compressed bodies: a source of its own (csrc_fields/), outside DEPS and source_digest()
+HOST_LZF_SRC = os.path.join(_HERE, "csrc_fields", "rpcc_lzf.c")
+HOST_LZF_DEPS = [HOST_LZF_SRC, os.path.join(_HERE, "csrc_fields", "lzf_decode.h")]
 
 
 def _side_library(subdir, src, header, lib, shared=("csrc_tile",)):
@@ -33,6 +36,7 @@ FILTER_SRC, FILTER_DEPS, FILTER_LIB = _side_library("csrc_filter", "radius_filte
 RANS_SRC, RANS_DEPS, RANS_LIB = _side_library("csrc_rans", "rans_kernels.hip", "rpcc_rans.h", "librpcc_rans.so")   # chunk-parallel rANS back-end
 RECORDS_SRC, RECORDS_DEPS, RECORDS_LIB = _side_library("csrc_records", "records_kernels.hip", "rpcc_records.h", "librpcc_records.so")   # NCLT record unpack
 ROWS_SRC, ROWS_DEPS, ROWS_LIB = _side_library("csrc_rows", "rows_kernels.hip", "rpcc_rows.h", "librpcc_rows.so")   # decoded batch -> .bin rows
+FIELDS_SRC, FIELDS_DEPS, FIELDS_LIB = _side_library("csrc_fields", "fields_kernels.hip", "rpcc_fields.h", "librpcc_fields.so")   # .pcd / .ply record unpack
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -54,11 +58,12 @@ def source_digest():
 
 
 def build_host(force=False, verbose=False):
-    """librpcc_host.so: the plain-C container packer (bzip2 through the libbz2 the interpreter's bz2 module links)."""
+    """librpcc_host.so: the plain-C container packer (bzip2 through the libbz2 the interpreter's bz2 module links) and the LZF decoder of
+    .pcd binary_compressed bodies."""
     os.makedirs(os.path.dirname(HOST_LIB), exist_ok=True)
-    if not force and os.path.exists(HOST_LIB) and os.path.getmtime(HOST_LIB) >= os.path.getmtime(HOST_SRC):
+    if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(HOST_LIB) >= os.path.getmtime(d) for d in [HOST_SRC] + HOST_LZF_DEPS):
         return HOST_LIB
-    cmd = [os.environ.get("CC", "gcc"), "-O2", "-shared", "-fPIC", "-Wall", HOST_SRC, "-o", HOST_LIB, "-l:libbz2.so.1.0"]
+    cmd = [os.environ.get("CC", "gcc"), "-O2", "-shared", "-fPIC", "-Wall", HOST_SRC, HOST_LZF_SRC, "-o", HOST_LIB, "-l:libbz2.so.1.0"]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -133,6 +138,11 @@ def build_rows(force=False, verbose=False):
     return _hipcc(ROWS_SRC, ROWS_LIB, ROWS_DEPS, force, verbose)
 
 
+def build_fields(force=False, verbose=False):
+    """librpcc_fields.so: the .pcd / .ply record unpack kernel (csrc_fields/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(FIELDS_SRC, FIELDS_LIB, FIELDS_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -149,6 +159,7 @@ def build(force=False, verbose=False):
     build_rans(force, verbose)
     build_records(force, verbose)
     build_rows(force, verbose)
+    build_fields(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

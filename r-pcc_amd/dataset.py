@@ -4,13 +4,15 @@ range-image loader.  use_radius_outlier_removal (dataset/dataset.py:29-35, Open3
 radius=1)) runs on the GPU through outlier.remove_radius_outlier (librpcc_filter.so).  Of the reference's
 dataset-specific classes (dataset/datasets/*.py) the one with logic of its own is here: NcltDataset reads NCLT's velodyne_sync
 records (nclt_dataset.py:36-63) through records.unpack_host, bit-equal to the reference's preprocessing; the
-other three only call Open3D on .pcd files.  The Open3D formats (.ply/.pcd read, .pcd write) are out of scope."""
+other three only call Open3D on .pcd files, rewriting each as a .bin with a zero fourth column; here .pcd and .ply files are read as they
+are, intensity included, through pointfile.read_rows, and save_point_cloud_to_file writes .pcd as well.  Open3D's
+colour output and big-endian .ply stay out of scope."""
 import os
 import struct
 
 import numpy as np
 
-from . import records
+from . import pointfile, records
 from .transformer import PCTransformer
 
 _CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lidar_cfg")
@@ -72,6 +74,8 @@ class DatasetTemplate:
             pc = np.fromfile(file, dtype=np.float32).reshape((-1, 4))
         elif ext in ("npy", "npz"):
             pc = np.load(file)
+        elif ext in pointfile.EXTENSIONS:
+            pc = pointfile.read_rows(file)
         else:
             assert False, "File type not correct: " + file
         return pc[:, :3]
@@ -79,10 +83,13 @@ class DatasetTemplate:
     @staticmethod
     def load_rows(file):
         """The sweep as stored, with its fourth column (not the reference's: load_data drops it) -> f32 [N,4] rows (x, y, z, intensity),
-        from a .bin, or from a .txt / .npy with at least 4 columns."""
+        from a .bin, or from a .txt / .npy with at least 4 columns.  A .pcd / .ply gives its `intensity` field, or zeros where it has none:
+        that is the file's own statement about its points."""
         ext = file.split(".")[-1]
         if ext == "bin":
             return np.fromfile(file, dtype=np.float32).reshape((-1, 4))
+        if ext in pointfile.EXTENSIONS:
+            return pointfile.read_rows(file)
         if ext == "txt":
             pc = np.loadtxt(file, ndmin=2)
         elif ext == "npy":
@@ -102,8 +109,9 @@ class DatasetTemplate:
 
     @staticmethod
     def save_point_cloud_to_file(file, point_cloud, color=None, intensity=None):
-        """dataset/dataset.py:72-107 (txt / bin / npy / ply).  intensity (one value per point, not the reference's): the fourth column of
-        txt / bin / npy instead of zeros, a fourth float property `intensity` of a ply; it goes through the same sum != 0 filter."""
+        """dataset/dataset.py:72-107 (txt / bin / npy / ply / pcd).  intensity (one value per point, not the reference's): the fourth column
+        of txt / bin / npy instead of zeros, a fourth float property `intensity` of a ply, a fourth field of a pcd; it goes through the same
+        sum != 0 filter.  A pcd is DATA binary, FIELDS x y z [intensity], float32, HEIGHT 1 (pointfile.write_pcd); color is not written."""
         ext = file.split(".")[-1]
         keep = np.where(np.sum(point_cloud, -1) != 0)
         point_cloud = point_cloud[keep]
@@ -125,6 +133,8 @@ class DatasetTemplate:
                            % (point_cloud.shape[0], "" if intensity is None else "property float intensity\n")).encode())
                 body = point_cloud[:, :3] if intensity is None else np.concatenate((point_cloud[:, :3], intensity[:, None]), -1)
                 fid.write(np.ascontiguousarray(body, dtype="<f4").tobytes())
+        elif ext == "pcd":
+            pointfile.write_pcd(file, point_cloud, intensity)
         else:
             assert False, "File type not correct."
 

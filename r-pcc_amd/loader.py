@@ -25,16 +25,18 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib, ops, records
+from . import _lib, ops, pointfile, records
 from .compress_utils import BatchPayload, pack_bitstream, pack_frames  # noqa: F401
 from .utils import available_cpus
 
 
 class _Slot:
-    def __init__(self, bc, B, cap_points, device, cols=3, nclt=False):
+    def __init__(self, bc, B, cap_points, device, cols=3, nclt=False, fields=False):
         P, K = bc.T.H * bc.T.W, bc.M + 2
         self.B, self.cap, self.cols = B, int(cap_points), int(cols)    # cols: floats per point in the staging / device input (3 or 4)
         self.nclt = bool(nclt)      # ingest="nclt": records are staged and sent (8 bytes per point); xyz_dev [cap,4] is filled on the device
+        self.fields = bool(fields)  # ingest="fields": the .pcd / .ply files' bytes are staged and sent; xyz_dev [cap,4] is filled on the device
+        self.cap_bytes, self.nbytes = 32 * self.cap, 0     # (fields) bytes of the chunk buffers -- a sizing hint, grow_bytes -- and of the staged chunk
         self._point_buffers(device)
         self.offs_pin = torch.zeros((B + 1,), dtype=torch.int64).pin_memory()
         self.fid_pin = torch.zeros((B,), dtype=torch.int64).pin_memory()
@@ -81,10 +83,24 @@ class _Slot:
         self.qp = torch.empty((self.cap,), dtype=torch.int16, device=device)
         self.qp_pin = torch.empty((self.cap,), dtype=torch.int16).pin_memory()
 
+    def grow_bytes(self, cap_bytes, device):
+        """ingest="fields": a chunk of more bytes than the slot was sized for.  Only called while the slot is idle."""
+        self.cap_bytes = int(cap_bytes)
+        self.chunk_pin = torch.empty((self.cap_bytes,), dtype=torch.uint8).pin_memory()
+        self.chunk_dev = torch.empty((self.cap_bytes,), dtype=torch.uint8, device=device)
+
     def _point_buffers(self, device):
         """The input buffers of cap points: the pinned staging and its device mirror -- floats, or with nclt the records, whose rows
-        exist on the device only (no pinned float staging)."""
-        if self.nclt:
+        exist on the device only (no pinned float staging); with fields the files' bytes and a descriptor per frame."""
+        if self.fields:
+            self.xyz_pin = None
+            if not hasattr(self, "chunk_pin"):
+                self.grow_bytes(self.cap_bytes, device)
+                self.desc_pin = torch.zeros((self.B, pointfile.DESC_WORDS), dtype=torch.int64).pin_memory()
+                self.desc_dev = torch.zeros((self.B, pointfile.DESC_WORDS), dtype=torch.int64, device=device)
+                self.fstatus_dev = torch.zeros((self.B,), dtype=torch.int32, device=device)
+                self.fstatus_pin = torch.zeros((self.B,), dtype=torch.int32).pin_memory()
+        elif self.nclt:
             self.xyz_pin = None
             self.rec_pin = torch.empty((self.cap, records.RECORD_BYTES), dtype=torch.uint8).pin_memory()
             self.rec_dev = torch.empty((self.cap, records.RECORD_BYTES), dtype=torch.uint8, device=device)
@@ -108,8 +124,13 @@ class StreamingCompressor:
                    "nclt" -- NCLT velodyne_sync records (records.py: 8 bytes per point, the intensity byte among them): frames are
                              record-file PATHS, read straight into a pinned record buffer, or uint8 [N,8] arrays; the records cross
                              the link and records.unpack (librpcc_records.so) writes the stored rows on the device, on the compute
-                             stream in front of the batch call.  8 bytes per point cross the link; intensity_scale is allowed."""
-        assert ingest in ("xyz", "rows", "nclt")
+                             stream in front of the batch call.  8 bytes per point cross the link; intensity_scale is allowed.
+                   "fields" -- .pcd / .ply files (pointfile.py): frames are PATHS.  A worker parses the header, reads the file as it is into
+                             the pinned chunk at a 16-byte aligned offset and fills the frame's descriptor; the chunk crosses the link and
+                             pointfile.unpack_into (librpcc_fields.so) writes the stored rows on the device, intensity included, in front
+                             of the batch call.  A binary_compressed body is LZF-decoded into the chunk by the worker; an ASCII file, or one
+                             with a step above RPCC_FIELDS_MAX_STEP, is parsed by the worker into stored rows in the chunk."""
+        assert ingest in ("xyz", "rows", "nclt", "fields")
         if bc.intensity_scale is not None and ingest == "xyz":
             raise ValueError('StreamingCompressor: a BatchCompressor with intensity_scale needs ingest="rows" (the fourth column must reach the device); '
                              'ingest="xyz" drops it')
@@ -136,7 +157,7 @@ class StreamingCompressor:
         self.enq_pool = ThreadPoolExecutor(1)
         self.side_stream = torch.cuda.Stream(device=self.device)     # late copies that must not queue behind the next batch
         self.seq_eager = max(1024, self.B * P // 16)                # index-sequence entries fetched with the batch (typical: P/20 per frame)
-        self.slots = [_Slot(bc, self.B, self.cap, self.device, cols=3 if ingest == "xyz" else 4, nclt=ingest == "nclt") for _ in range(self.depth)]
+        self.slots = [_Slot(bc, self.B, self.cap, self.device, cols=3 if ingest == "xyz" else 4, nclt=ingest == "nclt", fields=ingest == "fields") for _ in range(self.depth)]
         self.prof = {"stage": 0.0, "enqueue": 0.0, "collect": 0.0, "drain": 0.0}   # host seconds per phase (diagnostics)
         self.stage_chunks = max(1, min(self.B, 16))      # staging tasks per batch: a few MB each (more, smaller tasks are slower)
 
@@ -144,6 +165,8 @@ class StreamingCompressor:
     def _stage(self, slot, frames, frame_ids):
         n = len(frames)
         assert 0 < n <= self.B
+        if self.ingest == "fields":
+            return self._stage_fields(slot, frames, frame_ids)
         nclt = self.ingest == "nclt"
         rows = self.ingest == "rows" or nclt      # whole stored elements, files read in place: float rows, or records
         elem = records.RECORD_BYTES if nclt else 16     # bytes of one
@@ -203,12 +226,79 @@ class StreamingCompressor:
         slot.hid_rows = int(sizes.max()) if n else 0
         return int(offs[n])
 
+    def _stage_fields(self, slot, frames, frame_ids):
+        """ingest="fields": headers first (the chunk's offsets follow from them), then every file into its place in the pinned chunk."""
+        n = len(frames)
+        for f in frames:
+            if not isinstance(f, (str, os.PathLike)):
+                raise ValueError('ingest="fields" takes the paths of .pcd / .ply files')
+        layouts = list(self.pool.map(pointfile.read_layout, frames))
+        direct = [lay.data == "binary" and lay.max_step <= pointfile.MAX_STEP for lay in layouts]
+        sizes_f = [os.path.getsize(f) for f in frames]
+        # bytes of the chunk a frame takes: the file as it is; else the decompressed body, or the rows a worker makes of it
+        need = np.array([sz if d else (lay.body_bytes if lay.data == "binary_compressed" else 16 * lay.n)
+                         for lay, d, sz in zip(layouts, direct, sizes_f)], np.int64)
+        at = np.zeros(n + 1, np.int64)
+        at[1:] = np.cumsum((need + 15) & ~15)          # 16-byte aligned slots
+        sizes = np.fromiter((lay.n for lay in layouts), dtype=np.int64, count=n)
+        offs = np.zeros(self.B + 1, np.int64)
+        offs[1:n + 1] = np.cumsum(sizes)
+        offs[n + 1:] = offs[n]
+        if offs[n] > slot.cap:
+            slot.grow(int(offs[n]) + int(offs[n]) // 4, self.device)
+            self.grown += 1
+        if at[n] > slot.cap_bytes:
+            slot.grow_bytes(int(at[n]) + int(at[n]) // 4, self.device)
+            self.grown += 1
+        dst = slot.chunk_pin.numpy()
+        desc = np.tile(pointfile.stored_layout(0).desc(0), (self.B, 1))      # (the frames a short batch lacks: empty, valid)
+
+        def place(i):
+            lay, path, lo = layouts[i], frames[i], int(at[i])
+            if direct[i]:
+                view = memoryview(dst[lo: lo + sizes_f[i]])
+                with open(path, "rb", buffering=0) as fh:
+                    got = 0
+                    while got < len(view):
+                        m = fh.readinto(view[got:])
+                        if not m:
+                            break
+                        got += m
+                    if got != len(view) or fh.read(1):
+                        raise ValueError("%s changed size while it was read" % path)
+                desc[i] = lay.desc(lo + lay.data_off)
+            elif lay.data == "binary_compressed":
+                with open(path, "rb") as fh:
+                    buf = fh.read()
+                comp, uncomp = pointfile.compressed_sizes(lay, buf)
+                pointfile.lzf_decompress(memoryview(buf)[lay.data_off + 8: lay.data_off + 8 + comp], dst[lo: lo + uncomp], lay.name)
+                desc[i] = lay.desc(lo)
+            else:       # ASCII, or a step the kernel does not take: the host reader's rows, described as stored rows
+                rows = pointfile.read_rows(path)
+                if rows.shape[0] != lay.n:
+                    raise ValueError("%s changed while it was read" % path)
+                dst[lo: lo + 16 * lay.n] = rows.reshape(-1).view(np.uint8)
+                desc[i] = pointfile.stored_layout(lay.n).desc(lo)
+            return 1
+        list(self.pool.map(place, range(n)))
+        slot.desc_pin.numpy()[:] = desc
+        slot.offs_pin.numpy()[:] = offs
+        fid = np.zeros(self.B, np.int64)
+        fid[:n] = np.asarray(frame_ids if frame_ids is not None else np.arange(n), np.int64)[:n]
+        slot.fid_pin.numpy()[:] = fid
+        slot.n, slot.nbytes = n, int(at[n])
+        slot.hid_rows = int(sizes.max()) if n else 0
+        return int(offs[n])
+
     # ---- device part: H2D on the copy stream, everything else on the compute stream ------------------------------------
     def _enqueue(self, slot, npts):
         bc = self.bc
         torch.cuda.set_device(self.device)      # (runs on the enqueue thread)
         with torch.cuda.stream(self.copy_stream):
-            if slot.nclt:
+            if slot.fields:
+                slot.chunk_dev[:slot.nbytes].copy_(slot.chunk_pin[:slot.nbytes], non_blocking=True)
+                slot.desc_dev.copy_(slot.desc_pin, non_blocking=True)
+            elif slot.nclt:
                 slot.rec_dev[:npts].copy_(slot.rec_pin[:npts], non_blocking=True)
             else:
                 slot.xyz_dev[:npts].copy_(slot.xyz_pin[:npts], non_blocking=True)
@@ -219,6 +309,9 @@ class StreamingCompressor:
             self.compute_stream.wait_event(slot.h2d_done)
             if slot.nclt:     # the records -> the stored rows run_batch reads (16-byte stride), in front of it on this stream
                 records.unpack(slot.rec_dev[:npts], out=slot.xyz_dev[:npts])
+            if slot.fields:   # the files' bytes -> the stored rows, every frame of the chunk in one launch
+                pointfile.unpack_into(slot.chunk_dev[:slot.nbytes], slot.desc_dev, slot.offs_dev, npts, slot.xyz_dev, slot.fstatus_dev)
+                slot.fstatus_pin.copy_(slot.fstatus_dev, non_blocking=True)
             # (FPS: one ops.compress_batch; DBSCAN: projection, ground fit, dbscan_segment, ops.compress_batch_labels)
             bc.run_batch(slot.xyz_dev[:npts], slot.offs_dev, slot.ground, slot.buf, frame_ids=slot.fid_dev, max_rows=slot.hid_rows)
             bits, seq, nseq = ops.contour_encode(slot.buf.seg, bc.M, ws=slot.codec_ws)
@@ -261,6 +354,9 @@ class StreamingCompressor:
     def _collect(self, slot):
         slot.enq.result()                       # the enqueue thread has issued the batch (raises what it raised)
         slot.done.synchronize()
+        if slot.fields and slot.fstatus_pin.numpy()[:slot.n].any():      # (the workers validated every header: not expected)
+            raise ValueError("librpcc_fields.so refused the layout of frame(s) %s of the batch"
+                             % ", ".join(str(i) for i in np.nonzero(slot.fstatus_pin.numpy()[:slot.n])[0]))
         if slot.status_pin is not None:   # a frame DBSCAN gave more labels than max_labels (or a capped union-find): raise as collect() does
             self.bc.check_status(slot.status_pin.numpy()[:slot.n])
         if slot.int_pin is not None:

@@ -84,7 +84,7 @@ def init_gather_group(rank, world, local):
 
 
 def resolve_ingest(want, names, intensity=False, point_format=None, subpixel=False, hidden_points=False):
-    """The ingest mode of a whole datalist (--ingest, --intensity, --subpixel, --hidden_points, --input_format; names: its file names) -> "rows", "xyz" or "nclt";
+    """The ingest mode of a whole datalist (--ingest, --intensity, --subpixel, --hidden_points, --input_format; names: its file names) -> "rows", "xyz", "nclt" or "fields";
     SystemExit for a combination the options exclude.  --input_format nclt always stages the records themselves (8 bytes per point,
     the intensity byte among them), so it goes with --ingest auto only."""
     all_bin = all(str(name).endswith(".bin") for name in names)
@@ -92,6 +92,10 @@ def resolve_ingest(want, names, intensity=False, point_format=None, subpixel=Fal
         if want != "auto":
             raise SystemExit("--input_format nclt sends the 8-byte records to the device (ingest nclt) and does not go with --ingest %s" % want)
         return "nclt"
+    # .pcd / .ply files: their bytes go to the device as they are and pointfile.unpack writes 16-byte rows there, intensity included, so
+    # --intensity, --subpixel and --hidden_points go with it; a mixed list keeps the host path through load_data
+    if want == "auto" and len(names) > 0 and all(str(name).endswith((".pcd", ".ply")) for name in names):
+        return "fields"
     if intensity:      # the fourth column must reach the device: the rows as stored
         if not all_bin or want == "xyz":
             raise SystemExit("--intensity needs a datalist of .bin files (float32 rows x, y, z, intensity)" + (" and not --ingest xyz" if want == "xyz" else ""))
@@ -168,7 +172,7 @@ def compress(args, streaming_factory=None):
             for k, s in enumerate(range(0, len(mine), sc.B)):
                 names = [dataset.data_list[i] for i in mine[s:s + sc.B]]
                 names_of[k] = names
-                frames = names if ingest in ("rows", "nclt") else list(pool.map(dataset.load_data, names))     # paths: read in place by the loader
+                frames = names if ingest in ("rows", "nclt", "fields") else list(pool.map(dataset.load_data, names))     # paths: read in place by the loader
                 yield frames, [frame_identity(n) for n in names]
 
         def write_all(jobs):      # jobs: [(file name, bytes)]

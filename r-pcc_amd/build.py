@@ -37,6 +37,7 @@ RANS_SRC, RANS_DEPS, RANS_LIB = _side_library("csrc_rans", "rans_kernels.hip", "
 RECORDS_SRC, RECORDS_DEPS, RECORDS_LIB = _side_library("csrc_records", "records_kernels.hip", "rpcc_records.h", "librpcc_records.so")   # NCLT record unpack
 ROWS_SRC, ROWS_DEPS, ROWS_LIB = _side_library("csrc_rows", "rows_kernels.hip", "rpcc_rows.h", "librpcc_rows.so")   # decoded batch -> .bin rows
 FIELDS_SRC, FIELDS_DEPS, FIELDS_LIB = _side_library("csrc_fields", "fields_kernels.hip", "rpcc_fields.h", "librpcc_fields.so")   # .pcd / .ply record unpack
+CLOUD_SRC, CLOUD_DEPS, CLOUD_LIB = _side_library("csrc_cloud", "cloud_kernels.hip", "rpcc_cloud.h", "librpcc_cloud.so")   # image + hidden points -> .bin rows
 
 # -ffp-contract=off: the reference's C++ (projection, models, prediction, quantisation) is un-fused x86 SSE arithmetic and a
 # contracted FMA changes results.  (The reference's CUDA FPS kernel is a different matter: nvcc contracts its distance into
@@ -143,6 +144,11 @@ def build_fields(force=False, verbose=False):
     return _hipcc(FIELDS_SRC, FIELDS_LIB, FIELDS_DEPS, force, verbose)
 
 
+def build_cloud(force=False, verbose=False):
+    """librpcc_cloud.so: the .bin row packer for frames with extra points (csrc_cloud/), same flags and the same mtime rule as librpcc_hip.so."""
+    return _hipcc(CLOUD_SRC, CLOUD_LIB, CLOUD_DEPS, force, verbose)
+
+
 def build(force=False, verbose=False):
     try:
         build_host(force, verbose)
@@ -160,6 +166,7 @@ def build(force=False, verbose=False):
     build_records(force, verbose)
     build_rows(force, verbose)
     build_fields(force, verbose)
+    build_cloud(force, verbose)
     return _hipcc(SRC, LIB, DEPS, force, verbose)
 
 

@@ -445,14 +445,14 @@ class _DecodeSlot:
     """What one chunk in flight owns: its stream, the chunk-sized images it is decoded into, and the pinned buffers its results land in."""
 
     def __init__(self, bd, device):
-        n, P = bd.chunk, bd.T.H * bd.T.W
+        n, P = bd.chunk, bd.T.H * bd.T.W + getattr(bd, "hidden_capacity", 0)     # (hidden_points: the hidden points' rows behind the image's)
         self.stream = torch.cuda.Stream(device=device)
         with torch.cuda.device(device):
             self.images = bd.rows_buffers(n)
         self.status_pin = torch.empty((n,), dtype=torch.int32).pin_memory()
         self.offsets_pin = torch.empty((n + 1,), dtype=torch.int64).pin_memory()
         self.nonzero_pin = torch.empty((n,), dtype=torch.int32).pin_memory()
-        self.rows_pin = torch.empty((n * P, 4), dtype=torch.float32).pin_memory()     # every pixel kept: the most a chunk can hold
+        self.rows_pin = torch.empty((n * P, 4), dtype=torch.float32).pin_memory()     # every point kept: the most a chunk can hold
         self.small_done = torch.cuda.Event()
         self.rows_dev = None
         self.writes = []        # futures of the .bin files being written from rows_pin
@@ -463,12 +463,15 @@ class StreamingDecompressor:
     intensity); depth: chunks in flight, each on its own stream with its own pinned buffers; workers: host threads, which read the .rpcc
     files of later chunks and write the .bin files of earlier ones while the device works.  A chunk is bd.chunk frames: its containers go up
     in one copy, are decoded into chunk-sized images that never leave the device, and rows.pack turns those into the files' bytes --
-    status, offsets, non-zero counts and rows[:total] are all that comes back.  One process, no children."""
+    status, offsets, non-zero counts and rows[:total] are all that comes back.  One process, no children.
+    What is decoded follows from bd: a BatchDecompressor(device_trailers=True, hidden_points=True) decodes the hidden points into the
+    chunk-sized buffers too and cloud.pack puts their rows behind the image's; hidden_points=True here says the caller expects that."""
 
     def __init__(self, bd, depth=3, workers=None, pool=None, hidden_points=False):
-        if hidden_points:
+        if hidden_points and not (getattr(bd, "device_trailers", False) and getattr(bd, "hidden_points", False)):
             raise NotImplementedError("StreamingDecompressor: hidden_points -- the packed rows hold one point per pixel; decode containers with "
-                                      "the hidden_points trailer per frame (tools.decompress.decode_frame(..., hidden_points=True))")
+                                      "the hidden_points trailer per frame (tools.decompress.decode_frame(..., hidden_points=True)), or hand in a "
+                                      "BatchDecompressor(..., hidden_points=True, device_trailers=True)")
         self.bd, self.depth, self.device = bd, max(1, int(depth)), bd.device
         self.pool = pool or ThreadPoolExecutor(workers or min(32, available_cpus()))
         self.slots = [_DecodeSlot(bd, self.device) for _ in range(self.depth)]

@@ -9,8 +9,8 @@ import torch
 
 from . import entropy, ops
 from . import _lib
-from .compress_utils import (BACKENDS, BEAM_TABLE_HIDDEN, BEAM_TABLE_INTENSITY, BEAM_TABLE_SUBPIXEL, BasicCompressor, BatchPayload, columns, device_decoder, frame_slices, intensity_trailer_span,
-                             pack_bitstream, pack_frames, payload_spans, unpack_bitstream)  # noqa: F401
+from .compress_utils import (BACKENDS, BEAM_TABLE_HIDDEN, BEAM_TABLE_INTENSITY, BEAM_TABLE_SUBPIXEL, HIDDEN_COLUMN, SCHEMA, TRAILERS, BasicCompressor, BatchPayload, columns, device_decoder,
+                             frame_slices, intensity_trailer_span, pack_bitstream, pack_frames, payload_spans, unpack_bitstream)  # noqa: F401
 
 
 class BatchCompressor:
@@ -496,7 +496,11 @@ STREAM_TEXT = {_lib.STREAM_E_ENTROPY: "an entropy stream was refused by the devi
                _lib.STREAM_E_RESIDUAL: "residual_quantized does not hold one value per non-empty pixel of the label map",
                _lib.STREAM_E_CONTAINER: "the container's length prefixes do not fit its bytes",
                _lib.STREAM_E_INTENSITY: "no valid intensity payload follows the geometry (compressed without intensity, or the payload does not fit the label map; a "
-                                        "container that also carries the subpixel trailer gives its intensity on the per-frame path only)"}
+                                        "container that also carries the subpixel trailer gives its intensity on the per-frame path only)",
+               _lib.STREAM_E_SUBPIXEL: "no valid subpixel payload follows the geometry where the trailers asked for place it (compressed without --subpixel, or "
+                                       "the payload does not fit the label map or holds a code past its bits)",
+               _lib.STREAM_E_HIDDEN: "no valid hidden_points payload follows the geometry where the trailers asked for place it (compressed without "
+                                     "--hidden_points, or the payload does not fit the label map, or it holds more points than hidden_capacity)"}
 
 
 def container_spans(blob, uniform=True):
@@ -518,23 +522,37 @@ class BatchDecompressor:
     device_entropy / device_bunzip2 flags of a BasicCompressor handed in say: those govern the per-frame path.
     DBSCAN streams size their label count per frame (cluster_num=None, as decode_frame takes it): with max_labels=N they are decoded under the
     label cap N - 1 -- rpcc_decompress_batch takes a frame's row count from its plane payload -- with decode_frame(..., None, ...)'s refusals; a
-    frame with more rows than the cap is decoded once more through decode_frame.  Label maps come back in the cap's dtype."""
+    frame with more rows than the cap is decoded once more through decode_frame.  Label maps come back in the cap's dtype.
+    device_trailers=True (opt-in) decodes the subpixel and hidden_points trailers here as well; without it the two
+    are refused by name and every result is what it was before the flag existed."""
 
     CHUNK_FRAMES = 32              # frames per chunk at most, as the datalist tool reads them
     CHUNK_BUDGET_BYTES = 2 << 30   # device bytes one chunk may take: padded payloads, bzip2 work slots, work buffer and outputs
 
     def __init__(self, transformer, cluster_num, accuracy, uniform=True, level_acc=None, basic_compressor="bzip2", max_labels=None,
-                 intensity=False, subpixel=False, hidden_points=False):
+                 intensity=False, subpixel=False, hidden_points=False, device_trailers=False, hidden_capacity=None):
         """intensity=True: every container must carry the 'intensity' trailer (BatchCompressor(intensity_scale=...), --intensity):
         decompress_device returns a fifth tensor, f32 [B,H,W], decompress 4-tuples; a frame without a valid trailer gets
-        _lib.STREAM_E_INTENSITY (unless an earlier status applies) and a zero row.  The scale is read from each payload's header."""
-        if subpixel:
+        _lib.STREAM_E_INTENSITY (unless an earlier status applies) and a zero row.  The scale is read from each payload's header.
+        device_trailers=True: subpixel=True and hidden_points=True are taken too, alone, together and with intensity.  What follows a
+        container's geometry must then be exactly the trailers asked for, in file order, ending the blob (unpack_bitstream's rule).
+        subpixel: pc_rec holds the turned points.  hidden_points: decompress_device also returns (hidden f32 [B,cap,3], hidden_count i32 [B])
+        last, decompress returns points [P + m, 3]; hidden_capacity (None: P) is the cap, the hidden points per frame this path holds -- a
+        frame with more comes back through decode_frame like any E_HIDDEN frame, so no sound container fails because of it.  A frame's
+        status is the first that is not OK of: its geometry status (E_ENTROPY when one of its trailers' streams was refused by the entropy
+        decoder), E_INTENSITY, E_SUBPIXEL, E_HIDDEN; a refused frame's images are zeros and its hidden count is 0."""
+        self.device_trailers = bool(device_trailers)
+        if subpixel and not self.device_trailers:
             raise NotImplementedError("BatchDecompressor: subpixel -- the batch decoder back-projects along the pixels' centre rays; decode "
-                                      "containers with the subpixel trailer per frame (tools.decompress.decode_frame(..., subpixel=True))")
-        if hidden_points:
+                                      "containers with the subpixel trailer per frame (tools.decompress.decode_frame(..., subpixel=True)), or "
+                                      "pass device_trailers=True")
+        if hidden_points and not self.device_trailers:
             raise NotImplementedError("BatchDecompressor: hidden_points -- the batch decoder returns one point per pixel; decode containers "
-                                      "with the hidden_points trailer per frame (tools.decompress.decode_frame(..., hidden_points=True))")
-        self.intensity = bool(intensity)
+                                      "with the hidden_points trailer per frame (tools.decompress.decode_frame(..., hidden_points=True)), or "
+                                      "pass device_trailers=True")
+        self.intensity, self.subpixel, self.hidden_points = bool(intensity), bool(subpixel), bool(hidden_points)
+        if self.subpixel:
+            transformer.subpixel_tables()     # (a per-beam elevation table: NotImplementedError, as on the per-frame path)
         self.per_frame_rows = cluster_num is None     # DBSCAN streams
         if cluster_num is None:
             if max_labels is None:
@@ -560,6 +578,12 @@ class BatchDecompressor:
         self.ns = len(self.cols)
         self.caps = [c.bound(P, K) for c in self.cols]
         self.trailer_cap = columns(self.uniform, True)[-1].bound(P, K)
+        self.hidden_capacity = (P if hidden_capacity is None else int(hidden_capacity)) if self.hidden_points else 0
+        if self.hidden_capacity < 0:
+            raise ValueError("BatchDecompressor: hidden_capacity %d" % self.hidden_capacity)
+        # the trailers asked for, in file order, and the decoded bytes a stream of each can have: 8 + P, 8 + 2P, 16 + P + 4 hidden_capacity
+        self.trailers = tuple(t for t, on in zip(TRAILERS, (self.intensity, self.subpixel, self.hidden_points)) if on)
+        self.trailer_caps = {"intensity": self.trailer_cap, "subpixel": SCHEMA[6].bound(P, K), "hidden_points": HIDDEN_COLUMN.bound(P, K, self.hidden_capacity)}
         self.chunk = max(1, min(self.CHUNK_FRAMES, self.CHUNK_BUDGET_BYTES // self._frame_bytes()))
 
     def _frame_bytes(self):
@@ -569,7 +593,10 @@ class BatchDecompressor:
         outs = P * (2 if ops.is_wide(self.M) else 1) + 4 * P + 12 * P
         ws = -(-_lib.lib().rpcc_decompress_workspace_bytes(self.CHUNK_FRAMES, P, self.M) // self.CHUNK_FRAMES)
         inten = (2 * t + 4 * P + self.work_bytes(b"BZh9", t)) if self.intensity else 0   # coded + decoded trailer, the f32 image, its work slot
-        return sum(self.caps) + 5 * 256 + work + outs + ws + inten
+        # the other trailers alike (the subpixel points are pc_rec's); the hidden points [cap,3] and their count
+        more = sum(2 * c + self.work_bytes(b"BZh9", c) for c in (self.trailer_caps[t] for t in self.trailers if t != "intensity"))
+        more += (12 * self.hidden_capacity + 4) if self.hidden_points else 0
+        return sum(self.caps) + 5 * 256 + work + outs + ws + inten + more
 
     def _descriptors(self, m, addr, lens, dst_off, dst_cap, heads):
         """The six descriptor rows decode_slots takes, [addr | lens | dst_off | dst_cap | work_off | work_cap], into m (host i64 [6, n]): the
@@ -629,8 +656,9 @@ class BatchDecompressor:
         # the parts as [B, ...] arrays of their columns' dtypes; the last four in file order are decompress_batch's first four arguments
         typed = [dst[int(part[i]): int(part[i]) + B * row[i]].view(getattr(torch, c.dtype.name)).view(B, -1) for i, c in enumerate(self.cols)]
         bits, seq, model, q16 = typed[-4:]
+        # (subpixel: no centre-ray points -- ops.subpixel_decode writes the turned ones into out[3] below)
         ops.decompress_batch(bits, seq, model.view(B, K, 4), q16, plen, pest, self.T.tm_dev, self.accuracy if self.uniform else self.level_acc,
-                             H, W, salience=None if self.uniform else typed[0], out=out[:4])
+                             H, W, salience=None if self.uniform else typed[0], out=out[:3] + (None,) if self.subpixel else out[:4])
         if len(bad):
             out[0][meta[6 * n + len(sound): 6 * n + B]] = _lib.STREAM_E_CONTAINER
         if self.per_frame_rows and not self.uniform:
@@ -642,35 +670,91 @@ class BatchDecompressor:
             for o in out[1:]:
                 if o is not None:   # a refused frame's rows are zero (uint16 label maps: through their int16 view)
                     (o.view(torch.int16) if o.dtype == torch.uint16 else o).masked_fill_(late.view((B,) + (1,) * (o.dim() - 1)), 0)
-        if self.intensity:
-            self._chunk_intensity(blobs, arrays, base, offs, out)
+        if self.trailers:
+            self._chunk_trailers(blobs, arrays, base, offs, out)
 
-    def _chunk_intensity(self, blobs, arrays, base, offs, out):
-        """intensity=True: the chunk's trailers through one more decode_slots call into a [B, 8+P] array, then ops.intensity_decode on the
-        label maps just decoded.  A frame without a (valid) trailer, or whose geometry was refused, keeps its earlier status or gets
-        STREAM_E_INTENSITY, and a zero row."""
-        B, dev, row = len(blobs), self.device, self.trailer_cap
-        spans = [intensity_trailer_span(b, self.uniform) for b in blobs]
+    def _trailer_spans(self, blob):
+        """(start, length) of the coded bytes of every trailer asked for, in file order, or None.  device_trailers: unpack_bitstream's rule --
+        what follows the geometry is exactly these trailers, ending the blob.  Without it: intensity_trailer_span's one-trailer rule."""
+        if not self.device_trailers:
+            sp = intensity_trailer_span(blob, self.uniform)
+            return None if sp is None else [(sp[0], sp[1] - sp[0])]
+        tail, nt = list(payload_spans(blob, self.ns + len(TRAILERS)))[self.ns:], len(self.trailers)
+        return tail[:nt] if len(tail) >= nt and sum(tail[nt - 1]) == len(blob) else None
+
+    def _tables(self, needed):
+        """The device copy of the subpixel tables; None where a hidden_points decoder has none to give (a per-beam elevation table: a frame
+        with lateral codes is then refused, E_HIDDEN, and decode_frame says why)."""
+        try:
+            return self.T.subpixel_tables()
+        except NotImplementedError:
+            if needed:
+                raise
+            return None
+
+    def _chunk_trailers(self, blobs, arrays, base, offs, out):
+        """The chunk's wanted trailers: one more decode_slots call writes every one of them into a padded [B, bound] array of its own, then
+        ops.intensity_decode / ops.subpixel_decode / ops.hidden_decode run on the label maps and ranges just decoded.  Without
+        device_trailers (intensity alone): a frame without a (valid) trailer, or whose geometry was refused, keeps its earlier status or
+        gets STREAM_E_INTENSITY, and a zero row.  With it: a frame's status is the first that is not OK of geometry (E_ENTROPY when the
+        entropy decoder refused one of its trailers), E_INTENSITY, E_SUBPIXEL, E_HIDDEN, and a refused frame's outputs are all zeros."""
+        B, dev, want, nt = len(blobs), self.device, self.trailers, len(self.trailers)
+        row = np.array([self.trailer_caps[t] for t in want], np.int64)
+        part = np.zeros(nt + 1, np.int64)
+        part[1:] = np.cumsum((B * row + 255) // 256 * 256)       # a part per trailer, B rows of its bound, every part 256-aligned
+        spans = [self._trailer_spans(b) for b in blobs]
         have = [i for i, sp in enumerate(spans) if sp is not None]
         n = len(have)
-        nbytes = torch.zeros((B,), dtype=torch.int32, device=dev)     # 0: no trailer, refused by rpcc_intensity_decode
-        pay = torch.empty((B, row), dtype=torch.uint8, device=dev)
+        nbytes = torch.zeros((nt, B), dtype=torch.int32, device=dev)     # 0: no trailer, refused by the payload decoders
+        refused = torch.zeros((B,), dtype=torch.bool, device=dev)        # a trailer's stream the entropy decoder refused
+        pay = torch.empty(int(part[-1]), dtype=torch.uint8, device=dev)
         if n:
             fr = np.array(have, np.int64)
-            sp = np.array([spans[i] for i in have], np.int64)
-            meta_h = torch.empty((7, n), dtype=torch.int64, pin_memory=True)
+            sp = np.array([spans[i] for i in have], np.int64).reshape(n, nt, 2)
+            meta_h = torch.empty((7, n * nt), dtype=torch.int64, pin_memory=True)
             m = meta_h.numpy()
-            wtotal = self._descriptors(m, base + offs[fr] + sp[:, 0], sp[:, 1] - sp[:, 0], fr * row, row, [arrays[i][s: s + min(e - s, 4)] for i, (s, e) in zip(have, sp)])
-            m[6] = fr
+            wtotal = self._descriptors(m, (base + offs[fr][:, None] + sp[:, :, 0]).reshape(-1), sp[:, :, 1].reshape(-1),
+                                       (part[None, :nt] + fr[:, None] * row[None, :]).reshape(-1), np.tile(row, n),
+                                       [arrays[i][s: s + min(l, 4)] for i in have for s, l in spans[i]])
+            m[6] = np.repeat(fr, nt)
             meta = meta_h.to(dev, non_blocking=True)
             work = torch.empty(wtotal, dtype=torch.uint8, device=dev) if wtotal else None
-            dst_len, est = self.decode_slots([meta[k] for k in range(6)], pay.view(-1), work)
-            nbytes[meta[6]] = torch.where(est == 0, dst_len, torch.zeros_like(dst_len)).to(torch.int32)
-        status, seg, inten = out[0], out[1], out[4]
-        _, ist = ops.intensity_decode(pay, nbytes, seg, out=inten)
-        bad = status != _lib.STREAM_OK
-        inten.masked_fill_(bad.view(B, 1, 1), 0)
-        status.copy_(torch.where(bad, status, ist))
+            dst_len, est = self.decode_slots([meta[k] for k in range(6)], pay, work)
+            ok, idx = (est == 0).view(n, nt), meta[6].view(n, nt)[:, 0]
+            nbytes[:, idx] = torch.where(ok, dst_len.view(n, nt), torch.zeros_like(dst_len.view(n, nt))).to(torch.int32).t()
+            if self.device_trailers:
+                refused[idx] = ~ok.all(1)
+        rows = {t: pay[int(part[k]): int(part[k]) + B * int(row[k])].view(B, int(row[k])) for k, t in enumerate(want)}
+        nb = {t: nbytes[k] for k, t in enumerate(want)}
+        status, seg, rec = out[:3]
+        if not self.device_trailers:
+            inten = out[4]
+            _, ist = ops.intensity_decode(rows["intensity"], nb["intensity"], seg, out=inten)
+            bad = status != _lib.STREAM_OK
+            inten.masked_fill_(bad.view(B, 1, 1), 0)
+            status.copy_(torch.where(bad, status, ist))
+            return
+        st = torch.where((status == _lib.STREAM_OK) & refused, torch.full_like(status, _lib.STREAM_E_ENTROPY), status)
+        outs = [seg, rec]
+        if self.intensity:
+            _, tst = ops.intensity_decode(rows["intensity"], nb["intensity"], seg, out=out[4])
+            st = torch.where(st != _lib.STREAM_OK, st, tst)
+            outs.append(out[4])
+        if self.subpixel:    # (a caller that wants no points still wants the payload's verdict, as decode_frame gives it)
+            pc = out[3] if out[3] is not None else torch.empty((B,) + tuple(rec.shape[1:]) + (3,), dtype=torch.float32, device=dev)
+            _, tst = ops.subpixel_decode(rows["subpixel"], nb["subpixel"], seg, rec, self._tables(True), out=pc)
+            st = torch.where(st != _lib.STREAM_OK, st, tst)
+        if out[3] is not None:
+            outs.append(out[3])
+        if self.hidden_points:
+            hid, count = out[-2], out[-1]
+            _, _, tst = ops.hidden_decode(rows["hidden_points"], nb["hidden_points"], seg, self.T.tm_dev, self._tables(False), out=hid, count=count)
+            st = torch.where(st != _lib.STREAM_OK, st, tst)
+            outs.append(count)
+        status.copy_(st)
+        bad = st != _lib.STREAM_OK
+        for o in outs:      # a refused frame's rows are zero (uint16 label maps: through their int16 view)
+            (o.view(torch.int16) if o.dtype == torch.uint16 else o).masked_fill_(bad.view((B,) + (1,) * (o.dim() - 1)), 0)
 
     def upload(self, blobs):
         """The containers' bytes on the device, a chunk per copy, for decompress_device(blobs, uploaded=...): callers that hold the containers
@@ -686,6 +770,8 @@ class BatchDecompressor:
                torch.empty((B, H, W), dtype=torch.float32, device=dev), torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_points else None)
         if self.intensity:
             out += (torch.empty((B, H, W), dtype=torch.float32, device=dev),)
+        if self.hidden_points:
+            out += (torch.empty((B, self.hidden_capacity, 3), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev))
         with torch.cuda.device(dev):
             for c0 in range(0, B, self.chunk):
                 c1 = min(c0 + self.chunk, B)
@@ -697,7 +783,9 @@ class BatchDecompressor:
         H, W, dev = self.T.H, self.T.W, self.device
         out = (torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n, H, W), dtype=ops.label_dtype(self.M), device=dev),
                torch.empty((n, H, W), dtype=torch.float32, device=dev), torch.empty((n, H, W, 3), dtype=torch.float32, device=dev))
-        return out + ((torch.empty((n, H, W), dtype=torch.float32, device=dev),) if self.intensity else ())
+        out += (torch.empty((n, H, W), dtype=torch.float32, device=dev),) if self.intensity else ()
+        return out + ((torch.empty((n, self.hidden_capacity, 3), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
+                      if self.hidden_points else ())
 
     def decompress_rows_device(self, blobs, uploaded=None, images=None):
         """The .bin rows of the batch instead of its images (rows.py, librpcc_rows.so).  -> (status i32 [B], offsets i64 [B+1], rows f32 [B*H*W,4],
@@ -705,11 +793,11 @@ class BatchDecompressor:
         to back (a refused frame has no rows), nonzero[b] its pixels with a range != 0; with intensity=True the fourth column is the decoded
         intensity, else +0.0.  Each chunk is decoded into the same chunk-sized images (images: rows_buffers(self.chunk) of the caller's, else
         allocated here) and packed behind the chunk before: no image of the batch exists, here or on the host."""
-        from . import rows as R
+        from . import cloud, rows as R
         B, P, dev = len(blobs), self.T.H * self.T.W, self.device
         status = torch.empty((B,), dtype=torch.int32, device=dev)
         offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
-        out_rows = torch.empty((B * P, 4), dtype=torch.float32, device=dev)
+        out_rows = torch.empty((B * (P + self.hidden_capacity), 4), dtype=torch.float32, device=dev)   # (hidden_points: cloud.pack, the hidden points behind the image's)
         nonzero = torch.empty((B,), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             images = self.rows_buffers(min(self.chunk, B)) if images is None and B else images
@@ -718,7 +806,11 @@ class BatchDecompressor:
                 n = min(self.chunk, B - c0)
                 out = tuple(o[:n] for o in images)
                 self._chunk_device(blobs[c0: c0 + n], out, None if uploaded is None else uploaded[c0 // self.chunk])
-                table, _, _ = R.pack(out[3], out[4] if self.intensity else None, out[2], rows=out_rows, nonzero=nonzero[c0: c0 + n], base=base)
+                if self.hidden_points:
+                    table, _, _ = cloud.pack(out[3], out[4] if self.intensity else None, out[2], extra=out[-2], extra_count=out[-1], rows=out_rows,
+                                             nonzero=nonzero[c0: c0 + n], base=base)
+                else:
+                    table, _, _ = R.pack(out[3], out[4] if self.intensity else None, out[2], rows=out_rows, nonzero=nonzero[c0: c0 + n], base=base)
                 status[c0: c0 + n] = out[0]
                 offsets[c0: c0 + n + 1] = table[: n + 1]
                 base = table[n: n + 1]
@@ -728,17 +820,19 @@ class BatchDecompressor:
         """A frame the device decoder refused with a status decompress() falls back on: once more through decode_frame with the host library,
         its rows by the numpy rule.  -> (rows f32 [n,4], nonzero).  Any other status, and what the host library refuses too: ValueError."""
         from . import rows as R
-        from .tools.decompress import decode_frame
+        from .tools.decompress import decode_frame, point_intensity
+        flags = dict(intensity=self.intensity, subpixel=self.subpixel, hidden_points=self.hidden_points)
         try:
-            rec, pc, _, *w = decode_frame(unpack_bitstream(blob, self.uniform, intensity=self.intensity), self.host_bc, self.T, self.cluster_num,
-                                          self.accuracy, self.level_acc, self.uniform, intensity=self.intensity)
+            rec, pc, _, *w = decode_frame(unpack_bitstream(blob, self.uniform, **flags), self.host_bc, self.T, self.cluster_num,
+                                          self.accuracy, self.level_acc, self.uniform, **flags)
         except (ValueError, OSError, EOFError) as e:
             raise ValueError("frame %d: %s" % (index, e)) from e
-        return R.pack_host(pc, w[0] if w else None), int((rec != 0).sum())
+        return R.pack_host(pc, (point_intensity(w[0], pc) if self.hidden_points else w[0]) if w else None), int((rec != 0).sum())
 
     def falls_back(self, st):
-        """decompress()'s rule: E_ENTROPY, and E_PLANE on a DBSCAN stream (more rows than the cap), go through the per-frame path."""
-        return st == _lib.STREAM_E_ENTROPY or (st == _lib.STREAM_E_PLANE and self.per_frame_rows)
+        """decompress()'s rule: E_ENTROPY, E_PLANE on a DBSCAN stream (more rows than the cap) and E_HIDDEN (more points than hidden_capacity
+        on a sound payload; what is damaged the per-frame path refuses in words) go through the per-frame path."""
+        return st == _lib.STREAM_E_ENTROPY or (st == _lib.STREAM_E_PLANE and self.per_frame_rows) or st == _lib.STREAM_E_HIDDEN
 
     def refusal(self, st, index):
         return ValueError("frame %d: %s (status %d)" % (index, STREAM_TEXT.get(int(st), "refused"), int(st)))
@@ -770,16 +864,20 @@ class BatchDecompressor:
         res = []
         for c0 in range(0, len(blobs), self.chunk):
             part = blobs[c0: c0 + self.chunk]
+            flags = dict(intensity=self.intensity, subpixel=self.subpixel, hidden_points=self.hidden_points)
             status, seg, rec, pc, *w = (None if t is None else t.cpu().numpy() for t in self.decompress_device(part, want_points))
             for i, st in enumerate(status):
                 if st == _lib.STREAM_OK:
-                    res.append((rec[i], pc[i] if pc is not None else None, seg[i]) + ((w[0][i],) if self.intensity else ()))
+                    pts = pc[i] if pc is not None else None
+                    if self.hidden_points and pts is not None:     # decode_frame's [P + m, 3]: the image points, then the hidden points
+                        pts = np.concatenate([pts.reshape(-1, 3), w[-2][i, : int(w[-1][i])]])
+                    res.append((rec[i], pts, seg[i]) + ((w[0][i],) if self.intensity else ()))
                     continue
-                if st != _lib.STREAM_E_ENTROPY and not (st == _lib.STREAM_E_PLANE and self.per_frame_rows):   # (more rows than the cap: per frame)
+                if not self.falls_back(st):   # (more rows than the cap, more hidden points than the cap: per frame)
                     raise ValueError("frame %d: %s (status %d)" % (c0 + i, STREAM_TEXT.get(int(st), "refused"), int(st)))
                 try:
-                    res.append(decode_frame(unpack_bitstream(part[i], self.uniform, intensity=self.intensity), self.host_bc, self.T, self.cluster_num,
-                                            self.accuracy, self.level_acc, self.uniform, want_points=want_points, intensity=self.intensity))
+                    res.append(decode_frame(unpack_bitstream(part[i], self.uniform, **flags), self.host_bc, self.T, self.cluster_num,
+                                            self.accuracy, self.level_acc, self.uniform, want_points=want_points, **flags))
                 except (ValueError, OSError, EOFError) as e:
                     raise ValueError("frame %d: %s" % (c0 + i, e)) from e
         return res

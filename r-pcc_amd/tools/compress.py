@@ -54,6 +54,10 @@ def make_parser(datalist=False):
                        help="decompress_datalist.py: --batch_decode with several chunks in flight (loader.StreamingDecompressor): the .bin rows are "
                             "packed on the device and only they cross the link, while host threads read later files and write earlier ones; the "
                             "output files are the same.  Implies --batch_decode.")
+        p.add_argument("--device_trailers", action="store_true",
+                       help="decompress_datalist.py --batch_decode / --stream_decode: decode the --subpixel and --hidden_points trailers on the "
+                            "batch path as well (pipeline.BatchDecompressor(device_trailers=True)); without it the two are refused there and "
+                            "decoded per frame.  The output files are the same.")
         p.add_argument("--max_labels", type=int, default=None,
                        help="segment_method DBSCAN: the largest label a frame may use in the batch kernels (default and at most 1023; up to 255: "
                             "byte labels on the device).  compress_datalist.py refuses a frame with more; decompress_datalist.py --batch_decode "

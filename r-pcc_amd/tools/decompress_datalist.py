@@ -32,8 +32,11 @@ def decompress_batched(args, dataset, mine, cluster_num, accuracy, level_acc, un
     from rpcc_amd.pipeline import BatchDecompressor
     # (DBSCAN streams: cluster_num None -- the label count is the frame's; the batch decodes them under a label cap)
     cap = (getattr(args, "max_labels", None) or 1023) if cluster_num is None else None
+    # (--device_trailers: the subpixel and hidden_points trailers on this path too; without it decompress() has refused them by now)
+    trailers = dict(subpixel=getattr(args, "subpixel", None) is not None, hidden_points=getattr(args, "hidden_points", False),
+                    device_trailers=True) if getattr(args, "device_trailers", False) else {}
     bd = BatchDecompressor(dataset.PCTransformer, cluster_num, accuracy, uniform=uniform, level_acc=level_acc, basic_compressor=basic_compressor,
-                           max_labels=cap, intensity=getattr(args, "intensity", False))
+                           max_labels=cap, intensity=getattr(args, "intensity", False), **trailers)
     if getattr(args, "stream_decode", False):
         return decompress_streamed(args, bd, [dataset.data_list[i] for i in mine])
     for c0 in range(0, len(mine), CHUNK):
@@ -45,7 +48,7 @@ def decompress_batched(args, dataset, mine, cluster_num, accuracy, level_acc, un
         for name, (rec, pc, _, *w) in zip(names, bd.decompress(blobs)):
             out = output_path(args, name)
             os.makedirs(os.path.dirname(out), exist_ok=True)
-            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3), intensity=w[0].reshape(-1) if w else None)
+            dataset.save_point_cloud_to_file(out, pc.reshape(-1, 3), intensity=(point_intensity(w[0], pc) if bd.hidden_points else w[0].reshape(-1)) if w else None)
             if args.output:
                 print("%s -> %s (%d points)" % (name, out, int((rec != 0).sum())))
 
@@ -58,20 +61,21 @@ def decompress_streamed(args, bd, names):
     outs = [output_path(args, name) for name in names]
     report = (lambda i, rows, nonzero: print("%s -> %s (%d points)" % (names[i], outs[i], nonzero))) if args.output else None
     workers = int(getattr(args, "workers", 1) or 1)
-    StreamingDecompressor(bd, workers=workers if workers > 1 else None).run(names, outs, on_frame=report)
+    StreamingDecompressor(bd, workers=workers if workers > 1 else None, hidden_points=bd.hidden_points).run(names, outs, on_frame=report)
 
 
 def decompress(args):
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
-    if getattr(args, "batch_decode", False) and getattr(args, "subpixel", None) is not None:     # (before anything is read or built)
+    refused = getattr(args, "batch_decode", False) and not getattr(args, "device_trailers", False)
+    if refused and getattr(args, "subpixel", None) is not None:     # (before anything is read or built)
         raise NotImplementedError("--%s with --subpixel: the batch decoder back-projects along the pixels' centre rays; decode containers with "
-                                  "the subpixel trailer without --batch_decode / --stream_decode (the per-frame path)"
+                                  "the subpixel trailer without --batch_decode / --stream_decode (the per-frame path), or add --device_trailers"
                                   % ("stream_decode" if getattr(args, "stream_decode", False) else "batch_decode"))
-    if getattr(args, "batch_decode", False) and getattr(args, "hidden_points", False):
+    if refused and getattr(args, "hidden_points", False):
         raise NotImplementedError("--%s with --hidden_points: the batch decoder returns one point per pixel; decode containers with the "
-                                  "hidden_points trailer without --batch_decode / --stream_decode (the per-frame path)"
+                                  "hidden_points trailer without --batch_decode / --stream_decode (the per-frame path), or add --device_trailers"
                                   % ("stream_decode" if getattr(args, "stream_decode", False) else "batch_decode"))
     cfg, accuracy, segment_cfg, model_cfg, basic_compressor, uniform = resolve_cfg(args)
     # (--input_format: how the dataset reads original point files; this tool reads none, its outputs are float .bin files either way)
